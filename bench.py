@@ -15,6 +15,15 @@ ends -- nothing to compute before the first column group is up, fewer co-runners
 on the round-5 path (11.11 / 11.17 ms per proof against 11.06 / 11.04 at 60 and 11.02 / 11.05 at 100, one box;
 tools/inflight_timeline.py), and 60 proofs are 0.7 s of GPU time.
 
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what `value` and `ms_per_step` need: it builds the
+traces, warms up, times the K proofs and prints the line.  Everything else described here -- the comparison legs above,
+the profiled proof behind `roofline` and `kernel_ms`, the proof checks (oracle verifier, zk_verify, the committed pin),
+the CPU baseline, the run at the other hardware-queue count, and the sharded sub-record of a multi-rank run -- runs
+with --full (which --no-compare, --no-verify, --no-cpu-baseline, --ab and --sharded-log-n 0 trim as before).
+--dump-outputs DIR writes what the timed steps returned: the proof bytes of the last timed step (DIR/proof.npy) and of
+every input set they proved (DIR/proof_set<i>.npy), float32 with one value per byte; the workload is seeded, so the
+same arguments give the same inputs on every run and two builds can be compared file by file.
+
 Proofs in flight (--inflight P, default 3): each GPU holds P independent provers (own HBM buffers and
 compute streams, zk_prover objects; one upload stream per device) driven by P host threads, so one prover's trace
 upload, host-side transcript round trips and proof tail overlap the others' kernels.  P + 1 streams fit HIP's
@@ -363,6 +372,16 @@ def run_proofs_timed(fns, count: int, pg, local: int) -> float:
     return max_over_ranks(pg, time.perf_counter() - t0, local)
 
 
+def dump_outputs(directory, proofs: dict):
+    """--dump-outputs: what the timed path returned to its caller -- proof bytes -- as DIR/<name>.npy, float32 with one
+    value per byte (exact).  The workload is seeded, so two builds run with the same arguments write comparable files."""
+    d = Path(directory)
+    d.mkdir(parents=True, exist_ok=True)
+    for name, proof in proofs.items():
+        if proof is not None:
+            np.save(d / f"{name}.npy", np.frombuffer(proof, dtype=np.uint8).astype(np.float32))
+
+
 def pmc_valu(kernel: str):
     """Hardware VALU issue of the kernel from the committed rocprofv3 SQ/GRBM pass (tools/pmc_valu.py):
     SQ_INSTS_VALU over the 1024 SIMDs' 2-cycle issue slots (a plain wave64 VALU instruction takes one) --
@@ -419,7 +438,18 @@ def main():
     ap.add_argument("--torch-runtime", action="store_true",
                     help="import torch before the library (runtime A/B only): the library then runs on torch's bundled "
                          "HIP runtime and RCCL instead of the /opt/rocm copies it links")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the comparison legs, the profiled proof (roofline, per-kernel times), the "
+                         "proof checks (oracle, zk_verify, pin), the CPU baseline, the other queue count and, with "
+                         "several ranks, the sharded sub-record (--no-compare, --no-verify, --no-cpu-baseline, --ab and "
+                         "--sharded-log-n 0 trim it); a plain run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the proof bytes of the last timed step as DIR/proof.npy and of "
+                         "every input set the timed steps proved as DIR/proof_set<i>.npy (float32, one value per byte)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the headline alone
+        args.no_compare = args.no_verify = args.no_cpu_baseline = True
+        args.sharded_log_n = 0
     if args.torch_runtime:
         import torch  # noqa: F401  (maps torch/lib/libamdhip64.so first; the library shares it)
     # HIP's hardware queues per process: whatever the environment gives (the runtime's default is 4, which the GPU
@@ -486,11 +516,14 @@ def main():
     set_proofs = [None] * S
     nxt = [0]
     lock = threading.Lock()
+    # --dump-outputs: the proof of the timed step dealt last, and the input sets the timed steps proved
+    dumped = {"on": False, "step": -1, "proof": None, "sets": set()}
 
     def rotating_step(k):
         def f():
             with lock:
-                i = nxt[0] % S
+                j = nxt[0]
+                i = j % S
                 nxt[0] += 1
             tr, pb = sets[i]
             pr = provers[k].prove_host(tr, pb, opts)[0]
@@ -499,6 +532,10 @@ def main():
                     set_proofs[i] = pr
                 elif set_proofs[i] != pr:
                     raise AssertionError(f"input set {i}: two proofs of the same trace differ")
+                if dumped["on"]:
+                    dumped["sets"].add(i)
+                    if j > dumped["step"]:
+                        dumped["step"], dumped["proof"] = j, pr
             if i == 0:
                 last[k] = pr
         return f
@@ -511,7 +548,12 @@ def main():
     # tools/proof_times.py); the default is three per prover
     warm = args.warmup if args.warmup is not None else 3 * P
     run_proofs(fns, warm)
+    dumped["on"] = args.dump_outputs is not None
     elapsed = run_proofs_timed(fns, args.steps, pg, local)
+    dumped["on"] = False
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, {"proof": dumped["proof"],
+                                         **{f"proof_set{i}": set_proofs[i] for i in sorted(dumped["sets"])}})
     proof = set_proofs[0]
     assert proof is not None and all(p_ == proof for p_ in last if p_ is not None), \
         "provers disagree on the proof bytes"
@@ -563,21 +605,26 @@ def main():
         latency_ms = 1e3 * sorted(lat)[len(lat) // 2]
     stages = gpu.stage_times()
 
-    # one extra, untimed, profiled proof: per-kernel device time (HIP events on the prover stream), on the schedule the
-    # timed proofs ran (it runs alone, which AUTO would give the latency schedule's smaller launches)
-    gpu.set_upload_schedule(timed_sched)
-    gpu.profile(True)
-    gpu.prove_host(trace, pub, opts)
-    kstats = gpu.kernel_stats()
-    kops = gpu.kernel_ops()
-    gpu.profile(False)
-    gpu.set_upload_schedule(args.upload_schedule)
-    upst = gpu.upload_stats()  # that proof's trace upload (sparse / narrow hints learned from the proofs before it)
+    kstats = kops = None
+    if args.full:
+        # one extra, untimed, profiled proof: per-kernel device time (HIP events on the prover stream), on the schedule
+        # the timed proofs ran (it runs alone, which AUTO would give the latency schedule's smaller launches)
+        gpu.set_upload_schedule(timed_sched)
+        gpu.profile(True)
+        gpu.prove_host(trace, pub, opts)
+        kstats = gpu.kernel_stats()
+        kops = gpu.kernel_ops()
+        gpu.profile(False)
+        gpu.set_upload_schedule(args.upload_schedule)
+    # the trace upload of this prover's last proof (sparse / narrow hints learned from the proofs before it): with
+    # --full the profiled proof's, else its last timed one's
+    upst = gpu.upload_stats()
     upload = {"mb_per_proof": round(upst["bytes"] / 2**20, 1), "full_trace_mb": round(28 * n * 16 / 2**20, 1),
               "sparse_cols": upst["sparse"], "narrow8_cols": upst["narrow8"], "narrow32_cols": upst["narrow32"],
               "derived_cols": upst["derived"],
-              "schedule": {"timed_proofs": timed_sched, "profiled_proof": timed_sched,
-                           "latency_leg": args.upload_schedule if args.upload_schedule != "auto" else "latency"}}
+              "schedule": {"timed_proofs": timed_sched, "profiled_proof": timed_sched if args.full else None,
+                           "latency_leg": None if not args.full else
+                           args.upload_schedule if args.upload_schedule != "auto" else "latency"}}
 
     verified = None
     if rank == 0 and not args.no_verify:
@@ -589,16 +636,19 @@ def main():
         C.memmove(opub.stack_outputs, bytes(pub.stack_outputs), 256)
         opub.lwe_size, opub.delta = pub.lwe_size, pub.delta
         verified = orc.verify(proof, opub, min_sec)[0] == 0
-    from zkvm_amd.prover import verify as zk_verify
-    zk_verified = zk_verify(proof, pub, min_sec)[0] == 0
+    zk_verified = pin = all_verified = None
+    if args.full:
+        from zkvm_amd.prover import verify as zk_verify
+        zk_verified = zk_verify(proof, pub, min_sec)[0] == 0
     gpu.close()
     lifetime = None
     if not args.no_compare and not args.ab:
         lifetime = lifetime_leg(local, n, trace, pub, opts, proof)
-    # every rank: its proof accepted by zk_verify; rank 0's workload (seed 1000) is a committed oracle pin, so its
-    # proof must also equal the pin byte for byte (the other ranks' seeds have no pin)
-    pin = pin_check(proof, find_pin(args.log_n, 1000 + rank, opts))
-    all_verified = all_ranks_true(pg, zk_verified, local)
+    if args.full:
+        # every rank: its proof accepted by zk_verify; rank 0's workload (seed 1000) is a committed oracle pin, so its
+        # proof must also equal the pin byte for byte (the other ranks' seeds have no pin)
+        pin = pin_check(proof, find_pin(args.log_n, 1000 + rank, opts))
+        all_verified = all_ranks_true(pg, zk_verified, local)
     cpu = None
     if world == 1 and rank == 0 and not args.no_cpu_baseline:
         # the reported CPU baseline: one single-thread oracle proof of the headline workload's own trace (input set
@@ -707,7 +757,7 @@ def queues_leg(args, P):
     import subprocess
     other = "16" if os.environ.get("GPU_MAX_HW_QUEUES", "4") == "4" else "4"
     env = dict(os.environ, GPU_MAX_HW_QUEUES=other)
-    cmd = [sys.executable, str(ROOT / "bench.py"), "--no-cpu-baseline", "--no-verify", "--no-compare",
+    cmd = [sys.executable, str(ROOT / "bench.py"), "--full", "--no-cpu-baseline", "--no-verify", "--no-compare",
            "--sharded-log-n", "0", "--inflight", str(P), "--steps", str(args.steps), "--log-n", str(args.log_n)]
     if args.config5:
         cmd.append("--config5")
@@ -824,7 +874,45 @@ def vm_prove_leg(args, prog, src, w, proof, provers, opts, pg, local, rank):
 def build_line(args, rank, world, n, elapsed, warm, opts, opts_str, min_sec, P, program_ops, padded_ops, latency_ms,
                dev_s, pag_s, steady_s, cmp_steps, stages, kstats, kops, vm_rec, proof, verified, zk_verified, pin,
                all_verified, lifetime, cpu):
-    """rank 0's JSON line (the driver's contract) from the measurements of main()."""
+    """rank 0's JSON line (the driver's contract) from the measurements of main().  kstats / kops are None in a plain
+    run (no profiled proof): the line then carries no roofline and no per-kernel figures."""
+    roofline = roofline_record(args, kstats, kops) if kstats else None
+    kstats = kstats or {}
+    value = world * n * args.steps / elapsed
+    out = {
+        "metric": METRIC, "value": round(value, 1), "unit": "trace-steps/s", "n_gpus": world, "steps": args.steps,
+        "warmup": warm, "ms_per_step": round(1e3 * elapsed / args.steps, 3), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f128", "data": "synthetic (seeded VM trace)",
+        "full": bool(args.full),
+        "config": {"workload": f"configs[{4 if args.config5 else 2}]: 2^{args.log_n}-step READ2/ADD2/SMUL cipher-mix program, "
+                               f"full prove from the host-resident trace" +
+                               (" at 128-bit conjectured security" if args.config5 else ""),
+                   "trace_len": n, "trace_width": 28, "lde_len": n * opts.blowup_factor,
+                   "program_ops": program_ops, "padded_ops": padded_ops,
+                   "options": opts_str, "timed_region": "zk_prove_columns: page-locked host trace -> proof bytes",
+                   "parallelism": f"independent proofs, {P} in flight per GPU, x{world} GPUs",
+                   "host_numa_node": HOST["numa_node"]},
+        "security_bits_checked": min_sec if args.full else None,
+        "latency_ms": round(latency_ms, 3) if latency_ms is not None else None,
+        "device_resident_ms": round(1e3 * dev_s / cmp_steps, 3) if dev_s is not None else None,
+        "pageable_host_ms": round(1e3 * pag_s / cmp_steps, 3) if pag_s is not None else None,
+        "steady_state_ms": round(1e3 * steady_s / STEADY_PROOFS, 3) if steady_s is not None else None,
+        "roofline": roofline, "cpu_baseline": cpu,
+        "stage_ms": {k: round(v, 3) for k, v in stages.items()},
+        "kernel_ms": {k: round(v[0], 3) for k, v in sorted(kstats.items(), key=lambda kv: -kv[1][0])},
+        "kernel_launches": {k: v[1] for k, v in kstats.items()},
+        "kernel_alg_bytes": {k: v[2] for k, v in kstats.items()},
+        "vm": vm_rec,
+        "proof_bytes": len(proof), "proof_verified_by_oracle": verified, "proof_verified_by_zk_verify": zk_verified,
+        "proof_matches_pin": pin["proof_matches_pin"] if pin else None, "pin": pin["pin"] if pin else None,
+        "all_ranks_verified_by_zk_verify": all_verified,
+        "prover_lifetime": lifetime,
+    }
+    return out
+
+
+def roofline_record(args, kstats, kops):
+    """The line's `roofline` from the profiled proof's per-kernel stats (kernel_stats / kernel_ops)."""
     dom = max(kstats.items(), key=lambda kv: kv[1][0])
     name, (tot_ms, launches, tot_bytes) = dom
     avg_ms = tot_ms / launches
@@ -863,36 +951,7 @@ def build_line(args, rank, world, n, elapsed, warm, opts, opts_str, min_sec, P, 
             "achieved_fe_mul_per_s": round(muls / (tot_ms / 1e3), 1), "peak_fe_mul_per_s": FE_MUL_PEAK,
             "floor_ms_per_launch": round(floor_ms / launches, 4), "frac_vs_build_fe_mul_cost": round(floor_ms / tot_ms, 4)}
     roofline["valu_hw"] = hw
-    value = world * n * args.steps / elapsed
-    out = {
-        "metric": METRIC, "value": round(value, 1), "unit": "trace-steps/s", "n_gpus": world, "steps": args.steps,
-        "warmup": warm, "ms_per_step": round(1e3 * elapsed / args.steps, 3), "higher_is_better": True,
-        "scaling": "weak", "vs_baseline": None, "dtype": "f128", "data": "synthetic (seeded VM trace)",
-        "config": {"workload": f"configs[{4 if args.config5 else 2}]: 2^{args.log_n}-step READ2/ADD2/SMUL cipher-mix program, "
-                               f"full prove from the host-resident trace" +
-                               (" at 128-bit conjectured security" if args.config5 else ""),
-                   "trace_len": n, "trace_width": 28, "lde_len": n * opts.blowup_factor,
-                   "program_ops": program_ops, "padded_ops": padded_ops,
-                   "options": opts_str, "timed_region": "zk_prove_columns: page-locked host trace -> proof bytes",
-                   "parallelism": f"independent proofs, {P} in flight per GPU, x{world} GPUs",
-                   "host_numa_node": HOST["numa_node"]},
-        "security_bits_checked": min_sec,
-        "latency_ms": round(latency_ms, 3) if latency_ms is not None else None,
-        "device_resident_ms": round(1e3 * dev_s / cmp_steps, 3) if dev_s is not None else None,
-        "pageable_host_ms": round(1e3 * pag_s / cmp_steps, 3) if pag_s is not None else None,
-        "steady_state_ms": round(1e3 * steady_s / STEADY_PROOFS, 3) if steady_s is not None else None,
-        "roofline": roofline, "cpu_baseline": cpu,
-        "stage_ms": {k: round(v, 3) for k, v in stages.items()},
-        "kernel_ms": {k: round(v[0], 3) for k, v in sorted(kstats.items(), key=lambda kv: -kv[1][0])},
-        "kernel_launches": {k: v[1] for k, v in kstats.items()},
-        "kernel_alg_bytes": {k: v[2] for k, v in kstats.items()},
-        "vm": vm_rec,
-        "proof_bytes": len(proof), "proof_verified_by_oracle": verified, "proof_verified_by_zk_verify": zk_verified,
-        "proof_matches_pin": pin["proof_matches_pin"] if pin else None, "pin": pin["pin"] if pin else None,
-        "all_ranks_verified_by_zk_verify": all_verified,
-        "prover_lifetime": lifetime,
-    }
-    return out
+    return roofline
 
 
 def sharded_leg(args, log_n, world, rank, local, pg, steps, warmup, config5=False):
@@ -1030,6 +1089,8 @@ def run_sharded(args):
     native.lib()
     warm = args.warmup if args.warmup is not None else 3
     rec = sharded_leg(args, args.log_n, world, rank, local, pg, args.steps, warm, args.config5)
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, {"proof": rec["proof"]})
     verified = None
     if rank == 0 and not args.no_verify:
         import ctypes as C

@@ -56,6 +56,16 @@ def test_model_record_reads_the_committed_projection():
     assert bench.model_record(22, 8, True, {"device": 1.0}) is None   # configs[4]: not modelled
 
 
+def test_dump_outputs_writes_proof_bytes_as_float32(tmp_path):
+    import numpy as np
+    proof = bytes(range(256)) * 3 + b"\x00\xff"
+    bench.dump_outputs(tmp_path / "out", {"proof": proof, "proof_set1": proof[:7], "proof_set2": None})
+    assert sorted(p.name for p in (tmp_path / "out").iterdir()) == ["proof.npy", "proof_set1.npy"]
+    a = np.load(tmp_path / "out" / "proof.npy")
+    assert a.dtype == np.float32 and a.shape == (len(proof),)
+    assert a.astype(np.uint8).tobytes() == proof  # one value per byte, exact
+
+
 def test_all_ranks_true_single_process():
     assert bench.all_ranks_true(None, True, 0) is True
     assert bench.all_ranks_true(None, False, 0) is False

@@ -10,7 +10,7 @@ for v in "$@"; do
   i=$((i + 1))
   envs=()
   [ "$v" != "-" ] && read -r -a envs <<< "$v"
-  env "${envs[@]}" timeout -k 10 300 python3 bench.py --no-cpu-baseline --no-verify --steps ${STEPS:-10} --warmup 2 ${BENCH_ARGS:-} \
+  env "${envs[@]}" timeout -k 10 300 python3 bench.py --full --no-cpu-baseline --no-verify --steps ${STEPS:-10} --warmup 2 ${BENCH_ARGS:-} \
     > "$O/abenv_$i.json" 2> "$O/abenv_$i.err" || { echo "$v FAILED"; tail -5 "$O/abenv_$i.err"; exit 1; }
   python3 - "$v" "$O/abenv_$i.json" <<'PY'
 import json, sys

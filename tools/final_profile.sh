@@ -7,7 +7,7 @@ TAG=${1:-final}
 R=$(pwd)
 O=$R/gpurun_out
 bash tools/gpu_profile.sh "$TAG" tests bench
-timeout -k 10 400 python3 bench.py --log-n 22 --steps 6 --inflight 1 --no-cpu-baseline --no-compare --sharded-log-n 0 \
+timeout -k 10 400 python3 bench.py --full --log-n 22 --steps 6 --inflight 1 --no-cpu-baseline --no-compare --sharded-log-n 0 \
   > "$O/bench_2p22_$TAG.json" 2> "$O/bench_2p22_$TAG.err" || { tail -20 "$O/bench_2p22_$TAG.err"; exit 1; }
 echo "2^22 ok"
 cd /tmp && export TMPDIR=/tmp

@@ -9,7 +9,7 @@ mkdir -p "$O"
 timeout -k 10 600 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread > "$O/gpu_tests_$TAG.log" 2>&1 \
   || { tail -40 "$O/gpu_tests_$TAG.log"; exit 1; }
 tail -1 "$O/gpu_tests_$TAG.log"
-timeout -k 10 300 python3 bench.py --no-cpu-baseline "$@" > "$O/bench_$TAG.json" 2> "$O/bench_$TAG.err" \
+timeout -k 10 300 python3 bench.py --full --no-cpu-baseline "$@" > "$O/bench_$TAG.json" 2> "$O/bench_$TAG.err" \
   || { tail -20 "$O/bench_$TAG.err"; exit 1; }
 python3 - "$O/bench_$TAG.json" <<'PY'
 import json, sys

@@ -10,7 +10,7 @@ timeout -k 10 1000 python -u -m pytest tests -m gpu -x -v --timeout 300 --timeou
 rc=$?
 grep -E "passed|failed|error" $O/gpu_tests_$TAG.log | tail -3
 [ $rc -eq 0 ] || { grep -E "FAILED|Error|error" $O/gpu_tests_$TAG.log | head -20; exit $rc; }
-timeout -k 10 400 python3 bench.py --no-cpu-baseline "$@" > $O/bench_$TAG.json 2> $O/bench_$TAG.err
+timeout -k 10 400 python3 bench.py --full --no-cpu-baseline "$@" > $O/bench_$TAG.json 2> $O/bench_$TAG.err
 rc=$?
 tail -2 $O/bench_$TAG.err
 exit $rc

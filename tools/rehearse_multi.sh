@@ -7,7 +7,7 @@ N=${1:-2}
 O=gpurun_out
 mkdir -p "$O"
 ZK_BENCH_REHEARSE=1 timeout -k 10 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" \
-  --master-addr 127.0.0.1 --master-port 29517 bench.py --gpus "$N" --steps 8 --warmup 2 \
+  --master-addr 127.0.0.1 --master-port 29517 bench.py --full --gpus "$N" --steps 8 --warmup 2 \
   > "$O/rehearse_$N.json" 2> "$O/rehearse_$N.err"
 python3 - "$O/rehearse_$N.json" <<'PY'
 import json, sys
