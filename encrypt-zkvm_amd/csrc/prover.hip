@@ -22,6 +22,7 @@
 #include <cstdlib>
 #include <map>
 #include <memory>
+#include <new>
 #include <string>
 #include <vector>
 
@@ -427,6 +428,10 @@ void zk_prover_destroy(zk_prover *p) {
     if (p->h_vm) (void)hipHostFree(p->h_vm);
     if (p->sp_h) (void)hipHostFree(p->sp_h);
     if (p->h_pack) (void)hipHostFree(p->h_pack);
+    for (auto &s : p->fix_snaps) {
+        (void)hipFree(s.fpolys);
+        (void)hipFree(s.flde);
+    }
     delete p->open;
     delete p;
 }
@@ -550,6 +555,10 @@ int zk_prover_proof_info(const zk_prover *p, zk_proof_info *out) {
     for (const auto &h : p->hint_sets) out->hint_sets += h.n != 0 && h.have ? 1u : 0u;
     out->hinted_sparse = p->sp_hinted;
     out->derived = p->clk_used ? 1u : 0u;
+    for (int i = 0; i < zk_prover::ZK_FIXED_SNAPS; i++) {
+        const auto &s = p->fix_snaps[i];
+        out->fixed_sets += s.live && s.owner >= 0 && p->hint_sets[s.owner].snap == i ? 1u : 0u;
+    }
     return ZK_OK;
 }
 
@@ -566,6 +575,12 @@ int zk_prover_upload_stats(zk_prover *p, uint64_t *bytes, uint32_t *sparse_cols,
 int zk_prover_upload_derived(zk_prover *p, uint32_t *derived_cols) {
     if (!p || !derived_cols) ZK_FAIL(ZK_ERR_INVALID_ARG, "null argument");
     *derived_cols = p->clk_used ? 1u : 0u;
+    return ZK_OK;
+}
+
+int zk_prover_upload_fixed(zk_prover *p, uint32_t *fixed_cols) {
+    if (!p || !fixed_cols) ZK_FAIL(ZK_ERR_INVALID_ARG, "null argument");
+    *fixed_cols = p->fix_used;
     return ZK_OK;
 }
 
@@ -1206,7 +1221,84 @@ struct TraceSrc {
     bool hint_ok = true;               // host columns: the sparse hint of the previous proof may be used
     bool no_virtual = false;           // every trace LDE column written (stage dumps read them)
     const uint8_t *key = nullptr;      // host columns: the program hash the hints are keyed by (with n)
+    uint32_t lwe = 0;                  // ... and its lwe_size (the fixed columns depend on it too)
 };
+
+// Fixed columns (zk_prover::FixedSnap).  ZK_FIXED=0 turns the class off.
+bool zk::fixed_on() {
+    static const bool on = [] {
+        const char *e = getenv("ZK_FIXED");
+        return !(e && !strcmp(e, "0"));
+    }();
+    return on;
+}
+constexpr uint32_t ZK_FIXED_CAND = 0xFFEu;  // columns 1 .. 11
+
+// forget snapshot i (its device buffers stay allocated for the next snapshot of that size)
+static void fixed_drop(zk_prover *p, int i) {
+    if (i < 0) return;
+    zk_prover::FixedSnap &s = p->fix_snaps[i];
+    if (s.owner >= 0 && p->hint_sets[s.owner].snap == i) p->hint_sets[s.owner].snap = -1;
+    s.live = false;
+    s.owner = -1;
+    s.mask = 0;
+    for (auto &h : s.host) h.reset();
+    if (p->fix_pending == i) p->fix_pending = -1;
+}
+
+// A snapshot slot for hint set `owner` with buffers for k planes of n and B n elements: a free slot (one whose
+// buffers already have that size first), else the least recently used one.  -1 if the memory is not to be had.
+static int fixed_slot(zk_prover *p, int owner, size_t n, uint32_t B, int k) {
+    const size_t np = (size_t)k * n, nl = np * B;
+    int best = -1;
+    for (int i = 0; i < zk_prover::ZK_FIXED_SNAPS; i++) {
+        const auto &s = p->fix_snaps[i];
+        if (s.live) continue;
+        if (best < 0 || (s.cap_polys == np && s.cap_lde == nl)) best = i;
+    }
+    if (best < 0) {
+        best = 0;
+        for (int i = 1; i < zk_prover::ZK_FIXED_SNAPS; i++)
+            if (p->fix_snaps[i].used < p->fix_snaps[best].used) best = i;
+        fixed_drop(p, best);
+    }
+    zk_prover::FixedSnap &s = p->fix_snaps[best];
+    if (s.cap_polys != np || s.cap_lde != nl) {
+        // (the previous proofs on this prover have drained: nothing reads the old buffers)
+        (void)hipFree(s.fpolys);
+        (void)hipFree(s.flde);
+        s.fpolys = s.flde = nullptr;
+        s.cap_polys = s.cap_lde = 0;
+        if (hipMalloc((void **)&s.fpolys, np * sizeof(fe)) != hipSuccess ||
+            hipMalloc((void **)&s.flde, nl * sizeof(fe)) != hipSuccess) {
+            (void)hipGetLastError();
+            (void)hipFree(s.fpolys);
+            s.fpolys = s.flde = nullptr;
+            return -1;
+        }
+        s.cap_polys = np;
+        s.cap_lde = nl;
+    }
+    s.owner = owner;
+    s.n = n;
+    s.B = B;
+    s.k = k;
+    return best;
+}
+
+// rows [r0, r1) of a host column against a snapshot's host copy
+bool zk::same_rows(const uint8_t *col, const uint8_t *snap, size_t r0, size_t r1, int width) {
+    if (width == 16) return !memcmp(col + 16 * r0, snap + 16 * r0, 16 * (r1 - r0));
+    const uint64_t *v = reinterpret_cast<const uint64_t *>(col);
+    uint64_t bad = 0;
+    if (width == 1) {
+        for (size_t i = r0; i < r1; i++) bad |= (v[2 * i] ^ (uint64_t)snap[i]) | v[2 * i + 1];
+    } else {
+        const uint32_t *s = reinterpret_cast<const uint32_t *>(snap);
+        for (size_t i = r0; i < r1; i++) bad |= (v[2 * i] ^ (uint64_t)s[i]) | v[2 * i + 1];
+    }
+    return bad == 0;
+}
 
 // The hint set of (n, program), or null (prover state: zk_prover::HintSet)
 static zk_prover::HintSet *hint_find(zk_prover *p, size_t n, const uint8_t *key) {
@@ -1222,6 +1314,7 @@ static zk_prover::HintSet *hint_slot(zk_prover *p, size_t n, const uint8_t *key)
     h = &p->hint_sets[0];
     for (auto &e : p->hint_sets)
         if (e.used < h->used) h = &e;
+    fixed_drop(p, h->snap);  // an evicted set's snapshot goes with it
     *h = zk_prover::HintSet{};
     h->n = n;
     memcpy(h->key, key, 32);
@@ -1450,7 +1543,7 @@ static int trace_lde_commit(zk_prover *p, Plan *pl, const TraceSrc &src, size_t 
     // last row: nothing goes up but that value), and its narrow ones (8- or 32-bit values before the last row), which
     // go up packed.  Host threads check every hinted value while the other columns go up: a narrow column that does
     // not fit goes up whole, a sparse one that is not sparse voids the proof (prove_impl redoes it without hints).
-    const zk_prover::HintSet *H = sp && src.hint_ok ? hint_find(p, n, src.key) : nullptr;
+    zk_prover::HintSet *H = sp && src.hint_ok ? hint_find(p, n, src.key) : nullptr;
     const bool fresh = H && H->have;
     const uint32_t hint = fresh ? H->sparse : 0u;
     const uint32_t nw8 = fresh && narrow_on() ? H->nw8 & ~hint : 0u;
@@ -1464,15 +1557,34 @@ static int trace_lde_commit(zk_prover *p, Plan *pl, const TraceSrc &src, size_t 
     if (clk) nw32 &= ~1u;
     p->clk_used = clk;
     p->clk_bad = false;
+    // Fixed columns (zk_prover::FixedSnap): with this hint set's snapshot, the columns it holds (but the ones hinted
+    // sparse, which keep their own path) are formed from it and checked by host threads; without one, this proof
+    // takes it once its LDE is written (below)
+    zk_prover::FixedSnap *FS = nullptr;
+    const bool fix_ok = fresh && fixed_on() && !H->fixed_off;
+    if (fix_ok && H->snap >= 0) {
+        zk_prover::FixedSnap &s = p->fix_snaps[H->snap];
+        if (s.live && s.n == n && s.B == B && s.lwe == src.lwe) FS = &s;
+        else fixed_drop(p, H->snap);  // taken for another blowup or lwe_size: taken again
+    }
+    const uint32_t fixm = FS ? FS->mask & ~hint : 0u;
+    const bool snap_now = fix_ok && !FS;
+    if (FS) FS->used = ++p->hint_stamp;
+    p->fix_used = fixm;
+    p->fix_bad = false;
+    p->fix_pending = -1;
     const uint32_t virt = !src.no_virtual && virtual_on() ? hint & ~((1u << ZK_VIRT_MIN_COL) - 1u) : 0u;
     p->virt = 0;  // (set once the hinted columns' last rows are on the device)
     p->sp_hinted = hint;
     p->up_bytes = 0;
     p->up_sparse = hint;
-    p->up_nw8 = p->up_nw32 = 0;
+    // (a narrow column taken as fixed stays listed under its narrow class; none of its bytes cross the link)
+    p->up_nw8 = nw8 & fixm;
+    p->up_nw32 = nw32 & fixm;
     int dense[W], nd = 0, hin[W], nh = 0, nar[W], nn = 0;
     for (int c = 0; c < W; c++) {
         if (clk && c == 0) continue;
+        if ((fixm >> c) & 1u) continue;
         if ((hint >> c) & 1u) hin[nh++] = c;
         else if (((nw8 | nw32) >> c) & 1u) nar[nn++] = c;
         else dense[nd++] = c;
@@ -1560,17 +1672,20 @@ static int trace_lde_commit(zk_prover *p, Plan *pl, const TraceSrc &src, size_t 
         pb[2] = nn;
         np = pb[1] < nn ? 2 : 1;
     }
-    Latch packed[W], checked, clocked;
+    Latch packed[W], checked, clocked, compared, copied;
+    std::atomic<uint32_t> fixed_bad{0}, copy_bad{0};
     struct PackWait {
         Latch *parts;
         const int &np;
-        Latch &b, &c;
+        Latch &b, &c, &d, &e;
         ~PackWait() {
             for (int k = 0; k < np; k++) parts[k].wait();
             b.wait();
             c.wait();
+            d.wait();
+            e.wait();
         }
-    } pack_wait{packed, np, checked, clocked};
+    } pack_wait{packed, np, checked, clocked, compared, copied};
     constexpr size_t R = (size_t)1 << 18;
     const size_t per = (n - 1 + R - 1) / R;
     const size_t Rp = lat ? (size_t)1 << 16 : R, perp = (n - 1 + Rp - 1) / Rp;  // packing task rows
@@ -1658,6 +1773,39 @@ static int trace_lde_commit(zk_prover *p, Plan *pl, const TraceSrc &src, size_t 
         axpy_fill(p->st, pl->id_poly, pl->lagr, d, n, p->polys);
         axpy_fill(p->st, pl->id_lde, pl->lagr_lde, d, B * n, p->lde);
         ready[0] = true;
+    }
+    if (fixm) {
+        // the fixed columns: the snapshot's f_c plus last[c] times e_(n-1)'s coefficients / LDE, in one pass each; only
+        // the last-row values go up.  Their BLAKE3 blocks (0 .. 2 when the clock is derived too) start at once.
+        if (!p->fix_ws) ZK_CHECK_HIP(p->arena.alloc(&p->fix_ws, W));
+        fe_ws ws[W];
+        memset(ws, 0, sizeof ws);
+        FixedColList L;
+        for (int c = 0; c < W; c++) {
+            if (!((fixm >> c) & 1u)) continue;
+            fe last;
+            memcpy(&last, src.cols[c] + (n - 1) * sizeof(fe), sizeof(fe));
+            ws[c] = make_fe_ws(last);
+            L.col[L.count] = (uint8_t)c;
+            L.slot[L.count] = FS->slot[c];
+            L.count++;
+        }
+        ZK_TRY(h2d_small(p, p->fix_ws, ws, sizeof ws));
+        fixed_cols_axpy(p->st, L, false, FS->fpolys, FS->flde, pl->lagr, pl->lagr_lde, p->fix_ws, n, B, p->polys, p->lde);
+        for (int k = 0; k < L.count; k++) ready[L.col[k]] = true;
+        hash_ready(false);
+        // the host check: every row 0 .. n-2 of the caller's columns against the snapshot's host copy
+        compared.reset((int)(per * L.count));
+        for (int k = 0; k < L.count; k++)
+            for (size_t t = 0; t < per; t++) {
+                const size_t r0 = t * R, r1 = std::min(n - 1, r0 + R);
+                const int c = L.col[k], width = FS->width[c];
+                const uint8_t *col = src.cols[c], *snap = FS->host[c].get();
+                HostPool::get().submit([=, &fixed_bad, &compared] {
+                    if (!same_rows(col, snap, r0, r1, width)) fixed_bad.fetch_or(1u << c);
+                    compared.count_down();
+                });
+            }
     }
     // Upload items, each one copy (or a run of column copies) and an event on the shared upload stream: the wide
     // columns in groups of 4, the last 4 as 2 + 2 (after the last copy only 2 columns' NTTs, the last hash blocks and
@@ -1804,10 +1952,69 @@ static int trace_lde_commit(zk_prover *p, Plan *pl, const TraceSrc &src, size_t 
     hash_ready(true);
     merkle_tree(p->st, p->leaves, n * B, p->nodes);
     if (sp) ZK_TRY(d2h_small(p, p->sp_h, p->sp_nz, 3 * W * sizeof(unsigned)));  // for the next proof's hints
+    // The snapshot of the fixed class: f_c = column - last[c] e_(n-1), coefficients and LDE, from this proof's own polys
+    // and LDE, and rows 0 .. n-2 of the caller's columns for the later proofs' host check (narrow ones packed; one
+    // whose values do not fit its class is left out).  Memory that is not to be had turns the class off for this hint
+    // set; it never fails the proof.
+    const uint32_t cand = snap_now ? ZK_FIXED_CAND & ~hint : 0u;
+    if (cand) {
+        const int owner = (int)(H - p->hint_sets);
+        const int si = fixed_slot(p, owner, n, (uint32_t)B, __builtin_popcount(cand));
+        bool ok = si >= 0;
+        zk_prover::FixedSnap *s = ok ? &p->fix_snaps[si] : nullptr;
+        FixedColList L;
+        fe_ws ws[W];
+        memset(ws, 0, sizeof ws);
+        for (int c = 0; ok && c < W; c++) {
+            if (!((cand >> c) & 1u)) continue;
+            s->width[c] = ((H->nw8 >> c) & 1u) ? 1 : ((H->nw32 >> c) & 1u) ? 4 : 16;
+            s->host[c].reset(new (std::nothrow) uint8_t[(size_t)s->width[c] * n]);
+            if (!s->host[c]) ok = false;
+            s->slot[c] = (uint8_t)L.count;
+            L.col[L.count] = (uint8_t)c;
+            L.slot[L.count] = (uint8_t)L.count;
+            L.count++;
+            fe last;
+            memcpy(&last, src.cols[c] + (n - 1) * sizeof(fe), sizeof(fe));
+            ws[c] = make_fe_ws(fe_sub(fe_zero(), last));
+        }
+        if (ok && !p->fix_ws && p->arena.alloc(&p->fix_ws, W) != hipSuccess) {
+            (void)hipGetLastError();
+            ok = false;
+        }
+        if (ok) {
+            ZK_TRY(h2d_small(p, p->fix_ws, ws, sizeof ws));
+            fixed_cols_axpy(p->st, L, true, p->polys, p->lde, pl->lagr, pl->lagr_lde, p->fix_ws, n, B, s->fpolys, s->flde);
+            copied.reset((int)(per * L.count));
+            for (int k = 0; k < L.count; k++)
+                for (size_t t = 0; t < per; t++) {
+                    const size_t r0 = t * R, r1 = std::min(n - 1, r0 + R);
+                    const int c = L.col[k], width = s->width[c];
+                    const uint8_t *col = src.cols[c];
+                    uint8_t *dst = s->host[c].get();
+                    HostPool::get().submit([=, &copy_bad, &copied] {
+                        if (width == 16) memcpy(dst + 16 * r0, col + 16 * r0, 16 * (r1 - r0));
+                        else if (!pack_rows(col, r0, r1, width, dst)) copy_bad.fetch_or(1u << c);
+                        copied.count_down();
+                    });
+                }
+            copied.wait();
+            s->mask = cand & ~copy_bad.load();
+            s->lwe = src.lwe;
+            s->live = true;
+            s->used = ++p->hint_stamp;
+            p->fix_pending = si;
+        } else {
+            if (si >= 0) fixed_drop(p, si);
+            H->fixed_off = true;
+        }
+    }
     checked.wait();
     clocked.wait();
+    compared.wait();
     p->sp_bad = sparse_bad.load();
     p->clk_bad = clock_bad.load() != 0;
+    p->fix_bad = fixed_bad.load() != 0;
     return d2h_small(p, root, p->nodes + 32, 32);
 }
 
@@ -1910,25 +2117,50 @@ static int prove_impl(zk_prover *p, const TraceSrc &src_in, size_t n, const zk_o
                       uint8_t *proof_out, size_t *proof_len, zk_record *rec, const zk_dump *dump) {
     TraceSrc src = src_in;
     if (dump) src.no_virtual = true;  // the stage dumps read every trace LDE column
-    if (src.cols && pub) src.key = &pub->program_hash[0][0];  // hints are per (n, program)
+    if (src.cols && pub) {
+        src.key = &pub->program_hash[0][0];  // hints are per (n, program)
+        src.lwe = pub->lwe_size;
+    }
+    p->fix_used = 0;
+    p->fix_bad = false;
+    p->fix_pending = -1;
     p->sp_used = false;
     p->sp_hinted = 0;
     p->sp_bad = 0;
     p->clk_used = p->clk_bad = false;
     const size_t cap = proof_len ? *proof_len : 0;  // (in/out: a voided attempt has overwritten it with its length)
     int rc = prove_once(p, src, n, opt, pub, proof_out, proof_len, rec, dump);
+    // the snapshot this proof took serves the next ones only if the proof stands
+    const bool voided = p->sp_bad || p->clk_bad || p->fix_bad;
+    if (p->fix_pending >= 0) {
+        const int si = p->fix_pending;
+        p->fix_pending = -1;
+        if (rc == ZK_OK && !voided && src.cols && p->sp_used) p->hint_sets[p->fix_snaps[si].owner].snap = si;
+        else fixed_drop(p, si);
+    }
     if (!src.cols || !p->sp_used) return rc;
-    if (p->sp_bad || p->clk_bad) {
-        // a hint of this (n, program) was refuted: forget its column classes (and stop speculating the clock for it if
-        // that was refuted), prove again from every column
+    // the classes the fixed columns were held under (they were not detected on the device this time)
+    uint32_t fix_cols = 0, fix_w8 = 0, fix_w32 = 0;
+    if (p->fix_used && !voided) {
+        const zk_prover::HintSet *h = hint_find(p, n, src.key);
+        fix_cols = p->fix_used;
+        if (h) fix_w8 = h->nw8 & fix_cols, fix_w32 = h->nw32 & fix_cols;
+    }
+    if (voided) {
+        // a hint of this (n, program) was refuted: forget its column classes (and stop speculating the clock or the
+        // fixed class for it if that was refuted) and its snapshot, prove again from every column
         zk_prover::HintSet *h = hint_find(p, n, src.key);
         if (h) {
             if (p->clk_bad) h->clk_off = true;
+            if (p->fix_bad) h->fixed_off = true;
+            fixed_drop(p, h->snap);
             h->have = false;
             h->sparse = h->nw8 = h->nw32 = 0;
         }
         p->hint_redos++;
         p->clk_used = p->clk_bad = false;
+        p->fix_used = 0;
+        p->fix_bad = false;
         TraceSrc s2 = src;
         s2.hint_ok = false;
         p->sp_used = false;
@@ -1950,6 +2182,9 @@ static int prove_impl(zk_prover *p, const TraceSrc &src_in, size_t n, const zk_o
             w8 &= ~1u;
             w32 |= 1u;
         }
+        found &= ~fix_cols;
+        w8 = (w8 & ~fix_cols) | fix_w8;
+        w32 = (w32 & ~fix_cols) | fix_w32;
         if (src.key) {
             zk_prover::HintSet *h = hint_slot(p, n, src.key);
             h->have = true;

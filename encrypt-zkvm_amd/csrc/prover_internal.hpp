@@ -208,10 +208,39 @@ struct zk_prover {
         bool have = false;     // sparse / nw8 / nw32 hold a completed proof's findings
         uint32_t sparse = 0, nw8 = 0, nw32 = 0;
         bool clk_off = false;  // this (n, program)'s traces refuted the clock derivation: not speculated again
+        bool fixed_off = false;  // ... or the fixed class (or its snapshot could not be allocated): not tried again
+        int snap = -1;         // its FixedSnap (fix_snaps index), or -1
         uint64_t used = 0;     // LRU stamp
     };
     static constexpr int ZK_HINT_SETS = 8;
     HintSet hint_sets[ZK_HINT_SETS];
+    // Fixed columns (host-resident traces, trace_lde_commit): columns 1 .. 11 (opcode bits, hash flag, sponge, stack
+    // depth) depend on the program and lwe_size only, up to the random last row, so each is f_c + last[c] e_(n-1) with
+    // f_c the same from proof to proof of one program.  The first proof of a hint set that runs with fresh hints (the
+    // prover's second of that program) snapshots f_c's coefficients and LDE from its own polys / LDE into device
+    // buffers (hipMalloc, outside the arena; kept for reuse when the snapshot is dropped) and keeps rows 0 .. n-2 of
+    // those columns on the host (8- / 32-bit columns packed).  Later proofs neither upload nor transform them: one
+    // streaming pass (fixed_cols_axpy) forms their polys and LDE, while host threads compare the caller's columns with
+    // the host copy.  A mismatch voids the proof (redone without hints) and turns the class off for that hint set.
+    // Two snapshots per prover, least recently used evicted; an evicted HintSet drops its own.
+    struct FixedSnap {
+        bool live = false;
+        int owner = -1;        // hint_sets index
+        size_t n = 0;
+        uint32_t B = 0, lwe = 0;
+        uint32_t mask = 0;     // the columns held; column c in plane slot[c]
+        int k = 0;             // planes held
+        uint8_t slot[zk::W] = {}, width[zk::W] = {};  // width: bytes per row of the host copy (1, 4 or 16)
+        fe *fpolys = nullptr, *flde = nullptr;        // k x n, k x B n (coset-major like the prover's LDE)
+        size_t cap_polys = 0, cap_lde = 0;            // elements allocated
+        std::unique_ptr<uint8_t[]> host[zk::W];
+        uint64_t used = 0;
+    };
+    static constexpr int ZK_FIXED_SNAPS = 2;
+    FixedSnap fix_snaps[ZK_FIXED_SNAPS];
+    int fix_pending = -1;      // the snapshot this proof took: kept if the proof completes unrefuted (prove_impl)
+    uint32_t fix_used = 0;     // the columns the last proof took as fixed (zk_prover_upload_fixed)
+    bool fix_bad = false;      // ... and the host compare refuted them
     uint64_t hint_stamp = 0;
     uint32_t hint_redos = 0;  // proofs voided by a refuted hint and redone (zk_prover_proof_info)
     uint32_t sp_hinted = 0, sp_bad = 0;
@@ -366,6 +395,20 @@ int prove_fixed(zk_prover *p, size_t n, const zk_options *opt, const zk_pub_inpu
 // polys / lde of the preprocessed columns (all but 12 .. 12 + md - 1): f_c + last[c] e_(n-1) (vm_gpu.hip); B: the LDE
 // cosets held (fx's flde / lagr_lde and lde alike)
 void fixed_axpy(hipStream_t st, const FixedCols &fx, const fe_ws *ws_dev, size_t n, size_t B, fe *polys, fe *lde);
+// The same pass for the host-trace fixed class (zk_prover::FixedSnap): `count` trace columns col[k], each with a compact
+// plane slot[k] of the snapshot.  Use: polys / lde column col[k] = snapshot plane slot[k] + ws_dev[col[k]] e_(n-1)'s.
+// snapshot: the other way, plane slot[k] of polys / lde (the snapshot's buffers) = column col[k] of src_polys / src_lde
+// + ws_dev[col[k]] e_(n-1)'s, ws_dev holding the NEGATED last row (exact: f_c = column - last[c] e_(n-1)).
+struct FixedColList {
+    int count = 0;
+    uint8_t col[W], slot[W];
+};
+void fixed_cols_axpy(hipStream_t st, const FixedColList &L, bool snapshot, const fe *src_polys, const fe *src_lde,
+                     const fe *lagr, const fe *lagr_lde, const fe_ws *ws_dev, size_t n, size_t B, fe *polys, fe *lde);
+bool fixed_on();
+// rows [r0, r1) of a host column against a snapshot's host copy (`width` bytes per row: 1 or 4 packed integers, or the
+// 16-byte elements themselves): true if every row holds the snapshot's value
+bool same_rows(const uint8_t *col, const uint8_t *snap, size_t r0, size_t r1, int width);
 // zk_vm_prove, before its host stack pass: fixed_axpy of fx into p->polys / p->lde and the BLAKE3 blocks of the rows'
 // first columns that hold no live stack register (0 .. 2: columns 0 .. 11), on p->st; sets p->fix_prefix_blocks
 int fixed_prefix(zk_prover *p, size_t n, uint32_t B, const FixedCols &fx);

@@ -196,16 +196,20 @@ __global__ void __launch_bounds__(256) k_vm_fixed(const Op *code, size_t len, co
     for (int i = 0; i < 4; i++) trace[(size_t)(7 + i) * n + r] = sponge[(size_t)i * (len + 1) + rr];
 }
 
-// the preprocessed columns (FixedCols): out[c][i] = F[src][i] (0 when src < 0) + last[c] base[i] for the ncol
-// columns listed, over `count` points of planes of `stride` (coefficients: n; LDE: B n).  Streaming, HBM-bound: per
-// point the Lagrange value once, then per column one read (nonzero f_c) and one write.
+// the preprocessed columns (FixedCols): out[col][i] = F[src][i] (0 when src < 0) + w[wsi] base[i] for the ncol entries
+// listed, over `count` points of planes of `stride` (coefficients: n; LDE: B n).  Streaming, HBM-bound: per point the
+// Lagrange value once, then per entry one read (nonzero f_c) and one write.  Entries are arbitrary: zk_vm_prove reads
+// plane c of its 12 preprocessed columns into column c; the host-trace fixed class (prover.hip) reads compact snapshot
+// slots into trace columns, and, to take a snapshot, trace columns into slots with w = -last (f_c = column - last e_(n-1)).
+// F, base and out never overlap.
 struct AxpyCols {
     int ncol;
     uint8_t col[W];
     int8_t src[W];
+    uint8_t wsi[W];
 };
-__global__ void __launch_bounds__(256) k_fixed_axpy(const fe *F, const fe *base, size_t stride, AxpyCols A,
-                                                    const fe_ws *ws, fe *out) {
+__global__ void __launch_bounds__(256) k_fixed_axpy(const fe *__restrict__ F, const fe *__restrict__ base, size_t stride,
+                                                    AxpyCols A, const fe_ws *__restrict__ ws, fe *__restrict__ out) {
     const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (i >= stride) return;
     const fe b = base[i];
@@ -213,7 +217,7 @@ __global__ void __launch_bounds__(256) k_fixed_axpy(const fe *F, const fe *base,
     for (int k = 0; k < W; k++) {
         if (k < A.ncol) {
             const int c = A.col[k], s = A.src[k];
-            const fe t = fe_mul_uniform(b, load_fe_ws(ws, c));
+            const fe t = fe_mul_uniform(b, load_fe_ws(ws, A.wsi[k]));
             out[(size_t)c * stride + i] = s >= 0 ? fe_add(F[(size_t)s * stride + i], t) : t;
         }
     }
@@ -438,6 +442,7 @@ void zk::fixed_axpy(hipStream_t st, const FixedCols &fx, const fe_ws *ws_dev, si
         if (c >= 12 && c < 12 + fx.md) continue;  // dynamic: interpolated and extended from the trace
         A.col[A.ncol] = (uint8_t)c;
         A.src[A.ncol] = (int8_t)(c < 12 ? c : -1);
+        A.wsi[A.ncol] = (uint8_t)c;
         A.ncol++;
     }
     const size_t nf = 12, nz = (size_t)A.ncol - nf;
@@ -447,6 +452,27 @@ void zk::fixed_axpy(hipStream_t st, const FixedCols &fx, const fe_ws *ws_dev, si
     ZK_PROF(st, "fixed_axpy", (double)B * n * 16 * (1 + 2 * nf + nz),
             hipLaunchKernelGGL(k_fixed_axpy, dim3((unsigned)((B * n + 255) / 256)), dim3(256), 0, st, fx.flde,
                                fx.lagr_lde, B * n, A, ws_dev, lde));
+}
+
+void zk::fixed_cols_axpy(hipStream_t st, const FixedColList &L, bool snapshot, const fe *src_polys, const fe *src_lde,
+                         const fe *lagr, const fe *lagr_lde, const fe_ws *ws_dev, size_t n, size_t B, fe *polys, fe *lde) {
+    if (L.count <= 0) return;
+    AxpyCols A;
+    A.ncol = L.count;
+    for (int k = 0; k < L.count; k++) {
+        // use: slot -> column; snapshot: column -> slot (ws_dev then holds the negated last row)
+        A.col[k] = (uint8_t)(snapshot ? L.slot[k] : L.col[k]);
+        A.src[k] = (int8_t)(snapshot ? L.col[k] : L.slot[k]);
+        A.wsi[k] = (uint8_t)L.col[k];
+    }
+    const char *name = snapshot ? "fixed_snapshot" : "fixed_axpy";
+    const double per = 16.0 * (1 + 2 * L.count);
+    ZK_PROF(st, name, (double)n * per,
+            hipLaunchKernelGGL(k_fixed_axpy, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src_polys, lagr, n, A,
+                               ws_dev, polys));
+    ZK_PROF(st, name, (double)B * n * per,
+            hipLaunchKernelGGL(k_fixed_axpy, dim3((unsigned)((B * n + 255) / 256)), dim3(256), 0, st, src_lde, lagr_lde,
+                               B * n, A, ws_dev, lde));
 }
 
 zk_program::~zk_program() {

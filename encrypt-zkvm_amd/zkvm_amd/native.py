@@ -33,7 +33,7 @@ EXPORTED = (
     "zk_prover_acquire", "zk_prover_release", "zk_prover_pool_trim", "zk_prover_trace_buffer",
     "zk_prove", "zk_prove_columns", "zk_prove_columns_ex", "zk_host_alloc", "zk_host_free", "zk_host_register",
     "zk_host_unregister", "zk_prove_device", "zk_lde_new", "zk_lde_read_frame", "zk_lde_query", "zk_lde_free",
-    "zk_eval_constraints", "zk_commit_composition", "zk_comp_query", "zk_comp_free", "zk_prover_stage_times", "zk_prover_profile", "zk_prover_kernel_stats", "zk_prover_kernel_ops", "zk_prover_exchange_stats", "zk_prover_exchange_stats_ex", "zk_prover_shard_schedule", "zk_prover_upload_stats", "zk_prover_upload_derived", "zk_prover_set_upload_schedule", "zk_prover_proof_info", "zk_vm_trace",
+    "zk_eval_constraints", "zk_commit_composition", "zk_comp_query", "zk_comp_free", "zk_prover_stage_times", "zk_prover_profile", "zk_prover_kernel_stats", "zk_prover_kernel_ops", "zk_prover_exchange_stats", "zk_prover_exchange_stats_ex", "zk_prover_shard_schedule", "zk_prover_upload_stats", "zk_prover_upload_derived", "zk_prover_upload_fixed", "zk_prover_set_upload_schedule", "zk_prover_proof_info", "zk_vm_trace",
     "zk_verify", "zk_comm_create_loopback", "zk_comm_unique_id", "zk_comm_create_rccl", "zk_comm_create_host", "zk_comm_destroy", "zk_comm_set_measure", "zk_comm_set_trace_split", "zk_prove_sharded",
     "zk_program_compile", "zk_program_trace", "zk_program_free", "zk_vm_last_error", "zk_vm_trace_device",
     "zk_vm_prove",
@@ -65,7 +65,7 @@ class PubInputs(C.Structure):
 class ProofInfo(C.Structure):
     """zk_proof_info (include/zkvm_gpu.h): what the last proof on a prover did."""
     _fields_ = [("schedule", C.c_int32), ("hint_redos", C.c_uint32), ("hint_sets", C.c_uint32),
-                ("hinted_sparse", C.c_uint32), ("derived", C.c_uint32), ("_pad", C.c_uint32)]
+                ("hinted_sparse", C.c_uint32), ("derived", C.c_uint32), ("fixed_sets", C.c_uint32)]
 
 
 class Record(C.Structure):
@@ -194,6 +194,7 @@ def lib():
         L.zk_prover_kernel_ops.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double), i32, C.POINTER(i32)]
         L.zk_prover_upload_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
         L.zk_prover_upload_derived.argtypes = [vp, C.POINTER(u32)]
+        L.zk_prover_upload_fixed.argtypes = [vp, C.POINTER(u32)]
         L.zk_prover_exchange_stats.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.POINTER(C.c_double),
                                                C.POINTER(i32), i32, C.POINTER(i32)]
         L.zk_verify.argtypes = [vp, sz, C.POINTER(PubInputs), u32, C.c_char_p, sz]

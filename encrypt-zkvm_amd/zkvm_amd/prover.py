@@ -168,28 +168,33 @@ class GpuProver:
 
     def upload_stats(self) -> dict:
         """The last host-column proof's trace upload (zk_prover_upload_stats): bytes, and the columns taken as sparse,
-        uploaded packed as 8- / 32-bit integers, or derived from the AIR (the clock, zk_prover_upload_derived)."""
+        uploaded packed as 8- / 32-bit integers, derived from the AIR (the clock, zk_prover_upload_derived), or formed
+        from the program's fixed-column snapshot (zk_prover_upload_fixed)."""
         b = C.c_uint64(0)
         sp, n8, n32 = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
         check(lib().zk_prover_upload_stats(self.handle, C.byref(b), C.byref(sp), C.byref(n8), C.byref(n32)))
         dv = C.c_uint32(0)
         check(lib().zk_prover_upload_derived(self.handle, C.byref(dv)))
+        fx = C.c_uint32(0)
+        check(lib().zk_prover_upload_fixed(self.handle, C.byref(fx)))
         cols = lambda m: [c for c in range(28) if (m >> c) & 1]  # noqa: E731
         return {"bytes": b.value, "sparse": cols(sp.value), "narrow8": cols(n8.value), "narrow32": cols(n32.value),
-                "derived": cols(dv.value)}
+                "derived": cols(dv.value), "fixed": cols(fx.value)}
 
     UPLOAD_SCHEDULES = {"auto": 0, "throughput": 1, "latency": 2}
 
     def proof_info(self) -> dict:
         """zk_prover_proof_info: the upload schedule the last host-column proof ran ("throughput" / "latency", None after
         a device-trace proof), the proofs voided by a refuted column hint and redone (cumulative), the (n, program) hint
-        sets held, and the sparse / derived columns the last proof took from its hints."""
+        sets held, the sparse / derived columns the last proof took from its hints, and the fixed-column snapshots
+        held."""
         from .native import ProofInfo
         info = ProofInfo()
         check(lib().zk_prover_proof_info(self.handle, C.byref(info)))
         cols = lambda m: [c for c in range(28) if (m >> c) & 1]  # noqa: E731
         return {"schedule": {1: "throughput", 2: "latency"}.get(info.schedule), "hint_redos": info.hint_redos,
-                "hint_sets": info.hint_sets, "hinted_sparse": cols(info.hinted_sparse), "derived": cols(info.derived)}
+                "hint_sets": info.hint_sets, "hinted_sparse": cols(info.hinted_sparse), "derived": cols(info.derived),
+                "fixed_sets": info.fixed_sets}
 
     def set_upload_schedule(self, schedule: str):
         """zk_prover_set_upload_schedule: "auto" (latency when no other proof is in flight on the device), "throughput"

@@ -277,6 +277,17 @@ int zk_prover_upload_stats(zk_prover *p, uint64_t *bytes, uint32_t *sparse_cols,
  * the clock (rows 0 .. n-2 of any accepted trace hold 0 .. n-2: air/src/constrains.rs clock constraint and the
  * clk[0] = 0 assertion), checked against the caller's column by host threads */
 int zk_prover_upload_derived(zk_prover *p, uint32_t *derived_cols);
+/* the columns of the last host-column proof taken as fixed (bit c): columns 1 .. 11 (opcode bits, hash flag, sponge,
+ * stack depth) depend on the program and lwe_size only, up to the random last row.  The first proof of a (trace length,
+ * program hash) that runs with learned hints -- a prover's second proof of it -- snapshots their coefficients and LDE
+ * (less the last row's share) on the device, 1.6 GB at 2^20, and rows 0 .. n-2 on the host; from the next proof on they
+ * are neither uploaded nor transformed but formed by one streaming pass from the snapshot and the last-row values,
+ * while host threads compare every row 0 .. n-2 of the caller's columns with the snapshot.  A mismatch voids the proof,
+ * which is redone from every column (hint_redos), and the class is not tried again for that program.  At most two
+ * snapshots per prover (zk_proof_info::fixed_sets), least recently used evicted.  Columns hinted sparse keep that
+ * class.  A fixed column that is also narrow stays listed in narrow8_cols / narrow32_cols of zk_prover_upload_stats;
+ * its bytes are not counted: `bytes` is what crossed the link.  ZK_FIXED=0 in the environment turns the class off. */
+int zk_prover_upload_fixed(zk_prover *p, uint32_t *fixed_cols);
 /* How a host-resident trace goes up (zk_prove / zk_prove_columns).  ZK_SCHED_AUTO (the default): the latency schedule
  * for a proof that starts with no other proof in flight on its device, else the throughput schedule.
  * ZK_SCHED_THROUGHPUT: the narrow (packed) columns in two parts through the copy engine between 64-MB column groups.
@@ -291,14 +302,15 @@ int zk_prover_set_upload_schedule(zk_prover *p, int schedule);
  * when it starts (a proof counts as in flight from entry until its uploads and kernels have drained).
  * hint_redos: proofs this prover voided and redid because a column hint was refuted (cumulative).  hint_sets: the
  * (trace length, program hash) column-hint sets it holds (at most 8, least recently used evicted).  hinted_sparse /
- * derived: the sparse columns (bit c) and derived columns (bit 0, the clock) the last proof took from its hints. */
+ * derived: the sparse columns (bit c) and derived columns (bit 0, the clock) the last proof took from its hints.
+ * fixed_sets: the fixed-column snapshots it holds (zk_prover_upload_fixed; at most 2). */
 typedef struct {
     int32_t schedule;
     uint32_t hint_redos;
     uint32_t hint_sets;
     uint32_t hinted_sparse;
     uint32_t derived;
-    uint32_t _pad;
+    uint32_t fixed_sets;
 } zk_proof_info;
 int zk_prover_proof_info(const zk_prover *p, zk_proof_info *out);
 
