@@ -1089,6 +1089,56 @@ void hash_rows_blocks(hipStream_t st, const fe *base, int ncols, int log_n, int 
                                ncols / 4, leaves, virt));
 }
 
+// Blocks 0 .. nb - 1 of every row with their columns' LDE formed on the way (FixedHashCols): per LDE point e_(n-1)'s
+// value once, then per column the source plane's value plus the last-row W set times it, stored to the LDE (the
+// evaluator and the query gather read it) and placed in the message words; one block's four elements, its compression,
+// then the next block.  The same thread mapping as k_hash_rows_blocks (a wave's plane accesses, loads and stores, are 8
+// runs of 128 B), the same sums as k_fixed_axpy / k_axpy_fill: the value stored and the value hashed are one canonical
+// element.  The modes are kernel arguments (scalar branches); src, lagr_lde and lde never overlap.
+__global__ void __launch_bounds__(256) k_fixed_hash(FixedHashCols A, const fe *__restrict__ lagr_lde,
+                                                    const fe_ws *__restrict__ ws, fe *__restrict__ lde, int log_n,
+                                                    int log_b, int nb, int nblk, uint8_t *cv_leaves) {
+    const size_t N = (size_t)1 << (log_n + log_b), n = (size_t)1 << log_n, B = (size_t)1 << log_b;
+    const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (t >= N) return;
+    const size_t r = t & (B - 1), q = t >> log_b, at = r * n + q;
+    uint32_t h[8], m[16];
+    b3::iv(h);
+    const fe lg = lagr_lde[at];
+    for (int blk = 0; blk < nb; blk++) {
+        fe *p = lde + at + (size_t)(4 * blk) * B * n;
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            const int c = 4 * blk + e, mode = A.mode[c];
+            fe v;
+            if (mode == FixedHashCols::LOAD) {
+                v = p[(size_t)e * B * n];
+            } else {
+                const fe w = fe_mul_uniform(lg, load_fe_ws(ws, A.wsi[c]));
+                v = mode == FixedHashCols::FORM ? fe_add(A.src[c][at], w) : w;
+                p[(size_t)e * B * n] = v;
+            }
+            m[4 * e + 0] = (uint32_t)v.lo;
+            m[4 * e + 1] = (uint32_t)(v.lo >> 32);
+            m[4 * e + 2] = (uint32_t)v.hi;
+            m[4 * e + 3] = (uint32_t)(v.hi >> 32);
+        }
+        const uint32_t flags = (blk == 0 ? b3::CHUNK_START : 0u) | (blk == nblk - 1 ? (b3::CHUNK_END | b3::ROOT) : 0u);
+        b3::compress(h, m, 0, 0, 64, flags);
+    }
+    store_digest(cv_leaves + 32 * ((q << log_b) + r), h);
+}
+
+void fixed_hash(hipStream_t st, const FixedHashCols &A, const fe *lagr_lde, const fe_ws *ws_dev, fe *lde, int ncols,
+                int log_n, int log_b, int nb, uint8_t *leaves) {
+    const size_t N = (size_t)1 << (log_n + log_b);
+    double per = 16.0 + 32.0;  // e_(n-1)'s value, the chaining value
+    for (int c = 0; c < 4 * nb; c++) per += A.mode[c] == FixedHashCols::FORM ? 32.0 : 16.0;
+    ZK_PROF(st, "fixed_hash", per * N,
+            hipLaunchKernelGGL(k_fixed_hash, dim3(cdiv(N, 256)), dim3(256), 0, st, A, lagr_lde, ws_dev, lde, log_n, log_b,
+                               nb, ncols / 4, leaves));
+}
+
 // Sparse-column detection: nz[c0 + c] = 1 when column c has a nonzero entry before its last one; last[c0 + c] = its
 // last entry; with wstride > 0 also the width flags of SparseCols.  One pass over the columns (16 B per element read);
 // nz must be zeroed first.

@@ -1233,6 +1233,15 @@ bool zk::fixed_on() {
     return on;
 }
 constexpr uint32_t ZK_FIXED_CAND = 0xFFEu;  // columns 1 .. 11
+// ZK_FIXED_FUSE=0: their LDE (and the clock's, and zk_vm_prove's preprocessed columns') by the streaming passes and
+// hash_rows_blocks instead of inside the row hash of their blocks (fixed_hash)
+bool zk::fixed_fuse_on() {
+    static const bool on = [] {
+        const char *e = getenv("ZK_FIXED_FUSE");
+        return !(e && !strcmp(e, "0"));
+    }();
+    return on;
+}
 
 // forget snapshot i (its device buffers stay allocated for the next snapshot of that size)
 static void fixed_drop(zk_prover *p, int i) {
@@ -1756,6 +1765,19 @@ static int trace_lde_commit(zk_prover *p, Plan *pl, const TraceSrc &src, size_t 
         p->virt_lagr = pl->lagr_lde;
         for (int i = 0; i < nh; i++) ready[hin[i]] = true;
     }
+    // The fused prefix: with the fixed class in use, the leading blocks whose columns are each fixed, the derived clock,
+    // or hinted sparse with their LDE filled above get their formed columns' LDE inside their row hash (fixed_hash:
+    // blocks 0 .. 2 of the benchmark program); the coefficients keep their passes, and so does every such column past
+    // the prefix.  Empty without a snapshot in use or without the derived clock (column 0 is in block 0).
+    int fuse_nb = 0;
+    if (fixm && fixed_fuse_on()) {
+        auto pre = [&](int c) {
+            return (clk && c == 0) || ((fixm >> c) & 1u) || (((hint & ~virt) >> c) & 1u);
+        };
+        while (fuse_nb < W / 4 && pre(4 * fuse_nb) && pre(4 * fuse_nb + 1) && pre(4 * fuse_nb + 2) && pre(4 * fuse_nb + 3))
+            fuse_nb++;
+    }
+    fe_ws clk_d{};
     if (clk) {
         ZK_TRY(clock_tables(p, pl));
         clocked.reset((int)per);
@@ -1770,8 +1792,9 @@ static int trace_lde_commit(zk_prover *p, Plan *pl, const TraceSrc &src, size_t 
         fe last0;
         memcpy(&last0, col + (n - 1) * sizeof(fe), sizeof(fe));
         const fe_ws d = make_fe_ws(fe_sub(last0, fe_make(n - 1)));
+        clk_d = d;
         axpy_fill(p->st, pl->id_poly, pl->lagr, d, n, p->polys);
-        axpy_fill(p->st, pl->id_lde, pl->lagr_lde, d, B * n, p->lde);
+        if (!fuse_nb) axpy_fill(p->st, pl->id_lde, pl->lagr_lde, d, B * n, p->lde);
         ready[0] = true;
     }
     if (fixm) {
@@ -1790,9 +1813,28 @@ static int trace_lde_commit(zk_prover *p, Plan *pl, const TraceSrc &src, size_t 
             L.slot[L.count] = FS->slot[c];
             L.count++;
         }
+        if (fuse_nb) ws[0] = clk_d;  // (column 0 is never in the fixed class: its W set slot carries the clock's d)
         ZK_TRY(h2d_small(p, p->fix_ws, ws, sizeof ws));
-        fixed_cols_axpy(p->st, L, false, FS->fpolys, FS->flde, pl->lagr, pl->lagr_lde, p->fix_ws, n, B, p->polys, p->lde);
+        fixed_cols_axpy(p->st, L, false, FS->fpolys, FS->flde, pl->lagr, pl->lagr_lde, p->fix_ws, n, B, p->polys, p->lde,
+                        4 * fuse_nb);
         for (int k = 0; k < L.count; k++) ready[L.col[k]] = true;
+        if (fuse_nb) {
+            FixedHashCols A{};
+            for (int c = 0; c < 4 * fuse_nb; c++) {
+                A.wsi[c] = (uint8_t)c;
+                if (clk && c == 0) {
+                    A.mode[c] = FixedHashCols::FORM;
+                    A.src[c] = pl->id_lde;
+                } else if ((fixm >> c) & 1u) {
+                    A.mode[c] = FixedHashCols::FORM;
+                    A.src[c] = FS->flde + (size_t)FS->slot[c] * B * n;
+                } else {
+                    A.mode[c] = FixedHashCols::LOAD;  // hinted sparse: filled above
+                }
+            }
+            fixed_hash(p->st, A, pl->lagr_lde, p->fix_ws, p->lde, W, log_n, log_b, fuse_nb, p->leaves);
+            hashed = fuse_nb;
+        }
         hash_ready(false);
         // the host check: every row 0 .. n-2 of the caller's columns against the snapshot's host copy
         compared.reset((int)(per * L.count));
@@ -2536,9 +2578,22 @@ int zk::fixed_prefix(zk_prover *p, size_t n, uint32_t B, const FixedCols &fx) {
     fe_ws ws[W];
     for (int c = 0; c < W; c++) ws[c] = make_fe_ws(fx.last[c]);
     ZK_TRY(h2d_small(p, p->fix_ws, ws, sizeof ws));
-    fixed_axpy(p->st, fx, p->fix_ws, n, (size_t)1 << pl->log_b, p->polys, p->lde);
     constexpr int nb = 12 / 4;  // columns 0 .. 11 are preprocessed whatever the program's stack depth
-    hash_rows_blocks(p->st, p->lde, W, pl->log_n, pl->log_b, 0, nb, p->leaves);
+    const size_t Bn = n << pl->log_b;
+    if (fixed_fuse_on()) {
+        // their LDE inside the row hash of their blocks; the streaming pass extends the zero registers only
+        fixed_axpy(p->st, fx, p->fix_ws, n, (size_t)1 << pl->log_b, p->polys, p->lde, 4 * nb);
+        FixedHashCols A{};
+        for (int c = 0; c < 4 * nb; c++) {
+            A.mode[c] = FixedHashCols::FORM;
+            A.src[c] = fx.flde + (size_t)c * Bn;
+            A.wsi[c] = (uint8_t)c;
+        }
+        fixed_hash(p->st, A, fx.lagr_lde, p->fix_ws, p->lde, W, pl->log_n, pl->log_b, nb, p->leaves);
+    } else {
+        fixed_axpy(p->st, fx, p->fix_ws, n, (size_t)1 << pl->log_b, p->polys, p->lde);
+        hash_rows_blocks(p->st, p->lde, W, pl->log_n, pl->log_b, 0, nb, p->leaves);
+    }
     p->fix_prefix_blocks = nb;
     return ZK_OK;
 }

@@ -393,8 +393,10 @@ int sparse_begin(zk_prover *p, Plan *pl, SparseCols *out, const SparseCols **sp)
 int prove_fixed(zk_prover *p, size_t n, const zk_options *opt, const zk_pub_inputs *pub, const FixedCols *fx,
                 uint8_t *proof_out, size_t *proof_len);
 // polys / lde of the preprocessed columns (all but 12 .. 12 + md - 1): f_c + last[c] e_(n-1) (vm_gpu.hip); B: the LDE
-// cosets held (fx's flde / lagr_lde and lde alike)
-void fixed_axpy(hipStream_t st, const FixedCols &fx, const fe_ws *ws_dev, size_t n, size_t B, fe *polys, fe *lde);
+// cosets held (fx's flde / lagr_lde and lde alike).  lde_c0: the LDE launch forms the columns from lde_c0 on only (the
+// ones below it are formed by fixed_hash, inside their rows' hashing); the coefficients are always all of them
+void fixed_axpy(hipStream_t st, const FixedCols &fx, const fe_ws *ws_dev, size_t n, size_t B, fe *polys, fe *lde,
+                int lde_c0 = 0);
 // The same pass for the host-trace fixed class (zk_prover::FixedSnap): `count` trace columns col[k], each with a compact
 // plane slot[k] of the snapshot.  Use: polys / lde column col[k] = snapshot plane slot[k] + ws_dev[col[k]] e_(n-1)'s.
 // snapshot: the other way, plane slot[k] of polys / lde (the snapshot's buffers) = column col[k] of src_polys / src_lde
@@ -404,8 +406,11 @@ struct FixedColList {
     uint8_t col[W], slot[W];
 };
 void fixed_cols_axpy(hipStream_t st, const FixedColList &L, bool snapshot, const fe *src_polys, const fe *src_lde,
-                     const fe *lagr, const fe *lagr_lde, const fe_ws *ws_dev, size_t n, size_t B, fe *polys, fe *lde);
+                     const fe *lagr, const fe *lagr_lde, const fe_ws *ws_dev, size_t n, size_t B, fe *polys, fe *lde,
+                     int lde_c0 = 0);
 bool fixed_on();
+// ZK_FIXED_FUSE=0: the fixed / preprocessed columns' LDE by its own streaming pass and hash_rows_blocks, not fixed_hash
+bool fixed_fuse_on();
 // rows [r0, r1) of a host column against a snapshot's host copy (`width` bytes per row: 1 or 4 packed integers, or the
 // 16-byte elements themselves): true if every row holds the snapshot's value
 bool same_rows(const uint8_t *col, const uint8_t *snap, size_t r0, size_t r1, int width);

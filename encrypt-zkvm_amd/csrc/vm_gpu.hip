@@ -435,44 +435,60 @@ int fixed_columns(zk_prover *p, zk_program *prog, const zk::vm::Inputs &in, uint
 
 }  // namespace
 
-void zk::fixed_axpy(hipStream_t st, const FixedCols &fx, const fe_ws *ws_dev, size_t n, size_t B, fe *polys, fe *lde) {
-    AxpyCols A;
-    A.ncol = 0;
+void zk::fixed_axpy(hipStream_t st, const FixedCols &fx, const fe_ws *ws_dev, size_t n, size_t B, fe *polys, fe *lde,
+                    int lde_c0) {
+    AxpyCols A, E;  // coefficients: every preprocessed column; LDE: the ones from lde_c0 on
+    A.ncol = E.ncol = 0;
+    size_t ef = 0;
     for (int c = 0; c < W; c++) {
         if (c >= 12 && c < 12 + fx.md) continue;  // dynamic: interpolated and extended from the trace
         A.col[A.ncol] = (uint8_t)c;
         A.src[A.ncol] = (int8_t)(c < 12 ? c : -1);
         A.wsi[A.ncol] = (uint8_t)c;
         A.ncol++;
+        if (c < lde_c0) continue;
+        E.col[E.ncol] = (uint8_t)c;
+        E.src[E.ncol] = (int8_t)(c < 12 ? c : -1);
+        E.wsi[E.ncol] = (uint8_t)c;
+        E.ncol++;
+        ef += c < 12;
     }
     const size_t nf = 12, nz = (size_t)A.ncol - nf;
     ZK_PROF(st, "fixed_axpy", (double)n * 16 * (1 + 2 * nf + nz),
             hipLaunchKernelGGL(k_fixed_axpy, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, fx.fpolys, fx.lagr, n, A,
                                ws_dev, polys));
-    ZK_PROF(st, "fixed_axpy", (double)B * n * 16 * (1 + 2 * nf + nz),
+    if (!E.ncol) return;
+    ZK_PROF(st, "fixed_axpy", (double)B * n * 16 * (1 + ef + E.ncol),
             hipLaunchKernelGGL(k_fixed_axpy, dim3((unsigned)((B * n + 255) / 256)), dim3(256), 0, st, fx.flde,
-                               fx.lagr_lde, B * n, A, ws_dev, lde));
+                               fx.lagr_lde, B * n, E, ws_dev, lde));
 }
 
 void zk::fixed_cols_axpy(hipStream_t st, const FixedColList &L, bool snapshot, const fe *src_polys, const fe *src_lde,
-                         const fe *lagr, const fe *lagr_lde, const fe_ws *ws_dev, size_t n, size_t B, fe *polys, fe *lde) {
+                         const fe *lagr, const fe *lagr_lde, const fe_ws *ws_dev, size_t n, size_t B, fe *polys, fe *lde,
+                         int lde_c0) {
     if (L.count <= 0) return;
-    AxpyCols A;
+    AxpyCols A, E;  // coefficients: every listed column; LDE: the ones from lde_c0 on
     A.ncol = L.count;
+    E.ncol = 0;
     for (int k = 0; k < L.count; k++) {
         // use: slot -> column; snapshot: column -> slot (ws_dev then holds the negated last row)
         A.col[k] = (uint8_t)(snapshot ? L.slot[k] : L.col[k]);
         A.src[k] = (int8_t)(snapshot ? L.col[k] : L.slot[k]);
         A.wsi[k] = (uint8_t)L.col[k];
+        if (L.col[k] < lde_c0) continue;
+        E.col[E.ncol] = A.col[k];
+        E.src[E.ncol] = A.src[k];
+        E.wsi[E.ncol] = A.wsi[k];
+        E.ncol++;
     }
     const char *name = snapshot ? "fixed_snapshot" : "fixed_axpy";
-    const double per = 16.0 * (1 + 2 * L.count);
-    ZK_PROF(st, name, (double)n * per,
+    ZK_PROF(st, name, (double)n * 16.0 * (1 + 2 * A.ncol),
             hipLaunchKernelGGL(k_fixed_axpy, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src_polys, lagr, n, A,
                                ws_dev, polys));
-    ZK_PROF(st, name, (double)B * n * per,
+    if (!E.ncol) return;
+    ZK_PROF(st, name, (double)B * n * 16.0 * (1 + 2 * E.ncol),
             hipLaunchKernelGGL(k_fixed_axpy, dim3((unsigned)((B * n + 255) / 256)), dim3(256), 0, st, src_lde, lagr_lde,
-                               B * n, A, ws_dev, lde));
+                               B * n, E, ws_dev, lde));
 }
 
 zk_program::~zk_program() {

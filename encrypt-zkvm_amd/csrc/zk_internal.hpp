@@ -194,6 +194,21 @@ struct VirtCols {
 };
 void hash_rows_blocks(hipStream_t st, const fe *base, int ncols, int log_n, int log_b, int b0, int b1, uint8_t *leaves,
                       VirtCols virt = VirtCols());
+// Blocks 0 .. nb - 1 of every row (IV, then as hash_rows_blocks(0, nb)) with the columns' LDE formed in the same pass:
+// per column c < 4 nb
+//   FORM        lde column c = src[c] + ws_dev[wsi[c]] * lagr_lde  (src[c]: a coset-major plane of B n), stored and hashed
+//   FORM_NOSRC  lde column c = ws_dev[wsi[c]] * lagr_lde, stored and hashed
+//   LOAD        lde column c is already written: hashed only
+// (the fixed / preprocessed columns and the clock: prover.hip trace_lde_commit, fixed_prefix).  ncols as hash_rows_blocks.
+struct FixedHashCols {
+    enum : uint8_t { FORM = 0, FORM_NOSRC = 1, LOAD = 2 };
+    static constexpr int MAXC = 28;  // the trace width: 7 blocks
+    const fe *src[MAXC];
+    uint8_t wsi[MAXC];
+    uint8_t mode[MAXC];
+};
+void fixed_hash(hipStream_t st, const FixedHashCols &A, const fe *lagr_lde, const fe_ws *ws_dev, fe *lde, int ncols,
+                int log_n, int log_b, int nb, uint8_t *leaves);
 // Storage of a FRI layer of L values: natural order (lb = 0), or coset-major over 2^lb cosets of 2^lcn
 // points (natural index i at (i mod 2^lb) 2^lcn + i / 2^lb): layer 0 as the DEEP coset LDE leaves it
 struct FriLayout {
