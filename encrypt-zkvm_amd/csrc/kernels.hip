@@ -3018,12 +3018,47 @@ void coset_major_to_natural(hipStream_t st, const fe *src, int log_n, int log_b,
 
 // ================================================================ diagnostics (C ABI: zk_diag_*)
 namespace zk {
-__global__ void k_field_op(int op, const fe *a, const fe *b, fe *out, size_t count) {
+__global__ void k_field_op(int op, const fe *a, const fe *b, fe *out, size_t count, const fe_ws *ws, const fe_w2 *w2) {
     size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (t >= count) return;
     fe x = a[t], y = b[t];
     fe r;
+    const size_t w0 = t & ~(size_t)63, mir = count - 1 - t;  // the first element of lane t's wave; the mirrored lane
     switch (op) {
+    // ---- the constant-multiplier forms: ws[i] = make_fe_ws(b[i]), w2[i] = make_fe_w2(b[i]), built by the host
+    case 11: r = fe_mul_uniform(x, load_fe_ws(ws, (int)w0)); break;  // wave-uniform: the W set of b[w0], scalar loads
+    case 12: r = fe_mul_wsv(x, ws[t]); break;                        // per lane: the W set of b[t], vector loads
+    case 13: {
+        // pair (a[t], A) with (a[w0 + 63 - l], B), l = t - w0: A the W set of b[w0], B that of b[w0 + 63] (the wave's
+        // first and last element; count a multiple of 64); lane t returns output t & 1 of (a[t] A, a[w0 + 63 - l] B)
+        const fe_ws WA = load_fe_ws(ws, (int)w0), WB = load_fe_ws(ws, (int)w0 + 63);
+        fe o[2];
+        fe_mul_uniform2(x, WA, a[w0 + 63 - (t - w0)], WB, o[0], o[1]);
+        r = o[t & 1];
+        break;
+    }
+    case 14:
+    case 15: {
+        // pair (a[t], b[t]) with the mirrored lane's (a, b)[count - 1 - t]; lane t returns output t & 1
+        fe o[2];
+        if (op == 14) fe_mul_wsv2(x, ws[t], a[mir], ws[mir], o[0], o[1]);
+        else fe_mul_w2_2(x, w2[t], a[mir], w2[mir], o[0], o[1]);
+        r = o[t & 1];
+        break;
+    }
+    // ---- the raw final reductions: L = a[t] (128 bits), s4 = bits 0 .. 31 of b[t], s5 = bits 32 .. 34;
+    // (L + (s4 + s5 2^32) 2^128) mod p
+    case 16: r = ws_fold(lo32(x.lo), hi32(x.lo), lo32(x.hi), hi32(x.hi), lo32(y.lo), hi32(y.lo) & 7u); break;
+    case 17: {
+        // lane t's input and the mirrored lane's (count - 1 - t) in one paired block; lane t returns output t & 1
+        const fe x2 = a[mir], y2 = b[mir];
+        uint32_t A[4] = {lo32(x.lo), hi32(x.lo), lo32(x.hi), hi32(x.hi)};
+        uint32_t B[4] = {lo32(x2.lo), hi32(x2.lo), lo32(x2.hi), hi32(x2.hi)};
+        fe o[2];
+        ws_fold2(A, lo32(y.lo), hi32(y.lo) & 7u, B, lo32(y2.lo), hi32(y2.lo) & 7u, o[0], o[1]);
+        r = o[t & 1];
+        break;
+    }
     case 0: r = fe_add(x, y); break;
     case 1: r = fe_sub(x, y); break;
     case 2: r = fe_mul(x, y); break;
@@ -3057,8 +3092,9 @@ __global__ void k_blake3_elems(const fe *in, int k, size_t count, uint8_t *out) 
     store_digest(out + 32 * t, h);
 }
 
-void diag_field_op(hipStream_t st, int op, const fe *a, const fe *b, fe *out, size_t count) {
-    hipLaunchKernelGGL(k_field_op, dim3(cdiv(count, 256)), dim3(256), 0, st, op, a, b, out, count);
+void diag_field_op(hipStream_t st, int op, const fe *a, const fe *b, fe *out, size_t count, const fe_ws *ws,
+                   const fe_w2 *w2) {
+    hipLaunchKernelGGL(k_field_op, dim3(cdiv(count, 256)), dim3(256), 0, st, op, a, b, out, count, ws, w2);
 }
 void diag_blake3_elems(hipStream_t st, const fe *in, int k, size_t count, uint8_t *out) {
     hipLaunchKernelGGL(k_blake3_elems, dim3(cdiv(count, 256)), dim3(256), 0, st, in, k, count, out);

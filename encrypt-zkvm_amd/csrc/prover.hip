@@ -2844,19 +2844,54 @@ extern "C" void zk_diag_mul_limbs_host(const uint8_t *a, const uint8_t *b, uint8
 extern "C" void zk_diag_blake3_host(const uint8_t *in, size_t len, uint8_t out[32]) { b3::hash_bytes(in, len, out); }
 
 // GPU elementwise field op: 0 add, 1 sub, 2 mul, 3 inv(a), 4 a^b (b as a 128-bit exponent), 5 lazy add,
-// 6 canonical form of a, 7 multiply by b in two-part form
+// 6 canonical form of a, 7 multiply by b in two-part form, 8 .. 10 the butterflies' addsub2 forms.
+// 11 .. 15: a times the constant b through the production constant forms, the constants built here by make_fe_ws /
+// make_fe_w2 and uploaded as a table: 11 fe_mul_uniform (the constant of the first element of each 64-element wave),
+// 12 fe_mul_wsv, 13 fe_mul_uniform2 (count a multiple of 64), 14 fe_mul_wsv2, 15 fe_mul_w2_2; 16 / 17 the raw final
+// reductions ws_fold / ws_fold2 of a + (b mod 2^35) 2^128.  The pairing of the two-output forms: kernels.hip k_field_op.
 extern "C" int zk_diag_field_op(int device, int op, const uint8_t *a, const uint8_t *b, uint8_t *out, size_t count) {
     if (!a || !b || !out || count == 0) ZK_FAIL(ZK_ERR_INVALID_ARG, "null argument");
+    if (op < 0 || op > 17 || count > ((size_t)1 << 30) || (op == 13 && count % 64 != 0))
+        ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_field_op: unknown op, or a count the op does not take");
     ZK_CHECK_HIP(hipSetDevice(device));
+    std::vector<fe_ws> ws;
+    std::vector<fe_w2> w2;
+    if (op >= 11 && op <= 14) {
+        ws.resize(count);
+        for (size_t i = 0; i < count; i++) ws[i] = make_fe_ws(fe_from_bytes(b + 16 * i));
+    } else if (op == 15) {
+        w2.resize(count);
+        for (size_t i = 0; i < count; i++) w2[i] = make_fe_w2(fe_from_bytes(b + 16 * i));
+    }
     fe *d = nullptr;
+    void *tab = nullptr;
+    const size_t tab_bytes = ws.size() * sizeof(fe_ws) + w2.size() * sizeof(fe_w2);
     ZK_CHECK_HIP(hipMalloc(&d, 3 * count * sizeof(fe)));
-    ZK_CHECK_HIP(hipMemcpy(d, a, count * 16, hipMemcpyHostToDevice));
-    ZK_CHECK_HIP(hipMemcpy(d + count, b, count * 16, hipMemcpyHostToDevice));
-    diag_field_op(nullptr, op, d, d + count, d + 2 * count, count);
-    hipError_t e = hipMemcpy(out, d + 2 * count, count * 16, hipMemcpyDeviceToHost);
+    hipError_t e = tab_bytes ? hipMalloc(&tab, tab_bytes) : hipSuccess;
+    if (e == hipSuccess) e = hipMemcpy(d, a, count * 16, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d + count, b, count * 16, hipMemcpyHostToDevice);
+    if (e == hipSuccess && tab_bytes)
+        e = hipMemcpy(tab, ws.empty() ? (const void *)w2.data() : (const void *)ws.data(), tab_bytes, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        diag_field_op(nullptr, op, d, d + count, d + 2 * count, count, ws.empty() ? nullptr : (const fe_ws *)tab,
+                      w2.empty() ? nullptr : (const fe_w2 *)tab);
+        e = hipMemcpy(out, d + 2 * count, count * 16, hipMemcpyDeviceToHost);
+    }
     (void)hipFree(d);
+    if (tab) (void)hipFree(tab);
     ZK_CHECK_HIP(e);
     return ZK_OK;
+}
+
+// Host: the constant forms of w as the kernels read them -- out[0, 64) = make_fe_ws(w) (word 4 j + i = 32-bit word j
+// of w 2^(32 i) mod p), out[64, 96) = make_fe_w2(w) (w, w 2^64 mod p)
+extern "C" void zk_diag_make_ws_host(const uint8_t *w, uint8_t *out) {
+    const fe v = fe_from_bytes(w);
+    const fe_ws W = make_fe_ws(v);
+    const fe_w2 W2 = make_fe_w2(v);
+    memcpy(out, W.w, 64);
+    fe_to_bytes(W2.w, out + 64);
+    fe_to_bytes(W2.w64, out + 80);
 }
 
 // GPU BLAKE3 of `count` rows of k field elements (k <= 64)
@@ -2903,5 +2938,35 @@ extern "C" int zk_diag_ntt(int device, const uint8_t *in, size_t n, int batch, i
     ntt(p->st, T, d_in, n, d_out, n, batch, inverse != 0, use_pre ? &pre : nullptr, inverse ? &inv_n : nullptr, d_tmp);
     ZK_CHECK_HIP(hipStreamSynchronize(p->st));
     ZK_CHECK_HIP(hipMemcpy(out, d_out, n * batch * 16, hipMemcpyDeviceToHost));
+    return ZK_OK;
+}
+
+// GPU coset LDE as the prover runs it (ntt_lde over the plan's CosetTables): ncols (<= the trace width) columns of n
+// coefficients -- or, from_evals != 0, of n evaluations over <w_n>, interpolated first exactly as the prover does
+// (ntt with post_scale n^-1: four-step sizes take the pass-1 twiddles with n^-1 folded in) -- extended over the ncos
+// cosets r = r0 + j rstride of the blowup * n domain:  out[(c ncos + j) n + k] = P_c(3 w_N^r w_n^k).
+extern "C" int zk_diag_lde(int device, const uint8_t *in, size_t n, int ncols, uint32_t blowup, int r0, int rstride,
+                           int ncos, int from_evals, uint8_t *out) {
+    if (!in || !out || n < 8 || (n & (n - 1)) || ncols <= 0 || ncols > W || blowup < 8 || blowup > 64 ||
+        (blowup & (blowup - 1)) || r0 < 0 || rstride < 1 || ncos < 1 ||
+        (uint64_t)r0 + (uint64_t)(ncos - 1) * (uint64_t)rstride >= blowup)
+        ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_lde: n a power of two >= 8, 1 .. 28 columns, cosets r0 + j rstride < blowup");
+    zk_prover *p = nullptr;
+    int rc = zk_prover_create(device, std::max<size_t>(n, 16), blowup, &p);
+    if (rc) return rc;
+    std::unique_ptr<zk_prover, void (*)(zk_prover *)> guard(p, zk_prover_destroy);
+    Plan *pl = nullptr;
+    ZK_TRY(get_plan(p, n, blowup, &pl));
+    ZK_CHECK_HIP(hipMemcpy(p->d_trace, in, (size_t)ncols * n * 16, hipMemcpyHostToDevice));
+    const fe *coeffs = p->d_trace;
+    if (from_evals) {
+        const fe inv_n = h_inv(fe_make(n));
+        ntt(p->st, pl->Tn, p->d_trace, n, p->polys, n, ncols, true, nullptr, &inv_n, p->tmp);
+        coeffs = p->polys;
+    }
+    // p->lde holds 28 * blowup * n elements, p->tmp 28 * 8 * n (a launch covers at most 8 cosets)
+    ntt_lde(p->st, pl->Tn, pl->ct, coeffs, n, ncols, r0, rstride, ncos, p->lde, (size_t)ncos * n, n, p->tmp);
+    ZK_CHECK_HIP(hipStreamSynchronize(p->st));
+    ZK_CHECK_HIP(hipMemcpy(out, p->lde, (size_t)ncols * ncos * n * 16, hipMemcpyDeviceToHost));
     return ZK_OK;
 }

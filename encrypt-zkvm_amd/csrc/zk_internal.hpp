@@ -407,6 +407,8 @@ void gather_fe(hipStream_t st, const fe *src, const uint64_t *idx, size_t k, fe 
 }  // namespace zk
 
 namespace zk {
-void diag_field_op(hipStream_t st, int op, const fe *a, const fe *b, fe *out, size_t count);
+// ws / w2: the W sets / two-part forms of b[0 .. count) (ops 11 .. 14 / op 15; else null)
+void diag_field_op(hipStream_t st, int op, const fe *a, const fe *b, fe *out, size_t count, const fe_ws *ws = nullptr,
+                   const fe_w2 *w2 = nullptr);
 void diag_blake3_elems(hipStream_t st, const fe *in, int k, size_t count, uint8_t *out);
 }  // namespace zk

@@ -231,6 +231,10 @@ def lib():
         L.zk_diag_field_op.argtypes = [i32, i32, vp, vp, vp, sz]
         L.zk_diag_blake3_rows.argtypes = [i32, vp, i32, sz, vp]
         L.zk_diag_ntt.argtypes = [i32, vp, sz, i32, i32, vp, vp]
+        L.zk_diag_make_ws_host.argtypes = [vp, vp]
+        L.zk_diag_make_ws_host.restype = None
+        # (device, in, n, ncols, blowup, r0, rstride, ncos, from_evals, out)
+        L.zk_diag_lde.argtypes = [i32, vp, sz, i32, u32, i32, i32, i32, i32, vp]
         _lib = L
     return _lib
 

@@ -126,7 +126,7 @@ def test_blake3_rows(gpu, oracle, k):
         assert out.raw[32 * i:32 * i + 32] == oracle.blake3(elems_bytes(r))
 
 
-@pytest.mark.parametrize("log_n", [2, 4, 7, 10, 12, 13, 14, 16])
+@pytest.mark.parametrize("log_n", [1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19])
 def test_ntt(gpu, oracle, log_n):
     n = 1 << log_n
     rnd = random.Random(log_n)
@@ -171,7 +171,7 @@ def test_ntt_four_step_splits(oracle, log_n):
     assert out.raw == buf.raw, "inverse NTT differs"
 
 
-@pytest.mark.parametrize("log_n", [20, 21, 22])
+@pytest.mark.parametrize("log_n", [10, 11, 12, 13, 19, 20, 21, 22])
 def test_ntt_lazy_edge_values(oracle, log_n):
     """Columns drawn from {0, 1, 2, p - 2, p - 1}: pass-1 butterfly sums such as (p - 1) + 2 = p + 1 stay
     partially reduced in the tile (ZK_NTT_LAZY), and the wave-uniform j = 0 rounds, which skip their unit

@@ -81,6 +81,22 @@ def test_lazy_dot_product_on_host():
         assert bytes_elems(out.raw)[0] == sum(x * y for x, y in zip(a, b)) % P
 
 
+def test_constant_forms_on_host():
+    """The builders of the kernels' constant forms (f128.hpp make_fe_ws / make_fe_w2): the W set of w holds
+    W_i = w 2^(32 i) mod p, i < 4, as 32-bit words (word 4 j + i = word j of W_i), the two-part form w and w 2^64 mod p."""
+    rnd = random.Random(17)
+    consts = [0, 1, 2, P - 1, P - 2, 2**32, 2**64, 2**96, 2**127, 45 * 2**40, 2**64 - 1]
+    ws = consts + [rnd.randrange(P) for _ in range(1000)] + [rnd.randrange(2**32) for _ in range(50)]
+    out = C.create_string_buffer(96)
+    for w in ws:
+        native.lib().zk_diag_make_ws_host(elems_bytes([w]), out)
+        words = np.frombuffer(out.raw[:64], dtype="<u4")
+        for i in range(4):
+            got = sum(int(words[4 * j + i]) << (32 * j) for j in range(4))
+            assert got == w * 2**(32 * i) % P, (w, i, got)
+        assert bytes_elems(out.raw[64:]) == [w, w * 2**64 % P], w
+
+
 def test_host_blake3_matches_oracle(oracle):
     for n in (0, 1, 40, 63, 64, 65, 448, 1024, 1025, 2048, 4100):
         data = bytes((7 * i + 3) % 256 for i in range(n))
