@@ -22,4 +22,10 @@ inline int num_comp_cols(size_t n) {
 // verifier.cpp: the out-of-domain constraint identity at z (ood = [T(z)]_W ++ [T(zg)]_W ++ [H_j(z)]_C;
 // ct: 20 transition, cb: 22 boundary composition coefficients), over E (base values lift with b = 0)
 bool ood_identity(const fe2 *ood, int C, const fe2 *ct, const fe2 *cb, fe2 z, size_t n, const zk_pub_inputs *pub);
+// verifier.cpp: ProcessorAir::evaluate_transition (air/src/lib.rs:104-168) at one base-field frame -- the verifier's
+// frame evaluator with every value lifted (b = 0); cur / nxt: the 28 cells of rows s and s + 1, per: the 9 periodic
+// values of the step, out: the 20 constraint values.  air_periodic_row: row `step mod 16` of the raw periodic table
+// (CYCLE_MASK || round constants, lib.rs:201-225).
+void air_eval_base(const fe *cur, const fe *nxt, const fe *per, uint32_t lwe_size, uint32_t delta, fe *out);
+void air_periodic_row(size_t step, fe out[9]);
 }  // namespace zk

@@ -1953,6 +1953,200 @@ hipError_t eval_constraints_ext(hipStream_t st, const fe *lde, int log_n, int lo
                                 (size_t)8 << log_n, comp, bnd);
 }
 
+// ================================================================ trace validation
+// Trace::validate of winterfell 0.9 (the #[cfg(debug_assertions)] step of Prover::prove) for ProcessorAir:
+// evaluate_transition (air/src/lib.rs:104-168, constrains.rs:95-216, flags.rs:37-91) at the n - 2 trace-domain
+// steps with the raw periodic values (row s mod 16 of CYCLE_MASK || round constants, lib.rs:201-225), each of the
+// 20 values tested against zero on its own, and the 22 assertions of get_assertions (lib.rs:170-195) in that
+// method's order.  An evaluator body of its own: no coefficient, no divisor, no extension plane, nothing shared
+// with k_eval_constraints but the small helpers (cube, mds_row, adj_row with the 3^-72 correction, ZK_SEQ).
+// One thread per step s < n - 2; lane l of a wave reads trace[c n + s] and trace[c n + s + 1], consecutive 16-B
+// elements across the lanes.  Every operation returns the canonical representative, so "value != 0" is the exact
+// test on canonical trace cells.
+// Reduction: nothing is written for a block without a failing step (one barrier-or).  Otherwise per constraint a
+// ballot, its popcount and its lowest set lane (lanes are ascending steps) per wave, the four waves combined
+// through LDS, then one 64-bit atomicAdd and one atomicMin per failing constraint per block and one add for the
+// failing steps: device-scope integer atomics, so the report does not depend on the arrival order.
+__global__ void __launch_bounds__(256, ZK_EVAL_WAVES) k_validate_trace(const fe *trace, size_t n, const fe *per_tab,
+                                                                        fe delta, int L, ValReport *rep) {
+    __shared__ unsigned sh_cnt[4][20];
+    __shared__ unsigned long long sh_min[4][20];
+    __shared__ unsigned sh_steps[4];
+    __shared__ fe vstash[6][256];  // 24 KiB: four blocks a CU (the register budget's 16 waves) fit its 160 KiB
+    const int tid = threadIdx.x;
+    const size_t s = blockIdx.x * (size_t)256 + tid;
+    const size_t steps = n - 2;
+    if (blockIdx.x == 0 && tid < 22) {
+        // assertion k: clk@0, depth@0, (7+i)@0 / (7+i)@n-2 for i < 2, (12+i)@0 / (12+i)@n-2 for i < 8.  The host wrote
+        // the asserted value into a_found[k]; this thread alone reads it and replaces it with the cell's value
+        const int k = tid;
+        const int col = k == 0 ? 0 : k == 1 ? 11 : k < 6 ? 7 + ((k - 2) >> 1) : 12 + ((k - 6) >> 1);
+        const size_t step = (k >= 2 && (k & 1)) ? steps : 0;
+        const fe want = rep->a_found[k], got = trace[(size_t)col * n + step];
+        if (!fe_eq(want, got)) atomicOr(&rep->a_mask, 1u << k);
+        rep->a_found[k] = got;
+    }
+    unsigned mask = 0;
+    if (s < steps) {
+        const fe *tb = trace;  // laundered by ZK_SEQ between the sections
+#define VCUR(c) tb[(size_t)(c)*n + s]
+#define VNXT(c) tb[(size_t)(c)*n + s + 1]
+#define VSET(k, val) mask |= fe_is_zero(val) ? 0u : (1u << (k))
+        const fe one = fe_one();
+        // only the mask is live across the two sections: the five bits and s0' wait in a lane-private LDS slot (with
+        // them in registers the Rescue section spilled 22 VGPRs at this occupancy), and the complements and the
+        // selectors are formed where they are used
+        {
+            const fe b0 = VCUR(5), b1 = VCUR(4), b2 = VCUR(3), b3 = VCUR(2), b4 = VCUR(1);
+            const fe s0n = VNXT(12);
+            vstash[0][tid] = b0;
+            vstash[1][tid] = b1;
+            vstash[2][tid] = b2;
+            vstash[3][tid] = b3;
+            vstash[4][tid] = b4;
+            vstash[5][tid] = s0n;
+            // 12..15 Rescue round, 16..19 copy (constrains.rs:182-216)
+            // flags.rs: is_push = b0 (1 - b1)(1 - b2)(1 - b3)(1 - b4)
+            const fe is_push = fe_mul(fe_mul(fe_mul(fe_mul(b0, fe_sub(one, b1)), fe_sub(one, b2)), fe_sub(one, b3)),
+                                      fe_sub(one, b4));
+            fe opc = b0;  // 16 b0 + 8 b1 + 4 b2 + 2 b3 + b4
+            opc = fe_add(fe_add(opc, opc), b1);
+            opc = fe_add(fe_add(opc, opc), b2);
+            opc = fe_add(fe_add(opc, opc), b3);
+            opc = fe_add(fe_add(opc, opc), b4);
+            const fe push_term = fe_mul(s0n, is_push);
+            ZK_SEQ(tb, push_term.lo);
+            const fe *per = per_tab + (s & 15) * 9;
+            const fe c7 = VCUR(7), c8 = VCUR(8);
+            fe x[4] = {cube(c7), cube(c8), cube(VCUR(9)), cube(VCUR(10))};
+            fe m0[4];
+#pragma unroll
+            for (int r = 0; r < 4; r++) m0[r] = fe_add(mds_row(r, x), per[1 + r]);
+            m0[0] = fe_add(m0[0], opc);
+            m0[1] = fe_add(m0[1], push_term);
+            ZK_SEQ(tb, m0[3].lo);
+            const fe hf = per[0], h0 = VCUR(6);
+            fe y[4];
+            {
+                // 16..19 first: the next-row sponge words are consumed as they arrive
+                const fe nf = fe_sub(one, hf);
+                const fe n7 = VNXT(7), n8 = VNXT(8), n9 = VNXT(9), n10 = VNXT(10);
+                VSET(16, fe_mul(fe_mul(fe_sub(n7, c7), nf), h0));
+                VSET(17, fe_mul(fe_mul(fe_sub(n8, c8), nf), h0));
+                VSET(18, fe_mul(fe_mul(n9, nf), h0));
+                VSET(19, fe_mul(fe_mul(n10, nf), h0));
+                y[0] = fe_sub(n7, per[5]);
+                y[1] = fe_sub(n8, per[6]);
+                y[2] = fe_sub(n9, per[7]);
+                y[3] = fe_sub(n10, per[8]);
+            }
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                // (INV_MDS y)_r^3 = (adj_r y)^3 3^-72
+                const fe v3 = fe_mul(cube(adj_row(r, y)), ZK_INV3_72);
+                VSET(12 + r, fe_mul(fe_mul(fe_sub(v3, m0[r]), hf), h0));
+            }
+        }
+        ZK_SEQ(tb, mask);
+        {
+            // 0 clock, 2 shift, 8..11 the selectors that move one value
+            const fe b0 = vstash[0][tid], b1 = vstash[1][tid], b2 = vstash[2][tid], b3 = vstash[3][tid],
+                     b4 = vstash[4][tid], s0n = vstash[5][tid];
+            const fe s0 = VCUR(12), s1 = VCUR(13);
+            VSET(0, fe_sub(VNXT(0), fe_add(VCUR(0), one)));
+            VSET(2, fe_mul(b0, b1));
+            const fe nb0 = fe_sub(one, b0), nb1 = fe_sub(one, b1), nb2 = fe_sub(one, b2), nb3 = fe_sub(one, b3),
+                     nb4 = fe_sub(one, b4);
+            fe is_read2;
+            {
+                // flags.rs: the three selectors that start b0 (1 - b1)(1 - b2)
+                const fe pp = fe_mul(fe_mul(b0, nb1), nb2), pn3 = fe_mul(pp, nb3);
+                const fe d1 = fe_sub(VNXT(13), s0);
+                VSET(8, fe_mul(fe_mul(pn3, nb4), d1));
+                VSET(9, fe_mul(fe_mul(pn3, b4), d1));
+                is_read2 = fe_mul(fe_mul(pp, b3), nb4);
+                VSET(10, fe_mul(is_read2, fe_sub(VNXT(17), s0)));
+            }
+            const fe is_noop = fe_mul(fe_mul(fe_mul(fe_mul(nb0, nb1), nb2), nb3), nb4);
+            VSET(11, fe_mul(is_noop, fe_sub(s0n, s0)));
+            // the selectors that start (1 - b0) b1: add, sadd, add2, mul over (1 - b2), smul over b2
+            const fe q = fe_mul(nb0, b1), qa = fe_mul(q, nb2);
+            const fe is_add = fe_mul(fe_mul(qa, nb3), nb4), is_sadd = fe_mul(fe_mul(qa, b3), nb4),
+                     is_add2 = fe_mul(fe_mul(qa, b3), b4), is_mul = fe_mul(fe_mul(qa, nb3), b4),
+                     is_smul = fe_mul(fe_mul(fe_mul(q, b2), nb3), nb4);
+            VSET(3, fe_mul(is_add, fe_sub(s0n, fe_add(s0, s1))));
+            VSET(6, fe_mul(is_mul, fe_sub(s0n, fe_mul(s0, s1))));
+            // 1 depth: d' - d - b0 + b1 - 4 read2 + 4 add2
+            {
+                fe v = fe_add(fe_sub(fe_sub(VNXT(11), VCUR(11)), b0), b1);
+                fe r4 = fe_add(is_read2, is_read2), a4 = fe_add(is_add2, is_add2);
+                r4 = fe_add(r4, r4);
+                a4 = fe_add(a4, a4);
+                VSET(1, fe_add(fe_sub(v, r4), a4));
+            }
+            ZK_SEQ(tb, mask);
+            // 4 sadd / 5 add2 / 7 smul over the lwe_size ciphertext limbs (fhe/src/server_key.rs:89-124), limb by
+            // limb as the reference sums them
+            fe a4 = fe_zero(), a5 = fe_zero(), a7 = fe_zero();
+            for (int i = 0; i < L; i++) {
+                const fe sn = VNXT(12 + i), si1 = VCUR(13 + i);
+                const fe triv = i == L - 1 ? fe_mul(s0, delta) : fe_zero();  // encrypt_trivial: delta s0 in the body
+                a4 = fe_add(a4, fe_sub(sn, fe_add(si1, triv)));
+                a5 = fe_add(a5, fe_sub(sn, fe_add(VCUR(12 + i), VCUR(12 + L + i))));
+                a7 = fe_add(a7, fe_sub(sn, fe_mul(si1, s0)));
+            }
+            VSET(4, fe_mul(is_sadd, a4));
+            VSET(5, fe_mul(is_add2, a5));
+            VSET(7, fe_mul(is_smul, a7));
+        }
+#undef VCUR
+#undef VNXT
+#undef VSET
+    }
+    // block-uniform: a block without a failing step is done
+    if (!__syncthreads_or(mask != 0)) return;
+    const int wave = tid >> 6, lane = tid & 63;
+    const unsigned long long any = __ballot(mask != 0);
+    unsigned my_cnt = 0;
+    unsigned long long my_min = ~0ull;
+    if (any) {  // wave-uniform
+        for (int k = 0; k < 20; k++) {
+            const unsigned long long b = __ballot((mask >> k) & 1u);
+            if (lane == k && b) {
+                my_cnt = (unsigned)__popcll(b);
+                my_min = (s - lane) + (unsigned)__builtin_ctzll(b);
+            }
+        }
+    }
+    if (lane < 20) {
+        sh_cnt[wave][lane] = my_cnt;
+        sh_min[wave][lane] = my_min;
+    }
+    if (lane == 20) sh_steps[wave] = (unsigned)__popcll(any);
+    __syncthreads();
+    if (tid < 20) {
+        unsigned long long cnt = 0, mn = ~0ull;
+        for (int w = 0; w < 4; w++) {
+            cnt += sh_cnt[w][tid];
+            mn = sh_min[w][tid] < mn ? sh_min[w][tid] : mn;
+        }
+        if (cnt) {
+            atomicAdd(&rep->t_count[tid], cnt);
+            atomicMin(&rep->t_first[tid], mn);
+        }
+    } else if (tid == 20) {
+        atomicAdd(&rep->failing_steps, (unsigned long long)sh_steps[0] + sh_steps[1] + sh_steps[2] + sh_steps[3]);
+    }
+}
+
+hipError_t validate_trace(hipStream_t st, const fe *trace, size_t n, const fe *per_tab, fe delta, int lwe_size,
+                          ValReport *rep) {
+    const size_t steps = n - 2;  // (n >= 16: checked by the entry points)
+    ZK_PROF(st, "validate_trace", 448.0 * n, hipLaunchKernelGGL(k_validate_trace, dim3(cdiv(steps, 256)), dim3(256), 0, st,
+                                                                trace, n, per_tab, delta, lwe_size, rep));
+    return hipGetLastError();
+}
+
 // ================================================================ composition interpolation (K4)
 __global__ void __launch_bounds__(256) k_comp_cross(CrossMap m, const fe *wi_lo, const fe *wi_hi,
                                                     const fe *i3_lo, const fe *i3_hi, fe scale, fe w8inv,

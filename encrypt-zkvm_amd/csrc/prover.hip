@@ -390,6 +390,15 @@ static int create_prover(int device, size_t max_n, uint32_t max_b, int world, zk
     ZK_CHECK_HIP(A.alloc((uint8_t **)&p->fold_consts, sizeof(FoldConsts)));
     ZK_CHECK_HIP(A.alloc(&p->fri_seed, 32));
     ZK_CHECK_HIP(A.alloc(&p->fri_alphas, 2 * ZK_MAX_FRI_LAYERS));
+    // trace validation: the report and the raw periodic table (the Rescue constants, as the AIR lists them)
+    ZK_CHECK_HIP(A.alloc(&p->val_rep, 1));
+    ZK_CHECK_HIP(A.alloc(&p->val_per, 16 * 9));
+    {
+        fe per[16 * 9];
+        for (int r = 0; r < 16; r++) air_periodic_row((size_t)r, per + 9 * r);
+        ZK_CHECK_HIP(hipMemcpyAsync(p->val_per, per, sizeof per, hipMemcpyHostToDevice, p->st));
+        ZK_CHECK_HIP(hipStreamSynchronize(p->st));
+    }
     *out = p.release();
     return ZK_OK;
 }
@@ -774,6 +783,17 @@ BatchPlan zk::plan_batch(size_t nl, const std::vector<uint64_t> &idx) {
 
 // ---------------------------------------------------------------- the prove path
 // ---------------------------------------------------------------- protocol steps (host side)
+// the two checks of a trace alone, shared with the validation entry points (same bounds, same messages)
+static int check_trace_len(size_t n, size_t max_n) {
+    if (n < 16 || (n & (n - 1)) || n > max_n) ZK_FAIL(ZK_ERR_INVALID_ARG, "trace length must be a power of two in [16, max_trace_len]");
+    return ZK_OK;
+}
+static int check_lwe_size(const zk_pub_inputs *pub) {
+    if (pub->lwe_size == 0 || pub->lwe_size > 5)
+        ZK_FAIL(ZK_ERR_INVALID_ARG, "lwe_size must be in [1, 5] (enforce_add2 reads 2*lwe_size stack items, constrains.rs:129)");
+    return ZK_OK;
+}
+
 int zk::check_prove_args(size_t n, size_t max_n, uint32_t max_b, const zk_options *o, const zk_pub_inputs *pub) {
     if (!o || !pub) ZK_FAIL(ZK_ERR_INVALID_ARG, "null argument");
     if ((o->field_extension != 1 && o->field_extension != 2) || o->blowup < 8 || (o->blowup & (o->blowup - 1)) ||
@@ -783,10 +803,9 @@ int zk::check_prove_args(size_t n, size_t max_n, uint32_t max_b, const zk_option
         ZK_FAIL(ZK_ERR_INVALID_ARG, "unsupported proof options");
     // winter-air ProofOptions::new asserts grinding_factor <= 32 (and the proof stores it as one byte)
     if (o->grinding > 32) ZK_FAIL(ZK_ERR_INVALID_ARG, "grinding factor must be at most 32");
-    if (n < 16 || (n & (n - 1)) || n > max_n) ZK_FAIL(ZK_ERR_INVALID_ARG, "trace length must be a power of two in [16, max_trace_len]");
+    ZK_TRY(check_trace_len(n, max_n));
     if (o->blowup > max_b) ZK_FAIL(ZK_ERR_INVALID_ARG, "blowup exceeds the prover's max_blowup");
-    if (pub->lwe_size == 0 || pub->lwe_size > 5)
-        ZK_FAIL(ZK_ERR_INVALID_ARG, "lwe_size must be in [1, 5] (enforce_add2 reads 2*lwe_size stack items, constrains.rs:129)");
+    ZK_TRY(check_lwe_size(pub));
     if (o->num_queries >= n * o->blowup) ZK_FAIL(ZK_ERR_INVALID_ARG, "num_queries must be smaller than the LDE domain");
     return ZK_OK;
 }
@@ -2562,9 +2581,171 @@ static int prove_once(zk_prover *p, const TraceSrc &src, size_t n, const zk_opti
     return deliver_proof(bytes, degree_flag, proof_out, proof_len);
 }
 
+// ---------------------------------------------------------------- trace validation
+// Trace::validate (winterfell 0.9, the debug-build step of Prover::prove) on the GPU: include/zkvm_gpu.h
+// "trace validation" fixes the semantics; kernels.hip k_validate_trace is the device side.
+static std::string u128_dec(fe v) {
+    unsigned __int128 x = ((unsigned __int128)v.hi << 64) | v.lo;
+    if (!x) return "0";
+    std::string s;
+    while (x) {
+        s.insert(s.begin(), (char)('0' + (int)(x % 10)));
+        x /= 10;
+    }
+    return s;
+}
+
+// the trace is on p's device at d_trace; arguments are checked
+static int validate_on_device(zk_prover *p, const fe *d_trace, size_t n, const zk_pub_inputs *pub, zk_validation *out) {
+    ZK_CHECK_HIP(hipSetDevice(p->device));
+    IoScope io_scope(p);
+    zk_validation V;
+    memset(&V, 0, sizeof V);
+    V.trace_len = n;
+    V.steps_checked = n - 2;
+    V.first_index = -1;
+    // get_assertions (air/src/lib.rs:170-195), in its own order
+    fe expect[NUM_ASSERTS];
+    {
+        int k = 0;
+        auto put = [&](int col, size_t step, fe v) {
+            V.a_col[k] = (uint32_t)col;
+            V.a_step[k] = step;
+            expect[k] = v;
+            fe_to_bytes(v, V.a_expected[k]);
+            k++;
+        };
+        put(0, 0, fe_zero());
+        put(11, 0, fe_zero());
+        for (int i = 0; i < 2; i++) {
+            put(7 + i, 0, fe_zero());
+            put(7 + i, n - 2, fe_from_bytes(pub->program_hash[i]));
+        }
+        for (int i = 0; i < 8; i++) {
+            put(12 + i, 0, fe_zero());
+            put(12 + i, n - 2, fe_from_bytes(pub->stack_outputs[i]));
+        }
+    }
+    ValReport R;
+    memset(&R, 0, sizeof R);
+    for (int k = 0; k < NUM_TCONS; k++) R.t_first[k] = ~0ull;
+    for (int k = 0; k < NUM_ASSERTS; k++) R.a_found[k] = expect[k];
+    ZK_TRY(h2d_small(p, p->val_rep, &R, sizeof R));
+    ZK_CHECK_HIP(validate_trace(p->st, d_trace, n, p->val_per, fe_make(pub->delta), (int)pub->lwe_size, p->val_rep));
+    ZK_TRY(d2h_small(p, &R, p->val_rep, sizeof R));
+    ZK_TRY(d2h_flush(p));
+    V.failing_steps = R.failing_steps;
+    V.a_mask = R.a_mask;
+    V.a_failed = (uint32_t)__builtin_popcount(R.a_mask);
+    for (int k = 0; k < NUM_ASSERTS; k++) fe_to_bytes(R.a_found[k], V.a_found[k]);
+    for (int k = 0; k < ZK_MAX_TCONS; k++) V.t_first[k] = UINT64_MAX;
+    // the slow path: per failing constraint, rows t_first and t_first + 1 come back (28 pairs of neighbouring cells,
+    // one strided copy) and the host evaluator fills the value -- and must agree that it is not zero
+    for (int k = 0; k < NUM_TCONS; k++) {
+        V.t_count[k] = R.t_count[k];
+        if (!R.t_count[k]) continue;
+        const uint64_t s = R.t_first[k];
+        if (s >= n - 2) ZK_FAIL(ZK_ERR_DEVICE, "trace validation: the device reported a step outside the trace");
+        V.t_first[k] = s;
+        fe rows[W][2], cur[W], nxt[W], per[9], ev[NUM_TCONS];
+        ZK_CHECK_HIP(hipMemcpy2DAsync(rows, 2 * sizeof(fe), d_trace + s, n * sizeof(fe), 2 * sizeof(fe), W,
+                                      hipMemcpyDeviceToHost, p->st));
+        ZK_CHECK_HIP(hipStreamSynchronize(p->st));
+        for (int c = 0; c < W; c++) {
+            cur[c] = rows[c][0];
+            nxt[c] = rows[c][1];
+        }
+        air_periodic_row((size_t)s, per);
+        air_eval_base(cur, nxt, per, pub->lwe_size, pub->delta, ev);
+        if (fe_is_zero(ev[k]))
+            ZK_FAIL(ZK_ERR_DEVICE, "trace validation: device and host evaluators disagree at step " + std::to_string(s) +
+                                       " (transition constraint " + std::to_string(k) + ")");
+        fe_to_bytes(ev[k], V.t_value[k]);
+    }
+    // the first failure as winterfell's Trace::validate meets it: assertions first, then steps in order
+    std::string msg;
+    if (V.a_mask) {
+        const int k = __builtin_ctz(V.a_mask);
+        V.first_kind = 1;
+        V.first_index = k;
+        V.first_step = V.a_step[k];
+        msg = "trace does not satisfy assertion main_trace(" + std::to_string(V.a_col[k]) + ", " +
+              std::to_string(V.a_step[k]) + ") == " + u128_dec(expect[k]);
+    } else if (V.failing_steps) {
+        int best = -1;
+        for (int k = 0; k < NUM_TCONS; k++)
+            if (V.t_count[k] && (best < 0 || V.t_first[k] < V.t_first[best])) best = k;
+        if (best < 0) ZK_FAIL(ZK_ERR_DEVICE, "trace validation: failing steps without a failing constraint");
+        V.first_kind = 2;
+        V.first_index = best;
+        V.first_step = V.t_first[best];
+        msg = "main transition constraint " + std::to_string(best) + " did not evaluate to ZERO at step " +
+              std::to_string(V.first_step);
+    }
+    p->val_last = V;
+    p->val_have = true;
+    *out = V;
+    if (V.first_kind == 0) return ZK_OK;
+    ZK_FAIL(ZK_ERR_TRACE, msg + "; " + std::to_string(V.failing_steps) + " failing steps, " + std::to_string(V.a_failed) +
+                              " failed assertions");
+}
+
+static int check_validate_args(zk_prover *p, const void *trace, size_t n, const zk_pub_inputs *pub, zk_validation *out) {
+    if (!p || !trace || !pub || !out) ZK_FAIL(ZK_ERR_INVALID_ARG, "null argument");
+    ZK_REQUIRE_FULL_PROVER(p);
+    ZK_TRY(check_trace_len(n, p->max_n));
+    return check_lwe_size(pub);
+}
+
+int zk_validate_device(zk_prover *p, const void *d_trace, size_t n, const zk_pub_inputs *pub, zk_validation *out) {
+    ZK_TRY(check_validate_args(p, d_trace, n, pub, out));
+    return validate_on_device(p, (const fe *)d_trace, n, pub, out);
+}
+
+int zk_validate_columns(zk_prover *p, const uint8_t *const *columns, size_t n, const zk_pub_inputs *pub,
+                        zk_validation *out) {
+    ZK_TRY(check_validate_args(p, columns, n, pub, out));
+    for (int c = 0; c < W; c++)
+        if (!columns[c]) ZK_FAIL(ZK_ERR_INVALID_ARG, "null trace column");
+    ZK_CHECK_HIP(hipSetDevice(p->device));
+    // one full upload, every column whole (a debugging aid: none of the prove path's column classes)
+    for (int c = 0; c < W; c++)
+        ZK_CHECK_HIP(hipMemcpyAsync(p->d_trace + (size_t)c * n, columns[c], n * sizeof(fe), hipMemcpyHostToDevice, p->st));
+    const int rc = validate_on_device(p, p->d_trace, n, pub, out);
+    (void)hipStreamSynchronize(p->st);  // the caller's columns are free again on every way out
+    return rc;
+}
+
+int zk_prover_set_validate(zk_prover *p, int on) {
+    if (!p) ZK_FAIL(ZK_ERR_INVALID_ARG, "null prover");
+    p->validate = on != 0;
+    return ZK_OK;
+}
+
+int zk_prover_validation(const zk_prover *p, zk_validation *out) {
+    if (!p || !out) ZK_FAIL(ZK_ERR_INVALID_ARG, "null argument");
+    if (!p->val_have) ZK_FAIL(ZK_ERR_INVALID_ARG, "no validation has run on this prover");
+    *out = p->val_last;
+    return ZK_OK;
+}
+
+// zk_prover_set_validate(p, 1): Trace::validate before the proof.  Arguments the prove path would refuse are left
+// for it to report; a failing trace ends the call with ZK_ERR_TRACE and an empty proof before prove_impl is entered,
+// so no hint or snapshot state moves.
+static int validate_first(zk_prover *p, const void *d_trace, const uint8_t *const *cols, size_t n, const zk_options *opt,
+                          const zk_pub_inputs *pub, size_t *proof_len) {
+    if (!p || !p->validate || !proof_len || p->shard_world > 1) return ZK_OK;
+    if (check_prove_args(n, p->max_n, p->max_b, opt, pub) != ZK_OK) return ZK_OK;
+    zk_validation v;
+    const int rc = cols ? zk_validate_columns(p, cols, n, pub, &v) : zk_validate_device(p, d_trace, n, pub, &v);
+    if (rc != ZK_OK) *proof_len = 0;
+    return rc;
+}
+
 int zk_prove_device(zk_prover *p, const void *d_trace, size_t n, const zk_options *opt, const zk_pub_inputs *pub,
                     uint8_t *proof_out, size_t *proof_len, zk_record *rec, const zk_dump *dump) {
     if (!d_trace) ZK_FAIL(ZK_ERR_INVALID_ARG, "null argument");
+    ZK_TRY(validate_first(p, d_trace, nullptr, n, opt, pub, proof_len));
     TraceSrc src;
     src.dev = (const fe *)d_trace;
     return prove_impl(p, src, n, opt, pub, proof_out, proof_len, rec, dump);
@@ -2625,6 +2806,7 @@ int zk_prove_columns_ex(zk_prover *p, const uint8_t *const *columns, size_t n, c
     if (!columns) ZK_FAIL(ZK_ERR_INVALID_ARG, "null argument");
     for (int c = 0; c < W; c++)
         if (!columns[c]) ZK_FAIL(ZK_ERR_INVALID_ARG, "null trace column");
+    ZK_TRY(validate_first(p, nullptr, columns, n, opt, pub, proof_len));
     TraceSrc src;
     src.cols = columns;
     return prove_impl(p, src, n, opt, pub, proof_out, proof_len, rec, dump);

@@ -328,6 +328,12 @@ struct zk_prover {
     std::vector<double> kstat_muls, kstat_addsubs;
     size_t last_n = 0;
     uint32_t last_b = 0;
+    // trace validation (zk_validate_device): the device report and the raw 16 x 9 periodic table, allocated and
+    // filled with the prover; the switch of zk_prover_set_validate and the last report (zk_prover_validation)
+    zk::ValReport *val_rep = nullptr;
+    fe *val_per = nullptr;
+    bool validate = false, val_have = false;
+    zk_validation val_last = {};
 };
 
 namespace zk {

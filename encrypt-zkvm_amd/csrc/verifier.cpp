@@ -473,6 +473,24 @@ void verify(const uint8_t *proof, size_t plen, const zk_pub_inputs *pub, uint32_
 
 }  // namespace
 
+// The frame evaluator over the base field (air_shape.hpp): trace validation's host side (prover.hip) fills the
+// report's constraint values with it and cross-checks the device evaluator.  lwe_size in [1, 5] (the caller's check).
+void zk::air_eval_base(const fe *cur, const fe *nxt, const fe *per, uint32_t lwe_size, uint32_t delta, fe *out) {
+    fe2 c[W], x[W], q[9], ev[NT];
+    for (int i = 0; i < W; i++) {
+        c[i] = fe2_lift(cur[i]);
+        x[i] = fe2_lift(nxt[i]);
+    }
+    for (int i = 0; i < 9; i++) q[i] = fe2_lift(per[i]);
+    air_eval(c, x, q, lwe_size, fe_make(delta), ev);
+    for (int k = 0; k < NT; k++) out[k] = ev[k].a;
+}
+
+void zk::air_periodic_row(size_t step, fe out[9]) {
+    const int r = (int)(step & 15);
+    out[0] = fe_make(r < 14 ? 1 : 0);
+    for (int c = 0; c < 8; c++) out[1 + c] = fe_make(ZK_ARK[8 * r + c][0], ZK_ARK[8 * r + c][1]);
+}
 
 // The verifier's out-of-domain identity (winterfell verifier: evaluate_constraints at z against the
 // composition columns): sum_k ct_k C_k(z) * divisor(z) + boundary terms == sum_j z^(jn) H_j(z).

@@ -538,7 +538,9 @@ int zk_vm_prove(zk_prover *p, zk_program *prog, const uint8_t *public_in, size_t
     read_last(last_row, last);
     // ZK_VM_PREPROCESS=0: every column from the device trace (no per-program preprocessed columns)
     const char *pe = getenv("ZK_VM_PREPROCESS");
-    const bool pre = !(pe && !strcmp(pe, "0")) && opt->blowup <= p->max_b && opt->blowup >= 8;
+    // zk_prover_set_validate(p, 1): Trace::validate needs every column of the written trace in HBM, so the call takes
+    // the all-columns path and zk_prove_device validates before it proves (the same proof bytes either way)
+    const bool pre = !(pe && !strcmp(pe, "0")) && opt->blowup <= p->max_b && opt->blowup >= 8 && !p->validate;
     size_t n = 0;
     zk_program::Fixed f{};
     uint32_t md = 0;

@@ -277,6 +277,21 @@ hipError_t upload_rescue_consts(hipStream_t st);
 // bnd: the boundary (assertion) terms are evaluated per row (else: boundary_poly_add after interpolation)
 hipError_t eval_constraints_mapped(hipStream_t st, const fe *lde, int log_n, EvalMap map, const fe *periodic,
                              const fe *divs, const AirConsts *consts_dev, fe *comp, bool bnd = true);
+// Trace validation (kernels.hip k_validate_trace; zk_validate_device): the device report of one launch.  The host
+// initialises it in-stream: counts 0, firsts UINT64_MAX, a_mask 0 and a_found[k] = the value assertion k asserts
+// (get_assertions order, air/src/lib.rs:170-195), which the kernel replaces with the asserted cell's value.
+struct ValReport {
+    unsigned long long t_count[20];  // per transition constraint: steps s < n - 2 where it is non-zero
+    unsigned long long t_first[20];  // the lowest such step
+    unsigned long long failing_steps;
+    unsigned a_mask, pad_;
+    fe a_found[22];
+};
+static_assert(sizeof(ValReport) < 1024, "the validation report stays a small transfer");
+// per_tab: the raw periodic table, 16 rows of CYCLE_MASK || 8 round constants (air/src/lib.rs:201-225); trace:
+// 28 x n column-major, n >= 16
+hipError_t validate_trace(hipStream_t st, const fe *trace, size_t n, const fe *per_tab, fe delta, int lwe_size,
+                          ValReport *rep);
 // Inputs of the cross-coset step for coefficients k0 .. k0+kcount: c[r][kl] = c_r[k0 + kl]; output
 // polys[k2 * pstride + kl].
 struct CrossMap {

@@ -22,6 +22,7 @@ ZK_ERR_PROGRAM = -10
 ZK_ERR_STACK = -11
 ZK_ERR_CHIPLETS = -12
 ZK_ERR_DEGREE = -20
+ZK_ERR_TRACE = -21
 ZK_ERR_VERIFY = -30
 
 MAX_COLS, MAX_TCONS, MAX_ASSERTS, MAX_CCOLS, MAX_FRI, MAX_REM, MAX_Q = 32, 32, 32, 16, 16, 256, 255
@@ -38,6 +39,7 @@ EXPORTED = (
     "zk_program_compile", "zk_program_trace", "zk_program_free", "zk_vm_last_error", "zk_vm_trace_device",
     "zk_vm_prove",
     "zk_vm_prove_sharded",
+    "zk_validate_device", "zk_validate_columns", "zk_prover_set_validate", "zk_prover_validation",
 )
 
 
@@ -66,6 +68,37 @@ class ProofInfo(C.Structure):
     """zk_proof_info (include/zkvm_gpu.h): what the last proof on a prover did."""
     _fields_ = [("schedule", C.c_int32), ("hint_redos", C.c_uint32), ("hint_sets", C.c_uint32),
                 ("hinted_sparse", C.c_uint32), ("derived", C.c_uint32), ("fixed_sets", C.c_uint32)]
+
+
+class Validation(C.Structure):
+    """zk_validation (include/zkvm_gpu.h): the report of one trace validation (Trace::validate of winterfell 0.9)."""
+    _fields_ = [
+        ("trace_len", C.c_uint64), ("steps_checked", C.c_uint64), ("failing_steps", C.c_uint64),
+        ("t_count", C.c_uint64 * MAX_TCONS), ("t_first", C.c_uint64 * MAX_TCONS),
+        ("t_value", C.c_uint8 * (16 * MAX_TCONS)),
+        ("a_failed", C.c_uint32), ("a_mask", C.c_uint32),
+        ("a_col", C.c_uint32 * MAX_ASSERTS), ("a_step", C.c_uint64 * MAX_ASSERTS),
+        ("a_expected", C.c_uint8 * (16 * MAX_ASSERTS)), ("a_found", C.c_uint8 * (16 * MAX_ASSERTS)),
+        ("first_kind", C.c_int32), ("first_index", C.c_int32), ("first_step", C.c_uint64),
+    ]
+
+    NUM_TCONS, NUM_ASSERTS = 20, 22  # ProcessorAir: evaluate_transition's results, get_assertions' entries
+
+    def to_dict(self) -> dict:
+        """The report as plain ints (field elements as Python ints), the arrays cut to the AIR's 20 constraints
+        and 22 assertions."""
+        t, a = self.NUM_TCONS, self.NUM_ASSERTS
+        el = lambda b, k: int.from_bytes(bytes(b[16 * k:16 * k + 16]), "little")  # noqa: E731
+        return {
+            "trace_len": self.trace_len, "steps_checked": self.steps_checked, "failing_steps": self.failing_steps,
+            "t_count": list(self.t_count[:t]), "t_first": list(self.t_first[:t]),
+            "t_value": [el(self.t_value, k) for k in range(t)],
+            "a_failed": self.a_failed, "a_mask": self.a_mask,
+            "a_col": list(self.a_col[:a]), "a_step": list(self.a_step[:a]),
+            "a_expected": [el(self.a_expected, k) for k in range(a)],
+            "a_found": [el(self.a_found, k) for k in range(a)],
+            "first_kind": self.first_kind, "first_index": self.first_index, "first_step": self.first_step,
+        }
 
 
 class Record(C.Structure):
@@ -175,6 +208,10 @@ def lib():
         L.zk_host_unregister.argtypes = [vp]
         L.zk_prove_device.argtypes = [vp, vp, sz, C.POINTER(Options), C.POINTER(PubInputs), vp, C.POINTER(sz),
                                       C.POINTER(Record), C.POINTER(Dump)]
+        L.zk_validate_device.argtypes = [vp, vp, sz, C.POINTER(PubInputs), C.POINTER(Validation)]
+        L.zk_validate_columns.argtypes = [vp, C.POINTER(vp), sz, C.POINTER(PubInputs), C.POINTER(Validation)]
+        L.zk_prover_set_validate.argtypes = [vp, i32]
+        L.zk_prover_validation.argtypes = [vp, C.POINTER(Validation)]
         L.zk_lde_new.argtypes = [vp, vp, sz, sz, u32, C.POINTER(vp), vp]
         L.zk_lde_read_frame.argtypes = [vp, sz, vp, vp]
         L.zk_lde_query.argtypes = [vp, vp, sz, vp, vp, C.POINTER(sz)]

@@ -91,28 +91,65 @@ class GpuProver:
         return p.value
 
     def prove_device(self, d_trace: int, n: int, pub: PubInputs, options: ProofOptions = REFERENCE_OPTIONS,
-                     record: bool = False, dump=(), allow_degree_error=False):
+                     record: bool = False, dump=(), allow_degree_error=False, allow_trace_error=False):
         """zk_prove_device: the trace is already in this prover's HBM (upload_trace)."""
         return self._prove(lambda *a: lib().zk_prove_device(self.handle, d_trace, n, *a), n, pub, options, record,
-                           dump, allow_degree_error)
+                           dump, allow_degree_error, allow_trace_error)
 
-    def prove_host(self, trace: np.ndarray, pub: PubInputs, options: ProofOptions = REFERENCE_OPTIONS,
-                   record: bool = False, dump=(), allow_degree_error=False):
-        """zk_prove_columns_ex: the trace is a (28, n, 2) uint64 host array (pinned -- HostTrace -- or
-        pageable); the library uploads it column group by column group, overlapped with the interpolation."""
-        trace = np.ascontiguousarray(trace, dtype=np.uint64)
+    def _columns(self, trace: np.ndarray):
+        """The 28 column pointers of a (28, n, 2) uint64 host array (kept on the prover and reused)."""
         assert trace.ndim == 3 and trace.shape[0] == 28 and trace.shape[2] == 2
-        n = trace.shape[1]
         if getattr(self, "_cols", None) is None:
             self._cols = (C.c_void_p * 28)()
         cols = self._cols
         base, stride = trace.ctypes.data, trace.strides[0]
         for c in range(28):
             cols[c] = base + c * stride
-        return self._prove(lambda *a: lib().zk_prove_columns_ex(self.handle, cols, n, *a), n, pub, options, record,
-                           dump, allow_degree_error)
+        return cols
 
-    def _prove(self, call, n, pub, options, record, dump, allow_degree_error):
+    def prove_host(self, trace: np.ndarray, pub: PubInputs, options: ProofOptions = REFERENCE_OPTIONS,
+                   record: bool = False, dump=(), allow_degree_error=False, allow_trace_error=False):
+        """zk_prove_columns_ex: the trace is a (28, n, 2) uint64 host array (pinned -- HostTrace -- or
+        pageable); the library uploads it column group by column group, overlapped with the interpolation."""
+        trace = np.ascontiguousarray(trace, dtype=np.uint64)
+        cols = self._columns(trace)
+        n = trace.shape[1]
+        return self._prove(lambda *a: lib().zk_prove_columns_ex(self.handle, cols, n, *a), n, pub, options, record,
+                           dump, allow_degree_error, allow_trace_error)
+
+    # ---- Trace::validate (winterfell 0.9: Prover::prove's #[cfg(debug_assertions)] step), include/zkvm_gpu.h
+    def _validated(self, rc, v):
+        """(rc, report) for ZK_OK and ZK_ERR_TRACE (the report is filled either way); anything else raises."""
+        if rc not in (native.ZK_OK, native.ZK_ERR_TRACE):
+            check(rc, "validate")
+        return rc, v.to_dict()
+
+    def validate_device(self, d_trace: int, n: int, pub: PubInputs):
+        """zk_validate_device: check a trace in this prover's HBM against ProcessorAir.  Returns (rc, report):
+        rc ZK_OK or ZK_ERR_TRACE (native.lib().zk_last_error() then names the first failure), the report a dict of
+        ints (native.Validation.to_dict)."""
+        v = native.Validation()
+        return self._validated(lib().zk_validate_device(self.handle, d_trace, n, C.byref(pub), C.byref(v)), v)
+
+    def validate_host(self, trace: np.ndarray, pub: PubInputs):
+        """zk_validate_columns: the same for a (28, n, 2) uint64 host array, at the cost of one full upload."""
+        trace = np.ascontiguousarray(trace, dtype=np.uint64)
+        v = native.Validation()
+        rc = lib().zk_validate_columns(self.handle, self._columns(trace), trace.shape[1], C.byref(pub), C.byref(v))
+        return self._validated(rc, v)
+
+    def set_validate(self, on: bool):
+        """zk_prover_set_validate: validate every trace before proving it (the reference's debug-build behaviour); a
+        failing trace then ends the prove call with ZK_ERR_TRACE and no proof."""
+        check(lib().zk_prover_set_validate(self.handle, 1 if on else 0), "zk_prover_set_validate")
+
+    def validation(self) -> dict:
+        """zk_prover_validation: the report of the last validation that ran on this prover."""
+        v = native.Validation()
+        check(lib().zk_prover_validation(self.handle, C.byref(v)), "zk_prover_validation")
+        return v.to_dict()
+
+    def _prove(self, call, n, pub, options, record, dump, allow_degree_error, allow_trace_error=False):
         opt = options.to_c()
         # one proof buffer per prover, reused across proofs (a fresh 4 MiB ctypes buffer per call was
         # ~0.15 ms of zero-fill and page faults between two proofs); only plen bytes are copied out
@@ -134,7 +171,8 @@ class GpuProver:
                 setattr(dmp, name, held[name].ctypes.data)
         rc = call(C.byref(opt), C.byref(pub), buf, C.byref(plen), C.byref(rec) if rec is not None else None,
                   C.byref(dmp) if dmp is not None else None)
-        if not (rc == 0 or (allow_degree_error and rc == native.ZK_ERR_DEGREE)):
+        if not (rc == 0 or (allow_degree_error and rc == native.ZK_ERR_DEGREE)
+                or (allow_trace_error and rc == native.ZK_ERR_TRACE)):
             check(rc, "prove")
         return C.string_at(buf, plen.value), rec, held, rc
 

@@ -175,6 +175,58 @@ int zk_host_unregister(void *ptr);
 int zk_prove_device(zk_prover *p, const void *d_trace, size_t n, const zk_options *opt, const zk_pub_inputs *pub,
                     uint8_t *proof_out, size_t *proof_len, zk_record *rec, const zk_dump *dump);
 
+/* ---- trace validation: winterfell 0.9 Prover::prove runs `trace.validate(&air)` under #[cfg(debug_assertions)]
+ * before it proves (Trace::validate: every assertion of get_assertions against the trace, then evaluate_transition
+ * at every step 0 .. n - 1 - num_transition_exemptions), and panics with the first failure:
+ *   "trace does not satisfy assertion main_trace(col, step) == value"
+ *   "main transition constraint i did not evaluate to ZERO at step s"
+ * Here the whole trace is checked on the GPU and every failure is counted, not only the first.
+ * Semantics.  Base field; trace 28 x n column-major, n and lwe_size bounded as for zk_prove.  Transition constraints:
+ * evaluate_transition (air/src/lib.rs:104-168) at steps s = 0 .. n - 3 (set_num_transition_exemptions(2), lib.rs:94),
+ * frame = rows (s, s + 1), periodic values = row s mod 16 of CYCLE_MASK || round constants (lib.rs:201-225).
+ * Assertions: the 22 of get_assertions in that method's order (lib.rs:170-195): clk@0, depth@0, (7+i)@0 and
+ * (7+i)@n-2 for i < 2, (12+i)@0 and (12+i)@n-2 for i < 8.  First failure, as winterfell would hit it: the lowest
+ * failing assertion, else the lowest failing step and at it the lowest constraint.  Row n - 1 is never constrained.
+ * Values are 16-byte little-endian field elements. */
+#define ZK_ERR_TRACE -21 /* validation: the trace violates ProcessorAir; no proof was written */
+typedef struct {
+    uint64_t trace_len, steps_checked;  /* n, n - 2 */
+    uint64_t failing_steps;             /* steps with at least one non-zero transition constraint */
+    uint64_t t_count[ZK_MAX_TCONS];     /* per constraint (evaluate_transition's result index): steps where it is non-zero */
+    uint64_t t_first[ZK_MAX_TCONS];     /* the lowest such step, UINT64_MAX if none */
+    uint8_t t_value[ZK_MAX_TCONS][16];  /* its value at t_first (zero if none) */
+    uint32_t a_failed, a_mask;          /* count; bit k = assertion k in get_assertions order */
+    uint32_t a_col[ZK_MAX_ASSERTS];
+    uint64_t a_step[ZK_MAX_ASSERTS];
+    uint8_t a_expected[ZK_MAX_ASSERTS][16], a_found[ZK_MAX_ASSERTS][16]; /* all 22 filled */
+    int32_t first_kind;                 /* 0 valid, 1 assertion, 2 transition */
+    int32_t first_index;                /* the assertion / constraint of the first failure (-1 if valid) */
+    uint64_t first_step;
+} zk_validation;
+/* Trace::validate of a trace resident in this prover's device's HBM (e.g. in zk_prover_trace_buffer).  ZK_OK for a
+ * valid trace, ZK_ERR_TRACE otherwise; `out` is filled either way.  On failure zk_last_error() carries the first
+ * failure in winterfell's wording above, then "; <failing steps> failing steps, <failed assertions> failed
+ * assertions".  One pass over the trace (448 B per row) and one small read; for each failing constraint the two
+ * rows at its first step are read back and evaluated on the host as well (t_value), and ZK_ERR_DEVICE is returned if
+ * the host finds zero where the device did not.  Refused (ZK_ERR_INVALID_ARG) for a prover of
+ * zk_prover_create_shard, like every single-GPU entry point. */
+int zk_validate_device(zk_prover *p, const void *d_trace, size_t n, const zk_pub_inputs *pub, zk_validation *out);
+/* The same for a host trace, one pointer per column (winterfell's ColMatrix, as zk_prove_columns).  A debugging aid:
+ * it costs one full upload -- the 28 columns are copied whole into the prover's trace buffer (none of zk_prove's
+ * sparse, narrow, fixed or derived column classes) and validated there. */
+int zk_validate_columns(zk_prover *p, const uint8_t *const *columns, size_t n, const zk_pub_inputs *pub,
+                        zk_validation *out);
+/* on = 1: the debug-build behaviour of Prover::prove.  zk_prove, zk_prove_columns(_ex) and zk_prove_device validate
+ * the trace first (host traces through zk_validate_columns, then proved from the host columns as always), and
+ * zk_vm_prove validates the trace it has written.  A failing trace returns ZK_ERR_TRACE with *proof_len = 0: no
+ * proof is written and no column hint or snapshot is touched.  A valid trace goes on to the same proof bytes.
+ * Default 0: nothing is validated, and a bad trace ends in ZK_ERR_DEGREE after the whole proof, as before.
+ * The sharded entry points (zk_prove_sharded, zk_vm_prove_sharded) ignore the setting. */
+int zk_prover_set_validate(zk_prover *p, int on);
+/* The report of the last validation that ran on p (by either call above or by a proof with the switch on);
+ * ZK_ERR_INVALID_ARG if none has run. */
+int zk_prover_validation(const zk_prover *p, zk_validation *out);
+
 /* ---- plug point 1: Prover::new_trace_lde (prover/src/lib.rs:55-62) -> DefaultTraceLde ---- */
 /* interpolate the trace, extend it over the blowup coset domain and commit to its rows.
  * The LDE lives in the prover's device memory until zk_lde_free. */
