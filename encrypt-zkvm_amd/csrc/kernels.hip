@@ -845,7 +845,7 @@ __global__ void __launch_bounds__(256) k_sparse_fill(NttArgs a, int ncols, int l
 }
 
 // out[i] = F[i] + d * L[i], d wave-uniform (its W set a kernel argument): the clock column's coefficients / LDE from the
-// identity column's and e_(n-1)'s (trace_lde_commit)
+// identity column's and e_(n-1)'s (trace_commit.hip)
 __global__ void __launch_bounds__(256) k_axpy_fill(const fe *F, const fe *L, fe_ws d, size_t cnt, fe *out) {
     const size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (i < cnt) out[i] = fe_add(F[i], fe_mul_uniform(L[i], d));

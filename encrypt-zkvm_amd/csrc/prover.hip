@@ -562,8 +562,8 @@ int zk_prover_proof_info(const zk_prover *p, zk_proof_info *out) {
     out->schedule = p->last_sched;
     out->hint_redos = p->hint_redos;
     for (const auto &h : p->hint_sets) out->hint_sets += h.n != 0 && h.have ? 1u : 0u;
-    out->hinted_sparse = p->sp_hinted;
-    out->derived = p->clk_used ? 1u : 0u;
+    out->hinted_sparse = p->tc.sp_hinted;
+    out->derived = p->tc.clk_used ? 1u : 0u;
     for (int i = 0; i < zk_prover::ZK_FIXED_SNAPS; i++) {
         const auto &s = p->fix_snaps[i];
         out->fixed_sets += s.live && s.owner >= 0 && p->hint_sets[s.owner].snap == i ? 1u : 0u;
@@ -574,22 +574,22 @@ int zk_prover_proof_info(const zk_prover *p, zk_proof_info *out) {
 int zk_prover_upload_stats(zk_prover *p, uint64_t *bytes, uint32_t *sparse_cols, uint32_t *narrow8_cols,
                            uint32_t *narrow32_cols) {
     if (!p) ZK_FAIL(ZK_ERR_INVALID_ARG, "null prover");
-    if (bytes) *bytes = p->up_bytes;
-    if (sparse_cols) *sparse_cols = p->up_sparse;
-    if (narrow8_cols) *narrow8_cols = p->up_nw8;
-    if (narrow32_cols) *narrow32_cols = p->up_nw32;
+    if (bytes) *bytes = p->tc.up_bytes;
+    if (sparse_cols) *sparse_cols = p->tc.up_sparse;
+    if (narrow8_cols) *narrow8_cols = p->tc.up_nw8;
+    if (narrow32_cols) *narrow32_cols = p->tc.up_nw32;
     return ZK_OK;
 }
 
 int zk_prover_upload_derived(zk_prover *p, uint32_t *derived_cols) {
     if (!p || !derived_cols) ZK_FAIL(ZK_ERR_INVALID_ARG, "null argument");
-    *derived_cols = p->clk_used ? 1u : 0u;
+    *derived_cols = p->tc.clk_used ? 1u : 0u;
     return ZK_OK;
 }
 
 int zk_prover_upload_fixed(zk_prover *p, uint32_t *fixed_cols) {
     if (!p || !fixed_cols) ZK_FAIL(ZK_ERR_INVALID_ARG, "null argument");
-    *fixed_cols = p->fix_used;
+    *fixed_cols = p->tc.fix_used;
     return ZK_OK;
 }
 
@@ -1231,854 +1231,6 @@ static int lde_commit(zk_prover *p, Plan *pl, const fe *polys, int ncols, fe *ld
     return d2h_small(p, root, nodes + 32, 32);
 }
 
-// Where the trace comes from: resident in HBM (zk_prove_device), or W host columns (zk_prove,
-// zk_prove_columns, zk_lde_new: the reference's TraceTable / ColMatrix, vm/src/lib.rs:18, 26).
-struct TraceSrc {
-    const fe *dev = nullptr;
-    const uint8_t *const *cols = nullptr;
-    const FixedCols *fixed = nullptr;  // with dev: only the dynamic columns are in dev (zk_vm_prove)
-    bool hint_ok = true;               // host columns: the sparse hint of the previous proof may be used
-    bool no_virtual = false;           // every trace LDE column written (stage dumps read them)
-    const uint8_t *key = nullptr;      // host columns: the program hash the hints are keyed by (with n)
-    uint32_t lwe = 0;                  // ... and its lwe_size (the fixed columns depend on it too)
-};
-
-// Fixed columns (zk_prover::FixedSnap).  ZK_FIXED=0 turns the class off.
-bool zk::fixed_on() {
-    static const bool on = [] {
-        const char *e = getenv("ZK_FIXED");
-        return !(e && !strcmp(e, "0"));
-    }();
-    return on;
-}
-constexpr uint32_t ZK_FIXED_CAND = 0xFFEu;  // columns 1 .. 11
-// ZK_FIXED_FUSE=0: their LDE (and the clock's, and zk_vm_prove's preprocessed columns') by the streaming passes and
-// hash_rows_blocks instead of inside the row hash of their blocks (fixed_hash)
-bool zk::fixed_fuse_on() {
-    static const bool on = [] {
-        const char *e = getenv("ZK_FIXED_FUSE");
-        return !(e && !strcmp(e, "0"));
-    }();
-    return on;
-}
-
-// forget snapshot i (its device buffers stay allocated for the next snapshot of that size)
-static void fixed_drop(zk_prover *p, int i) {
-    if (i < 0) return;
-    zk_prover::FixedSnap &s = p->fix_snaps[i];
-    if (s.owner >= 0 && p->hint_sets[s.owner].snap == i) p->hint_sets[s.owner].snap = -1;
-    s.live = false;
-    s.owner = -1;
-    s.mask = 0;
-    for (auto &h : s.host) h.reset();
-    if (p->fix_pending == i) p->fix_pending = -1;
-}
-
-// A snapshot slot for hint set `owner` with buffers for k planes of n and B n elements: a free slot (one whose
-// buffers already have that size first), else the least recently used one.  -1 if the memory is not to be had.
-static int fixed_slot(zk_prover *p, int owner, size_t n, uint32_t B, int k) {
-    const size_t np = (size_t)k * n, nl = np * B;
-    int best = -1;
-    for (int i = 0; i < zk_prover::ZK_FIXED_SNAPS; i++) {
-        const auto &s = p->fix_snaps[i];
-        if (s.live) continue;
-        if (best < 0 || (s.cap_polys == np && s.cap_lde == nl)) best = i;
-    }
-    if (best < 0) {
-        best = 0;
-        for (int i = 1; i < zk_prover::ZK_FIXED_SNAPS; i++)
-            if (p->fix_snaps[i].used < p->fix_snaps[best].used) best = i;
-        fixed_drop(p, best);
-    }
-    zk_prover::FixedSnap &s = p->fix_snaps[best];
-    if (s.cap_polys != np || s.cap_lde != nl) {
-        // (the previous proofs on this prover have drained: nothing reads the old buffers)
-        (void)hipFree(s.fpolys);
-        (void)hipFree(s.flde);
-        s.fpolys = s.flde = nullptr;
-        s.cap_polys = s.cap_lde = 0;
-        if (hipMalloc((void **)&s.fpolys, np * sizeof(fe)) != hipSuccess ||
-            hipMalloc((void **)&s.flde, nl * sizeof(fe)) != hipSuccess) {
-            (void)hipGetLastError();
-            (void)hipFree(s.fpolys);
-            s.fpolys = s.flde = nullptr;
-            return -1;
-        }
-        s.cap_polys = np;
-        s.cap_lde = nl;
-    }
-    s.owner = owner;
-    s.n = n;
-    s.B = B;
-    s.k = k;
-    return best;
-}
-
-// rows [r0, r1) of a host column against a snapshot's host copy
-bool zk::same_rows(const uint8_t *col, const uint8_t *snap, size_t r0, size_t r1, int width) {
-    if (width == 16) return !memcmp(col + 16 * r0, snap + 16 * r0, 16 * (r1 - r0));
-    const uint64_t *v = reinterpret_cast<const uint64_t *>(col);
-    uint64_t bad = 0;
-    if (width == 1) {
-        for (size_t i = r0; i < r1; i++) bad |= (v[2 * i] ^ (uint64_t)snap[i]) | v[2 * i + 1];
-    } else {
-        const uint32_t *s = reinterpret_cast<const uint32_t *>(snap);
-        for (size_t i = r0; i < r1; i++) bad |= (v[2 * i] ^ (uint64_t)s[i]) | v[2 * i + 1];
-    }
-    return bad == 0;
-}
-
-// The hint set of (n, program), or null (prover state: zk_prover::HintSet)
-static zk_prover::HintSet *hint_find(zk_prover *p, size_t n, const uint8_t *key) {
-    if (!key) return nullptr;
-    for (auto &h : p->hint_sets)
-        if (h.n == n && !memcmp(h.key, key, 32)) return &h;
-    return nullptr;
-}
-// ... found or made, evicting the least recently used set
-static zk_prover::HintSet *hint_slot(zk_prover *p, size_t n, const uint8_t *key) {
-    zk_prover::HintSet *h = hint_find(p, n, key);
-    if (h) return h;
-    h = &p->hint_sets[0];
-    for (auto &e : p->hint_sets)
-        if (e.used < h->used) h = &e;
-    fixed_drop(p, h->snap);  // an evicted set's snapshot goes with it
-    *h = zk_prover::HintSet{};
-    h->n = n;
-    memcpy(h->key, key, 32);
-    return h;
-}
-
-// Virtual columns: the first trace column no transition constraint or assertion reads -- the evaluator reads columns
-// 0 .. 12 + 2 lwe_size - 1 <= 21 (enforce_add2 reads 2 lwe_size stack items, lwe_size <= 5; constrains.rs) -- so a
-// hinted sparse column from here on needs no LDE in memory (ZK_VIRTUAL=0 writes it)
-constexpr int ZK_VIRT_MIN_COL = 22;
-static bool virtual_on() {
-    static const bool on = [] {
-        const char *e = getenv("ZK_VIRTUAL");
-        return !(e && !strcmp(e, "0"));
-    }();
-    return on;
-}
-
-// Column groups of a host-resident trace upload.  The copy engine streams group g + 1 while the CUs interpolate and
-// extend group g; more groups overlap more of the copy but add a launch drain per NTT pass and group.  A/B on one box
-// (3 provers in flight): 1 group 12.73-13.02 ms per proof at 22.7 ms latency, 2 groups 13.15-13.24 / 18.7, 4 groups
-// 13.16-13.32 / 16.8, 7 groups of 4 13.02-13.04 / 15.9 (device-resident 12.15-12.32).  Round 4: the rows are hashed
-// block by block as their columns' LDEs complete (hash_rows_blocks: a 28-element row is 7 BLAKE3 blocks of 4
-// columns), and the last 4 columns go up as two groups of 2, so after the last copy only 2 columns' NTTs, one
-// compression per row and the Merkle tree remain (latency 15.3-15.4 -> 13.9-14.2 ms against 7 groups of 4, all rows
-// hashed at the end; profiles/r04_ab_queues_pass1.txt).
-
-// hipMemcpyAsync from page-locked memory (zk_host_alloc, zk_host_register, any hipHostMalloc'd or
-// hipHostRegister'ed buffer) is a DMA in stream order; from pageable memory the runtime stages the copy
-// through its own pinned buffers and returns once the source has been read (the host thread copies).
-// Both are correct here; the pinned form is the fast one (DESIGN.md "Host-resident trace").
-// Columns that are contiguous in host memory (zk_prove's single buffer) go up as one copy per run.
-static int upload_trace_group(zk_prover *p, const TraceSrc &src, size_t n, int c0, int nc) {
-    const size_t col = n * sizeof(fe);
-    p->up_bytes += (uint64_t)nc * col;
-    for (int c = c0; c < c0 + nc;) {
-        int e = c + 1;
-        while (e < c0 + nc && src.cols[e] == src.cols[e - 1] + col) e++;
-        ZK_CHECK_HIP(hipMemcpyAsync(p->d_trace + (size_t)c * n, src.cols[c], (size_t)(e - c) * col, hipMemcpyHostToDevice,
-                                    p->up));
-        c = e;
-    }
-    return ZK_OK;
-}
-
-// S2: interpolate the 28 trace columns (winter-math interpolate_poly over <w_n>), extend them over the B
-// cosets of the LDE domain (coset r: the coefficients scaled by (3 w_N^r)^k) and commit to the rows.
-// A host-resident trace goes up on the upload stream in the column groups of the upload plan; each group's
-// event gates that group's interpolation and coset LDE on the compute stream.
-// Sparse trace columns (SparseCols): a column that is zero in every row but the last (the VM's stack registers past
-// the program's maximum depth, five of the benchmark's 28) interpolates to last * lagr and extends to last * lagr_lde;
-// sparse_detect flags them on the device and the NTT passes skip their DFTs.  Exact: the same polynomials and LDE.
-// ZK_SPARSE=0 transforms every column.
-bool zk::sparse_on() {
-    static const bool on = [] {
-        const char *e = getenv("ZK_SPARSE");
-        return !(e && !strcmp(e, "0"));
-    }();
-    return on;
-}
-
-// Narrow columns (host-resident traces): ZK_NARROW=0 uploads every column whole.
-bool zk::narrow_on() {
-    static const bool on = [] {
-        const char *e = getenv("ZK_NARROW");
-        return !(e && !strcmp(e, "0"));
-    }();
-    return on;
-}
-
-// The AIR clock (ZK_CLOCK=0 turns its derivation off)
-bool zk::clock_on() {
-    static const bool on = [] {
-        const char *e = getenv("ZK_CLOCK");
-        return !(e && !strcmp(e, "0"));
-    }();
-    return on;
-}
-
-int zk::plan_rank_tables(zk_prover *p, Plan *pl, int r0, int G) {
-    if (p->shard_world <= 1 || !pl->lagr) return ZK_OK;  // a full prover's tables hold every coset
-    const size_t n = (size_t)1 << pl->log_n, Bl = ((size_t)1 << pl->log_b) >> ilog2((size_t)G);
-    // the rank's block of cosets r0 .. r0 + Bl - 1 (shard.hip: rank g owns g Bl + j)
-    if (pl->lagr_lde && pl->lde_r0 == r0 && pl->lde_shift == 0 && pl->lde_cos == (int)Bl) return ZK_OK;
-    if (!pl->lagr_lde) ZK_CHECK_HIP(p->arena.alloc(&pl->lagr_lde, Bl * n));
-    ntt_lde(p->st, pl->Tn, pl->ct, pl->lagr, n, 1, r0, 1, (int)Bl, pl->lagr_lde, Bl * n, n, p->tmp);
-    if (pl->id_lde) ntt_lde(p->st, pl->Tn, pl->ct, pl->id_poly, n, 1, r0, 1, (int)Bl, pl->id_lde, Bl * n, n, p->tmp);
-    pl->lde_r0 = r0;
-    pl->lde_shift = 0;
-    pl->lde_cos = (int)Bl;
-    ZK_CHECK_HIP(hipStreamSynchronize(p->st));
-    return ZK_OK;
-}
-
-// the identity column 0, 1, ..., n-1 interpolated and extended over the cosets the plan's fill tables hold
-// (Plan::id_poly / id_lde, lde_r0 / lde_shift / lde_cos: all B for a full prover), once per plan
-int zk::clock_tables(zk_prover *p, Plan *pl) {
-    if (pl->id_poly) return ZK_OK;
-    if (!pl->lde_cos) ZK_FAIL(ZK_ERR_INVALID_ARG, "internal error: the plan's rank tables are not built");
-    const size_t n = (size_t)1 << pl->log_n, nc = (size_t)pl->lde_cos;
-    fe *poly = nullptr, *lde = nullptr;
-    ZK_CHECK_HIP(p->arena.alloc(&poly, n));
-    ZK_CHECK_HIP(p->arena.alloc(&lde, nc * n));
-    std::vector<fe> id(n);
-    for (size_t i = 0; i < n; i++) id[i] = fe_make(i);
-    fe *d = nullptr;
-    ZK_CHECK_HIP(hipMalloc(&d, n * sizeof(fe)));
-    hipError_t err = hipMemcpy(d, id.data(), n * sizeof(fe), hipMemcpyHostToDevice);
-    if (err == hipSuccess) {
-        const fe inv_n = h_inv(fe_make(n));
-        ntt(p->st, pl->Tn, d, n, poly, n, 1, true, nullptr, &inv_n, p->tmp);
-        ntt_lde(p->st, pl->Tn, pl->ct, poly, n, 1, pl->lde_r0, 1 << pl->lde_shift, (int)nc, lde, nc * n, n, p->tmp);
-        err = hipStreamSynchronize(p->st);
-    }
-    (void)hipFree(d);
-    ZK_CHECK_HIP(err);
-    pl->id_poly = poly;
-    pl->id_lde = lde;
-    return ZK_OK;
-}
-
-// rows [r0, r1) of a host column: row i holds i (the AIR clock)
-bool zk::clock_rows(const uint8_t *col, size_t r0, size_t r1) {
-    const uint64_t *v = reinterpret_cast<const uint64_t *>(col);
-    uint64_t bad = 0;
-    for (size_t i = r0; i < r1; i++) bad |= (v[2 * i] ^ (uint64_t)i) | v[2 * i + 1];
-    return bad == 0;
-}
-
-// rows [r0, r1) of a host column as `width`-byte integers (1 or 4) at dst + width * row; false if a value does not fit
-bool zk::pack_rows(const uint8_t *col, size_t r0, size_t r1, int width, uint8_t *dst) {
-    const uint64_t *v = reinterpret_cast<const uint64_t *>(col);
-    uint64_t over = 0;
-    if (width == 1) {
-        for (size_t i = r0; i < r1; i++) {
-            const uint64_t lo = v[2 * i], hi = v[2 * i + 1];
-            over |= (lo >> 8) | hi;
-            dst[i] = (uint8_t)lo;
-        }
-    } else {
-        uint32_t *d = reinterpret_cast<uint32_t *>(dst);
-        for (size_t i = r0; i < r1; i++) {
-            const uint64_t lo = v[2 * i], hi = v[2 * i + 1];
-            over |= (lo >> 32) | hi;
-            d[i] = (uint32_t)lo;
-        }
-    }
-    return over == 0;
-}
-
-// rows [r0, r1) of a host column all zero
-bool zk::zero_rows(const uint8_t *col, size_t r0, size_t r1) {
-    const uint64_t *v = reinterpret_cast<const uint64_t *>(col);
-    uint64_t any = 0;
-    for (size_t i = 2 * r0; i < 2 * r1; i++) any |= v[i];
-    return any == 0;
-}
-
-int zk::sparse_begin(zk_prover *p, Plan *pl, SparseCols *out, const SparseCols **sp) {
-    *sp = nullptr;
-    if (!sparse_on() || !pl->lagr || !pl->lagr_lde) return ZK_OK;
-    if (!p->sp_nz) {
-        ZK_CHECK_HIP(p->arena.alloc(&p->sp_nz, 4 * W));  // nonzero, 8-bit, 32-bit flags; [3W]: column 0 not the clock
-        ZK_CHECK_HIP(p->arena.alloc(&p->sp_last, W));
-        ZK_CHECK_HIP(hipHostMalloc((void **)&p->sp_h, 3 * W * sizeof(unsigned), hipHostMallocDefault));
-    }
-    ZK_CHECK_HIP(hipMemsetAsync(p->sp_nz, 0, 4 * W * sizeof(unsigned), p->st));
-    *out = SparseCols{p->sp_nz, p->sp_last, pl->lagr, pl->lagr_lde, 0};
-    out->lde_r0 = pl->lde_r0;
-    out->lde_shift = pl->lde_shift;
-    if (clock_on()) {  // the AIR clock of column 0, detected with the sparse columns (device-side traces)
-        ZK_TRY(clock_tables(p, pl));
-        out->id_poly = pl->id_poly;
-        out->id_lde = pl->id_lde;
-        out->idoff = 3 * W;
-    }
-    *sp = out;
-    return ZK_OK;
-}
-
-static int trace_lde_commit(zk_prover *p, Plan *pl, const TraceSrc &src, size_t n, uint8_t root[32]) {
-    const fe inv_n = h_inv(fe_make(n));
-    p->virt = 0;  // every LDE column is written unless the host path below takes some as virtual
-    SparseCols spc{};
-    const SparseCols *sp = nullptr;
-    if (!src.fixed) ZK_TRY(sparse_begin(p, pl, &spc, &sp));
-    p->sp_used = sp != nullptr;
-    if (src.dev && src.fixed) {
-        // zk_vm_prove: interpolate and extend the dynamic stack columns only; the preprocessed ones by one pass
-        const FixedCols &fx = *src.fixed;
-        const size_t B = (size_t)1 << pl->log_b, c0 = 12;
-        if (fx.md > 0) {
-            ntt(p->st, pl->Tn, src.dev + c0 * n, n, p->polys + c0 * n, n, fx.md, true, nullptr, &inv_n, p->tmp);
-            ntt_lde(p->st, pl->Tn, pl->ct, p->polys + c0 * n, n, fx.md, 0, 1, (int)B, p->lde + c0 * B * n, B * n, n,
-                    p->tmp);
-        }
-        const int pre = p->fix_prefix_blocks;  // (zk_vm_prove: the preprocessed part went first, fixed_prefix)
-        p->fix_prefix_blocks = 0;
-        if (pre) {
-            hash_rows_blocks(p->st, p->lde, W, pl->log_n, pl->log_b, pre, W / 4, p->leaves);
-        } else {
-            if (!p->fix_ws) ZK_CHECK_HIP(p->arena.alloc(&p->fix_ws, W));
-            fe_ws ws[W];
-            for (int c = 0; c < W; c++) ws[c] = make_fe_ws(fx.last[c]);
-            ZK_TRY(h2d_small(p, p->fix_ws, ws, sizeof ws));
-            fixed_axpy(p->st, fx, p->fix_ws, n, B, p->polys, p->lde);
-            hash_rows_cosets(p->st, p->lde, W, pl->log_n, pl->log_b, 0, pl->log_b, p->leaves);
-        }
-        merkle_tree(p->st, p->leaves, n * B, p->nodes);
-        return d2h_small(p, root, p->nodes + 32, 32);
-    }
-    if (src.dev) {
-        if (sp) sparse_detect(p->st, src.dev, n, 0, W, *sp);
-        ntt(p->st, pl->Tn, src.dev, n, p->polys, n, W, true, nullptr, &inv_n, p->tmp, sp);
-        const size_t B = (size_t)1 << pl->log_b;
-        ntt_lde(p->st, pl->Tn, pl->ct, p->polys, n, W, 0, 1, (int)B, p->lde, B * n, n, p->tmp, sp);
-        hash_rows_cosets(p->st, p->lde, W, pl->log_n, pl->log_b, 0, pl->log_b, p->leaves);
-        merkle_tree(p->st, p->leaves, n * B, p->nodes);
-        return d2h_small(p, root, p->nodes + 32, 32);
-    }
-    const int log_n = pl->log_n, log_b = pl->log_b;
-    const size_t B = (size_t)1 << log_b;
-    // The device trace buffer is free: the previous proof on this prover returned only after its stream drained
-    // (and the trace is read by the interpolation alone).
-    // hints of the previous proof of this length (hint_ok: prove_impl allows them): its sparse columns (zero but the
-    // last row: nothing goes up but that value), and its narrow ones (8- or 32-bit values before the last row), which
-    // go up packed.  Host threads check every hinted value while the other columns go up: a narrow column that does
-    // not fit goes up whole, a sparse one that is not sparse voids the proof (prove_impl redoes it without hints).
-    zk_prover::HintSet *H = sp && src.hint_ok ? hint_find(p, n, src.key) : nullptr;
-    const bool fresh = H && H->have;
-    const uint32_t hint = fresh ? H->sparse : 0u;
-    const uint32_t nw8 = fresh && narrow_on() ? H->nw8 & ~hint : 0u;
-    uint32_t nw32 = fresh && narrow_on() ? H->nw32 & ~hint & ~nw8 : 0u;
-    // The AIR clock: constraint 0 (clk' = clk + 1, air/src/constrains.rs) and the assertion clk[0] = 0 force rows
-    // 0 .. n-2 of column 0 of any trace the AIR accepts to 0 .. n-2, so its interpolant and LDE are the identity
-    // column's (per plan) plus (last - (n - 1)) times e_(n-1)'s: no upload, no transform.  Taken once the previous
-    // proof found column 0 narrow (32-bit), checked by host threads while the other columns go up; a column that is
-    // not 0 .. n-2 voids the proof, which is redone without hints (and this length is not speculated again).
-    const bool clk = fresh && clock_on() && (nw32 & 1u) && !H->clk_off;
-    if (clk) nw32 &= ~1u;
-    p->clk_used = clk;
-    p->clk_bad = false;
-    // Fixed columns (zk_prover::FixedSnap): with this hint set's snapshot, the columns it holds (but the ones hinted
-    // sparse, which keep their own path) are formed from it and checked by host threads; without one, this proof
-    // takes it once its LDE is written (below)
-    zk_prover::FixedSnap *FS = nullptr;
-    const bool fix_ok = fresh && fixed_on() && !H->fixed_off;
-    if (fix_ok && H->snap >= 0) {
-        zk_prover::FixedSnap &s = p->fix_snaps[H->snap];
-        if (s.live && s.n == n && s.B == B && s.lwe == src.lwe) FS = &s;
-        else fixed_drop(p, H->snap);  // taken for another blowup or lwe_size: taken again
-    }
-    const uint32_t fixm = FS ? FS->mask & ~hint : 0u;
-    const bool snap_now = fix_ok && !FS;
-    if (FS) FS->used = ++p->hint_stamp;
-    p->fix_used = fixm;
-    p->fix_bad = false;
-    p->fix_pending = -1;
-    const uint32_t virt = !src.no_virtual && virtual_on() ? hint & ~((1u << ZK_VIRT_MIN_COL) - 1u) : 0u;
-    p->virt = 0;  // (set once the hinted columns' last rows are on the device)
-    p->sp_hinted = hint;
-    p->up_bytes = 0;
-    p->up_sparse = hint;
-    // (a narrow column taken as fixed stays listed under its narrow class; none of its bytes cross the link)
-    p->up_nw8 = nw8 & fixm;
-    p->up_nw32 = nw32 & fixm;
-    int dense[W], nd = 0, hin[W], nh = 0, nar[W], nn = 0;
-    for (int c = 0; c < W; c++) {
-        if (clk && c == 0) continue;
-        if ((fixm >> c) & 1u) continue;
-        if ((hint >> c) & 1u) hin[nh++] = c;
-        else if (((nw8 | nw32) >> c) & 1u) nar[nn++] = c;
-        else dense[nd++] = c;
-    }
-    if (sp) spc.wstride = W;  // width flags for the next proof's narrow hint
-    bool ready[W] = {};
-    // contiguous runs of a column list: f(first column, count)
-    auto runs = [](const int *cols, int k, auto f) -> int {
-        for (int i = 0; i < k;) {
-            int j = i + 1;
-            while (j < k && cols[j] == cols[j - 1] + 1) j++;
-            ZK_TRY(f(cols[i], j - i));
-            i = j;
-        }
-        return ZK_OK;
-    };
-    // with the hints learned, the uploaded columns' flags come from the interpolation's pass 1 (no separate pass over
-    // them; a column found sparse there is transformed in full this time and hinted next time)
-    const bool fuse_det = fresh;
-    bool fused_tf = false, all_tf = false;
-    auto transform = [&](int c0, int nc) -> int {  // interpolation + coset LDE of columns [c0, c0 + nc)
-        SparseCols gsp = spc;
-        gsp.col0 = c0;
-        gsp.fused = fused_tf;
-        gsp.all = all_tf;
-        ntt(p->st, pl->Tn, p->d_trace + (size_t)c0 * n, n, p->polys + (size_t)c0 * n, n, nc, true, nullptr, &inv_n, p->tmp,
-            sp ? &gsp : nullptr);
-        ntt_lde(p->st, pl->Tn, pl->ct, p->polys + (size_t)c0 * n, n, nc, 0, 1, (int)B, p->lde + (size_t)c0 * B * n, B * n, n,
-                p->tmp, sp ? &gsp : nullptr);
-        return ZK_OK;
-    };
-    int hashed = 0;
-    auto hash_ready = [&](bool last) {  // the blocks whose 4 columns are extended, at least two per launch but the last
-        int b = hashed;
-        while (b < W / 4 && ready[4 * b] && ready[4 * b + 1] && ready[4 * b + 2] && ready[4 * b + 3]) b++;
-        if (b - hashed >= 2 || (last && b > hashed)) {
-            hash_rows_blocks(p->st, p->lde, W, log_n, log_b, hashed, b, p->leaves,
-                             VirtCols{p->virt, p->sp_last, pl->lagr_lde});
-            hashed = b;
-        }
-    };
-    // the kernels of an uploaded column list: detection (flags for the next proof's hints), transforms, hashing
-    auto process = [&](const int *cols, int nc) -> int {
-        if (sp && !fuse_det)
-            ZK_TRY(runs(cols, nc, [&](int c0, int k) { sparse_detect(p->st, p->d_trace, n, c0, k, spc); return ZK_OK; }));
-        fused_tf = sp && fuse_det;
-        const int rc = runs(cols, nc, transform);
-        fused_tf = false;
-        ZK_TRY(rc);
-        for (int i = 0; i < nc; i++) ready[cols[i]] = true;
-        hash_ready(false);
-        return ZK_OK;
-    };
-    // host checks of the hints: one pool task per quarter million rows of a hinted column, the narrow ones packing
-    // rows 0 .. n-2 (1 or 4 bytes each) into pinned h_pack as they go; the latch is waited for on every way out (the
-    // tasks read the caller's columns)
-    NarrowCols NC{};
-    size_t pack_bytes = 0;
-    for (int i = 0; i < nn; i++) {
-        NC.col[i] = nar[i];
-        NC.width[i] = ((nw8 >> nar[i]) & 1u) ? 1 : 4;
-        NC.off[i] = pack_bytes;
-        pack_bytes += ((size_t)NC.width[i] * n + 15) & ~(size_t)15;
-    }
-    NC.count = nn;
-    std::atomic<uint32_t> pack_bad{0}, sparse_bad{0}, clock_bad{0};
-    // Two upload schedules (set per proof by prove_once, see zk_prover::lat_sched):
-    //  - throughput (other proofs in flight on the device): the narrow columns go up in two parts (the first half of
-    //    them, the rest) through the copy engine, each as soon as its packing is done, in quarter-million-row tasks;
-    //  - latency (this proof alone on the device): dense groups 0 and 1 start crossing the link at once; the narrow
-    //    columns are packed in parts of 1, 2, 2, ... columns (64 K-row tasks, so each part is ready in ~0.1-0.2 ms)
-    //    and each part's expansion kernel reads the pinned packed bytes itself (no copy engine: that is busy with the
-    //    dense groups), so the first kernels start ~0.2 ms into the call and the device has the narrow columns' work
-    //    while the first dense groups cross.
-    const bool lat = p->lat_sched && nn > 0;
-    int pb[W + 1], np = 0;  // part k: narrow columns pb[k] .. pb[k+1]-1
-    pb[0] = 0;
-    if (lat) {
-        for (int i = 0; i < nn;) {
-            i = std::min(nn, i + (np == 0 ? 1 : 2));
-            pb[++np] = i;
-        }
-    } else if (nn) {
-        pb[1] = (nn + 1) / 2;
-        pb[2] = nn;
-        np = pb[1] < nn ? 2 : 1;
-    }
-    Latch packed[W], checked, clocked, compared, copied;
-    std::atomic<uint32_t> fixed_bad{0}, copy_bad{0};
-    struct PackWait {
-        Latch *parts;
-        const int &np;
-        Latch &b, &c, &d, &e;
-        ~PackWait() {
-            for (int k = 0; k < np; k++) parts[k].wait();
-            b.wait();
-            c.wait();
-            d.wait();
-            e.wait();
-        }
-    } pack_wait{packed, np, checked, clocked, compared, copied};
-    constexpr size_t R = (size_t)1 << 18;
-    const size_t per = (n - 1 + R - 1) / R;
-    const size_t Rp = lat ? (size_t)1 << 16 : R, perp = (n - 1 + Rp - 1) / Rp;  // packing task rows
-    if (nn) {
-        if (pack_bytes > p->h_pack_cap) {  // the previous proof's copies from it have drained (CopyGuard)
-            if (p->h_pack) (void)hipHostFree(p->h_pack);
-            p->h_pack = nullptr;
-            p->h_pack_cap = 0;
-            ZK_CHECK_HIP(hipHostMalloc((void **)&p->h_pack, pack_bytes, hipHostMallocMapped | hipHostMallocCoherent));
-            p->h_pack_cap = pack_bytes;
-        }
-        for (int k = 0; k < np; k++) packed[k].reset((int)(perp * (pb[k + 1] - pb[k])));
-        for (int i = 0, k = 0; i < nn; i++) {
-            if (i == pb[k + 1]) k++;  // part k holds narrow column i
-            for (size_t t = 0; t < perp; t++) {
-                const size_t r0 = t * Rp, r1 = std::min(n - 1, r0 + Rp);
-                const uint8_t *col = src.cols[nar[i]];
-                uint8_t *dst = p->h_pack + NC.off[i];
-                const int width = NC.width[i], c = nar[i];
-                const bool tail = r1 == n - 1;
-                Latch *lt = &packed[k];
-                HostPool::get().submit([=, &pack_bad] {
-                    if (!pack_rows(col, r0, r1, width, dst)) pack_bad.fetch_or(1u << c);
-                    if (tail) memset(dst + (size_t)width * (n - 1), 0, width);  // the last row's slot (not read)
-                    lt->count_down();
-                });
-            }
-        }
-    }
-    if (nh) {
-        checked.reset((int)(per * nh));
-        for (int i = 0; i < nh; i++)
-            for (size_t t = 0; t < per; t++) {
-                const size_t r0 = t * R, r1 = std::min(n - 1, r0 + R);
-                const uint8_t *col = src.cols[hin[i]];
-                const int c = hin[i];
-                HostPool::get().submit([=, &sparse_bad, &checked] {
-                    if (!zero_rows(col, r0, r1)) sparse_bad.fetch_or(1u << c);
-                    checked.count_down();
-                });
-            }
-        // hinted sparse columns: their coefficients and LDE are last * e_(n-1)'s (the NTT passes' sparse fill)
-        fe lastv[W];
-        memset(lastv, 0, sizeof lastv);
-        for (int i = 0; i < nh; i++) memcpy(&lastv[hin[i]], src.cols[hin[i]] + (n - 1) * sizeof(fe), sizeof(fe));
-        ZK_TRY(h2d_small(p, p->sp_last, lastv, sizeof lastv));
-        // no transform: the fills alone -- the coefficients of every hinted column, the LDE of the non-virtual ones
-        int hnv[W], nhv = 0;
-        for (int i = 0; i < nh; i++)
-            if (!((virt >> hin[i]) & 1u)) hnv[nhv++] = hin[i];
-        SparseCols gsp = spc;
-        gsp.fused = false;
-        gsp.all = true;
-        ZK_TRY(runs(hin, nh, [&](int c0, int nc) {
-            gsp.col0 = c0;
-            ntt(p->st, pl->Tn, p->d_trace + (size_t)c0 * n, n, p->polys + (size_t)c0 * n, n, nc, true, nullptr, &inv_n,
-                p->tmp, &gsp);
-            return ZK_OK;
-        }));
-        ZK_TRY(runs(hnv, nhv, [&](int c0, int nc) {
-            gsp.col0 = c0;
-            ntt_lde(p->st, pl->Tn, pl->ct, p->polys + (size_t)c0 * n, n, nc, 0, 1, (int)B, p->lde + (size_t)c0 * B * n,
-                    B * n, n, p->tmp, &gsp);
-            return ZK_OK;
-        }));
-        p->virt = virt;
-        memcpy(p->virt_last, lastv, sizeof lastv);
-        p->virt_lagr = pl->lagr_lde;
-        for (int i = 0; i < nh; i++) ready[hin[i]] = true;
-    }
-    // The fused prefix: with the fixed class in use, the leading blocks whose columns are each fixed, the derived clock,
-    // or hinted sparse with their LDE filled above get their formed columns' LDE inside their row hash (fixed_hash:
-    // blocks 0 .. 2 of the benchmark program); the coefficients keep their passes, and so does every such column past
-    // the prefix.  Empty without a snapshot in use or without the derived clock (column 0 is in block 0).
-    int fuse_nb = 0;
-    if (fixm && fixed_fuse_on()) {
-        auto pre = [&](int c) {
-            return (clk && c == 0) || ((fixm >> c) & 1u) || (((hint & ~virt) >> c) & 1u);
-        };
-        while (fuse_nb < W / 4 && pre(4 * fuse_nb) && pre(4 * fuse_nb + 1) && pre(4 * fuse_nb + 2) && pre(4 * fuse_nb + 3))
-            fuse_nb++;
-    }
-    fe_ws clk_d{};
-    if (clk) {
-        ZK_TRY(clock_tables(p, pl));
-        clocked.reset((int)per);
-        const uint8_t *col = src.cols[0];
-        for (size_t t = 0; t < per; t++) {
-            const size_t r0 = t * R, r1 = std::min(n - 1, r0 + R);
-            HostPool::get().submit([=, &clock_bad, &clocked] {
-                if (!clock_rows(col, r0, r1)) clock_bad.store(1u);
-                clocked.count_down();
-            });
-        }
-        fe last0;
-        memcpy(&last0, col + (n - 1) * sizeof(fe), sizeof(fe));
-        const fe_ws d = make_fe_ws(fe_sub(last0, fe_make(n - 1)));
-        clk_d = d;
-        axpy_fill(p->st, pl->id_poly, pl->lagr, d, n, p->polys);
-        if (!fuse_nb) axpy_fill(p->st, pl->id_lde, pl->lagr_lde, d, B * n, p->lde);
-        ready[0] = true;
-    }
-    if (fixm) {
-        // the fixed columns: the snapshot's f_c plus last[c] times e_(n-1)'s coefficients / LDE, in one pass each; only
-        // the last-row values go up.  Their BLAKE3 blocks (0 .. 2 when the clock is derived too) start at once.
-        if (!p->fix_ws) ZK_CHECK_HIP(p->arena.alloc(&p->fix_ws, W));
-        fe_ws ws[W];
-        memset(ws, 0, sizeof ws);
-        FixedColList L;
-        for (int c = 0; c < W; c++) {
-            if (!((fixm >> c) & 1u)) continue;
-            fe last;
-            memcpy(&last, src.cols[c] + (n - 1) * sizeof(fe), sizeof(fe));
-            ws[c] = make_fe_ws(last);
-            L.col[L.count] = (uint8_t)c;
-            L.slot[L.count] = FS->slot[c];
-            L.count++;
-        }
-        if (fuse_nb) ws[0] = clk_d;  // (column 0 is never in the fixed class: its W set slot carries the clock's d)
-        ZK_TRY(h2d_small(p, p->fix_ws, ws, sizeof ws));
-        fixed_cols_axpy(p->st, L, false, FS->fpolys, FS->flde, pl->lagr, pl->lagr_lde, p->fix_ws, n, B, p->polys, p->lde,
-                        4 * fuse_nb);
-        for (int k = 0; k < L.count; k++) ready[L.col[k]] = true;
-        if (fuse_nb) {
-            FixedHashCols A{};
-            for (int c = 0; c < 4 * fuse_nb; c++) {
-                A.wsi[c] = (uint8_t)c;
-                if (clk && c == 0) {
-                    A.mode[c] = FixedHashCols::FORM;
-                    A.src[c] = pl->id_lde;
-                } else if ((fixm >> c) & 1u) {
-                    A.mode[c] = FixedHashCols::FORM;
-                    A.src[c] = FS->flde + (size_t)FS->slot[c] * B * n;
-                } else {
-                    A.mode[c] = FixedHashCols::LOAD;  // hinted sparse: filled above
-                }
-            }
-            fixed_hash(p->st, A, pl->lagr_lde, p->fix_ws, p->lde, W, log_n, log_b, fuse_nb, p->leaves);
-            hashed = fuse_nb;
-        }
-        hash_ready(false);
-        // the host check: every row 0 .. n-2 of the caller's columns against the snapshot's host copy
-        compared.reset((int)(per * L.count));
-        for (int k = 0; k < L.count; k++)
-            for (size_t t = 0; t < per; t++) {
-                const size_t r0 = t * R, r1 = std::min(n - 1, r0 + R);
-                const int c = L.col[k], width = FS->width[c];
-                const uint8_t *col = src.cols[c], *snap = FS->host[c].get();
-                HostPool::get().submit([=, &fixed_bad, &compared] {
-                    if (!same_rows(col, snap, r0, r1, width)) fixed_bad.fetch_or(1u << c);
-                    compared.count_down();
-                });
-            }
-    }
-    // Upload items, each one copy (or a run of column copies) and an event on the shared upload stream: the wide
-    // columns in groups of 4, the last 4 as 2 + 2 (after the last copy only 2 columns' NTTs, the last hash blocks and
-    // the Merkle tree remain); the packed narrow columns first, in two parts (below); narrow columns that did not fit,
-    // whole, last.  The next item's copy is queued before the host waits for the current one's event
-    // (the compute stream never parks on the upload stream: a parked stream would hold up the kernels of other
-    // provers that share its hardware queue), so the copy engine always has the next group.
-    int gsz[W], ngroups = 0;
-    // (a first group of 1 or 2 columns, so the first kernels start after a shorter copy, measured slower: latency
-    // 13.90-13.95 vs 13.73-13.79 ms, throughput unchanged; profiles/r04h_ab_first_group.txt; round 5, 3 x 31 single
-    // calls: 14.75-14.78 / 14.67-14.70 vs 14.76-14.84 ms, profiles/r05d_latency_ab.txt)
-    int left = nd;
-    while (left > 0) {
-        const int k = left > 4 ? 4 : left > 2 ? 2 : left;
-        gsz[ngroups++] = left == 4 ? 2 : k;
-        left -= gsz[ngroups - 1];
-    }
-    if (ngroups + (lat ? 1 : np + 1) > ZK_UPLOAD_GROUPS_MAX) ZK_FAIL(ZK_ERR_INVALID_ARG, "too many upload groups");
-    struct Item {
-        const int *cols = nullptr;
-        int nc = 0;
-        int part = -1;  // narrow part (packed), or -1 (whole columns)
-        int ev = 0;
-    };
-    int fallback[W], nfb = 0, good[W], ev = 0, gi = 0, di = 0;
-    bool narrow_done[2] = {np < 1, np < 2}, fb_done = false;
-    NarrowCols G[W] = {};
-    size_t part_off[W + 1];  // byte range of each part in h_pack
-    for (int k = 0; k <= np; k++) part_off[k] = pb[k] < nn ? NC.off[pb[k]] : pack_bytes;
-    uint8_t *stage = reinterpret_cast<uint8_t *>(p->ctmp);  // composition scratch: free until S4
-    // part k's columns once packed (the host waits for its packing), its unpackable ones to the fallback list
-    auto narrow_item = [&](int k, Item *it) -> bool {
-        packed[k].wait();
-        if (k < 2) narrow_done[k] = true;
-        const uint32_t bad = pack_bad.load();
-        NarrowCols &g = G[k];
-        int *gd = good + pb[k], ng = 0;
-        for (int i = pb[k]; i < pb[k + 1]; i++) {
-            if ((bad >> nar[i]) & 1u) {  // a value that does not fit: this column goes up whole
-                fallback[nfb++] = nar[i];
-                continue;
-            }
-            g.col[g.count] = nar[i];
-            g.width[g.count] = NC.width[i];
-            g.off[g.count] = NC.off[i];
-            memcpy(&g.last[g.count], src.cols[nar[i]] + (n - 1) * sizeof(fe), sizeof(fe));
-            g.count++;
-            gd[ng++] = nar[i];
-        }
-        if (!ng) return false;
-        *it = Item{gd, ng, k, -1};
-        return true;
-    };
-    auto count_part = [&](int k) {  // part k's packed bytes cross the link
-        p->up_bytes += part_off[k + 1] - part_off[k];
-        const NarrowCols &g = G[k];
-        for (int i = 0; i < g.count; i++) (g.width[i] == 1 ? p->up_nw8 : p->up_nw32) |= 1u << g.col[i];
-    };
-    auto issue = [&](const Item &it) -> int {
-        std::lock_guard<std::mutex> lk(*p->up_mu);
-        // a copy that fails part-way through the item still gets the item's event behind the copies queued before
-        // it, so upload_drain (CopyGuard) waits for every DMA that reads the caller's columns
-        UploadEvent rec{p->ev_up[it.ev], p->up};
-        if (it.part >= 0) {
-            const size_t a = part_off[it.part];
-            ZK_CHECK_HIP(hipMemcpyAsync(stage + a, p->h_pack + a, part_off[it.part + 1] - a, hipMemcpyHostToDevice,
-                                        p->up));
-            count_part(it.part);
-        } else {
-            ZK_TRY(runs(it.cols, it.nc, [&](int c0, int k) { return upload_trace_group(p, src, n, c0, k); }));
-        }
-        return rec.record();
-    };
-    if (lat) {
-        // the latency schedule: dense groups 0 and 1 go up at once, group g + 2 once group g has landed; the narrow
-        // parts in order as they are packed, each expanded straight from the pinned buffer; then the dense groups
-        int gev[W];
-        auto issue_dense = [&]() -> int {
-            if (gi >= ngroups) return ZK_OK;
-            gev[gi] = ev++;
-            const Item d{dense + di, gsz[gi], -1, gev[gi]};
-            di += gsz[gi++];
-            return issue(d);
-        };
-        ZK_TRY(issue_dense());
-        ZK_TRY(issue_dense());
-        // (h_pack is pinned and mapped; part k's bytes are written by the pool threads before packed[k] opens and the
-        // expansion kernel is launched after that, and a kernel dispatch acquires at system scope, so the kernel
-        // reads this proof's bytes -- tests/test_gpu_parity.py changes a narrow column between proofs on this path)
-        uint8_t *hp = nullptr;
-        ZK_CHECK_HIP(hipHostGetDevicePointer((void **)&hp, p->h_pack, 0));
-        for (int k = 0; k < np; k++) {
-            Item it;
-            if (!narrow_item(k, &it)) continue;
-            count_part(k);
-            expand_narrow(p->st, hp, G[k], n, p->d_trace);
-            ZK_TRY(process(it.cols, it.nc));
-        }
-        for (int g = 0, d0 = 0; g < ngroups; d0 += gsz[g++]) {
-            ZK_CHECK_HIP(hipEventSynchronize(p->ev_up[gev[g]]));
-            ZK_TRY(issue_dense());
-            ZK_TRY(process(dense + d0, gsz[g]));
-        }
-        narrow_done[0] = narrow_done[1] = true;  // (the fallback columns, if any, go through the loop below)
-    }
-    // The throughput schedule: the first narrow part before anything else (packed by the host threads in ~0.3 ms, a
-    // few MB over PCIe: the first kernels start then instead of after a 64-MB dense group; one call alone -0.45 ms,
-    // 14.32-14.36 vs 14.76-14.84 ms over 3 x 31 calls, profiles/r05d_latency_ab.txt), the second as soon as it is
-    // packed, the dense groups in between.
-    auto next_item = [&](Item *it) -> bool {
-        if (!narrow_done[0] && narrow_item(0, it)) {
-            it->ev = ev++;
-            return true;
-        }
-        if (!narrow_done[1] && (packed[1].ready() || gi == ngroups) && narrow_item(1, it)) {
-            it->ev = ev++;
-            return true;
-        }
-        if (gi < ngroups) {
-            *it = Item{dense + di, gsz[gi], -1, ev++};
-            di += gsz[gi++];
-            return true;
-        }
-        if (narrow_done[0] && narrow_done[1] && nfb && !fb_done) {
-            fb_done = true;
-            *it = Item{fallback, nfb, -1, ev++};
-            return true;
-        }
-        return false;
-    };
-    Item cur;
-    bool have = next_item(&cur);
-    if (have) ZK_TRY(issue(cur));
-    while (have) {
-        Item nxt;
-        const bool more = next_item(&nxt);
-        if (more) ZK_TRY(issue(nxt));
-        ZK_CHECK_HIP(hipEventSynchronize(p->ev_up[cur.ev]));
-        if (cur.part >= 0) expand_narrow(p->st, stage, G[cur.part], n, p->d_trace);
-        ZK_TRY(process(cur.cols, cur.nc));
-        cur = nxt;
-        have = more;
-    }
-    hash_ready(true);
-    merkle_tree(p->st, p->leaves, n * B, p->nodes);
-    if (sp) ZK_TRY(d2h_small(p, p->sp_h, p->sp_nz, 3 * W * sizeof(unsigned)));  // for the next proof's hints
-    // The snapshot of the fixed class: f_c = column - last[c] e_(n-1), coefficients and LDE, from this proof's own polys
-    // and LDE, and rows 0 .. n-2 of the caller's columns for the later proofs' host check (narrow ones packed; one
-    // whose values do not fit its class is left out).  Memory that is not to be had turns the class off for this hint
-    // set; it never fails the proof.
-    const uint32_t cand = snap_now ? ZK_FIXED_CAND & ~hint : 0u;
-    if (cand) {
-        const int owner = (int)(H - p->hint_sets);
-        const int si = fixed_slot(p, owner, n, (uint32_t)B, __builtin_popcount(cand));
-        bool ok = si >= 0;
-        zk_prover::FixedSnap *s = ok ? &p->fix_snaps[si] : nullptr;
-        FixedColList L;
-        fe_ws ws[W];
-        memset(ws, 0, sizeof ws);
-        for (int c = 0; ok && c < W; c++) {
-            if (!((cand >> c) & 1u)) continue;
-            s->width[c] = ((H->nw8 >> c) & 1u) ? 1 : ((H->nw32 >> c) & 1u) ? 4 : 16;
-            s->host[c].reset(new (std::nothrow) uint8_t[(size_t)s->width[c] * n]);
-            if (!s->host[c]) ok = false;
-            s->slot[c] = (uint8_t)L.count;
-            L.col[L.count] = (uint8_t)c;
-            L.slot[L.count] = (uint8_t)L.count;
-            L.count++;
-            fe last;
-            memcpy(&last, src.cols[c] + (n - 1) * sizeof(fe), sizeof(fe));
-            ws[c] = make_fe_ws(fe_sub(fe_zero(), last));
-        }
-        if (ok && !p->fix_ws && p->arena.alloc(&p->fix_ws, W) != hipSuccess) {
-            (void)hipGetLastError();
-            ok = false;
-        }
-        if (ok) {
-            ZK_TRY(h2d_small(p, p->fix_ws, ws, sizeof ws));
-            fixed_cols_axpy(p->st, L, true, p->polys, p->lde, pl->lagr, pl->lagr_lde, p->fix_ws, n, B, s->fpolys, s->flde);
-            copied.reset((int)(per * L.count));
-            for (int k = 0; k < L.count; k++)
-                for (size_t t = 0; t < per; t++) {
-                    const size_t r0 = t * R, r1 = std::min(n - 1, r0 + R);
-                    const int c = L.col[k], width = s->width[c];
-                    const uint8_t *col = src.cols[c];
-                    uint8_t *dst = s->host[c].get();
-                    HostPool::get().submit([=, &copy_bad, &copied] {
-                        if (width == 16) memcpy(dst + 16 * r0, col + 16 * r0, 16 * (r1 - r0));
-                        else if (!pack_rows(col, r0, r1, width, dst)) copy_bad.fetch_or(1u << c);
-                        copied.count_down();
-                    });
-                }
-            copied.wait();
-            s->mask = cand & ~copy_bad.load();
-            s->lwe = src.lwe;
-            s->live = true;
-            s->used = ++p->hint_stamp;
-            p->fix_pending = si;
-        } else {
-            if (si >= 0) fixed_drop(p, si);
-            H->fixed_off = true;
-        }
-    }
-    checked.wait();
-    clocked.wait();
-    compared.wait();
-    p->sp_bad = sparse_bad.load();
-    p->clk_bad = clock_bad.load() != 0;
-    p->fix_bad = fixed_bad.load() != 0;
-    return d2h_small(p, root, p->nodes + 32, 32);
-}
-
 static void coset_major_rows_to_host(zk_prover *p, const fe *base, int ncols, size_t n, uint32_t B, uint8_t *dst) {
     // dst: N x ncols row-major (natural index)
     size_t N = n * B;
@@ -2171,90 +1323,25 @@ static int check_ood_identity(const std::vector<fe2> &e, int C, const AirConsts 
 static int prove_once(zk_prover *p, const TraceSrc &src, size_t n, const zk_options *opt, const zk_pub_inputs *pub,
                       uint8_t *proof_out, size_t *proof_len, zk_record *rec, const zk_dump *dump);
 
-// One proof, plus the hints' bookkeeping for host-resident traces: a hinted sparse column that the host check finds
-// nonzero voids the proof, which is redone without hints; a completed proof leaves the columns it found sparse and
-// narrow (8- or 32-bit before the last row) as the next proof's hints.
-static int prove_impl(zk_prover *p, const TraceSrc &src_in, size_t n, const zk_options *opt, const zk_pub_inputs *pub,
+// One proof, plus the hints' bookkeeping for host-resident traces (trace_commit.hip): a hinted column that the host
+// check refutes voids the proof, which is redone without hints; a completed proof leaves the columns it found sparse
+// and narrow (8- or 32-bit before the last row) as the next proof's hints.
+static int prove_impl(zk_prover *p, TraceSrc src, size_t n, const zk_options *opt, const zk_pub_inputs *pub,
                       uint8_t *proof_out, size_t *proof_len, zk_record *rec, const zk_dump *dump) {
-    TraceSrc src = src_in;
     if (dump) src.no_virtual = true;  // the stage dumps read every trace LDE column
     if (src.cols && pub) {
         src.key = &pub->program_hash[0][0];  // hints are per (n, program)
         src.lwe = pub->lwe_size;
     }
-    p->fix_used = 0;
-    p->fix_bad = false;
-    p->fix_pending = -1;
-    p->sp_used = false;
-    p->sp_hinted = 0;
-    p->sp_bad = 0;
-    p->clk_used = p->clk_bad = false;
+    p->tc = {};
     const size_t cap = proof_len ? *proof_len : 0;  // (in/out: a voided attempt has overwritten it with its length)
     int rc = prove_once(p, src, n, opt, pub, proof_out, proof_len, rec, dump);
-    // the snapshot this proof took serves the next ones only if the proof stands
-    const bool voided = p->sp_bad || p->clk_bad || p->fix_bad;
-    if (p->fix_pending >= 0) {
-        const int si = p->fix_pending;
-        p->fix_pending = -1;
-        if (rc == ZK_OK && !voided && src.cols && p->sp_used) p->hint_sets[p->fix_snaps[si].owner].snap = si;
-        else fixed_drop(p, si);
-    }
-    if (!src.cols || !p->sp_used) return rc;
-    // the classes the fixed columns were held under (they were not detected on the device this time)
-    uint32_t fix_cols = 0, fix_w8 = 0, fix_w32 = 0;
-    if (p->fix_used && !voided) {
-        const zk_prover::HintSet *h = hint_find(p, n, src.key);
-        fix_cols = p->fix_used;
-        if (h) fix_w8 = h->nw8 & fix_cols, fix_w32 = h->nw32 & fix_cols;
-    }
-    if (voided) {
-        // a hint of this (n, program) was refuted: forget its column classes (and stop speculating the clock or the
-        // fixed class for it if that was refuted) and its snapshot, prove again from every column
-        zk_prover::HintSet *h = hint_find(p, n, src.key);
-        if (h) {
-            if (p->clk_bad) h->clk_off = true;
-            if (p->fix_bad) h->fixed_off = true;
-            fixed_drop(p, h->snap);
-            h->have = false;
-            h->sparse = h->nw8 = h->nw32 = 0;
-        }
-        p->hint_redos++;
-        p->clk_used = p->clk_bad = false;
-        p->fix_used = 0;
-        p->fix_bad = false;
-        TraceSrc s2 = src;
-        s2.hint_ok = false;
-        p->sp_used = false;
-        p->sp_bad = 0;
+    if (trace_hints_refuted(p, src, n, rc)) {  // prove again from every column
+        src.hint_ok = false;
         *proof_len = cap;
-        rc = prove_once(p, s2, n, opt, pub, proof_out, proof_len, rec, dump);
-        if (!p->sp_used) return rc;
+        rc = prove_once(p, src, n, opt, pub, proof_out, proof_len, rec, dump);
     }
-    if (rc == ZK_OK || rc == ZK_ERR_DEGREE || rc == ZK_ERR_BUFFER_TOO_SMALL) {
-        // (the hinted sparse columns were not detected on the device: their flags stayed 0, and the host checked them)
-        uint32_t found = 0, w8 = 0, w32 = 0;
-        for (int c = 0; c < W; c++) {
-            if (p->sp_h[c] == 0) found |= 1u << c;
-            else if (p->sp_h[W + c] == 0) w8 |= 1u << c;
-            else if (p->sp_h[2 * W + c] == 0) w32 |= 1u << c;
-        }
-        if (p->clk_used) {  // (its flags were not detected on the device) the clock stays in the 32-bit class
-            found &= ~1u;
-            w8 &= ~1u;
-            w32 |= 1u;
-        }
-        found &= ~fix_cols;
-        w8 = (w8 & ~fix_cols) | fix_w8;
-        w32 = (w32 & ~fix_cols) | fix_w32;
-        if (src.key) {
-            zk_prover::HintSet *h = hint_slot(p, n, src.key);
-            h->have = true;
-            h->sparse = found;
-            h->nw8 = w8;
-            h->nw32 = w32;
-            h->used = ++p->hint_stamp;
-        }
-    }
+    trace_hints_learn(p, src, n, rc);
     return rc;
 }
 
@@ -2267,7 +1354,7 @@ static int prove_once(zk_prover *p, const TraceSrc &src, size_t n, const zk_opti
     // may free those columns as soon as this returns (a completed proof has long finished them).  Kernels of
     // a failed proof may also still be queued on st: the next proof's uploads into d_trace (on the upload stream,
     // ordered only by the previous proof having drained st) must not race them, so both drain here.
-    // proofs in flight on the device: alone, the trace goes up on the latency schedule (trace_lde_commit).  Declared
+    // proofs in flight on the device: alone, the trace goes up on the latency schedule (trace_commit.hip).  Declared
     // before the copy guard, so this proof counts as in flight until its uploads and kernels have drained.
     DeviceBusy busy{p->dev_busy};
     struct CopyGuard {
@@ -2491,7 +1578,7 @@ static int prove_once(zk_prover *p, const TraceSrc &src, size_t n, const zk_opti
     auto fe_at = [&](const fe *base, size_t idx) { addr[na++] = (uint64_t)(uintptr_t)(base + idx); };
     auto row_at = [&](const fe *base, int ncols, uint64_t i) {  // coset-major LDE row i
         for (int c = 0; c < ncols; c++) {
-            if (base == p->lde && ((p->virt >> c) & 1u)) fe_at(p->virt_lagr, (i & (B - 1)) * n + (i >> log_b));
+            if (base == p->lde && ((p->tc.virt >> c) & 1u)) fe_at(p->tc.virt_lagr, (i & (B - 1)) * n + (i >> log_b));
             else fe_at(base, ((size_t)c * B + (i & (B - 1))) * n + (i >> log_b));
         }
     };
@@ -2530,10 +1617,10 @@ static int prove_once(zk_prover *p, const TraceSrc &src, size_t n, const zk_opti
         const fe *got = p->h_gather_out;
         size_t off = 0;
         O.trace_rows.assign(got, got + nu * W);
-        if (p->virt)  // virtual columns: the gather read e_(n-1)'s LDE there; times the column's last row
+        if (p->tc.virt)  // virtual columns: the gather read e_(n-1)'s LDE there; times the column's last row
             for (size_t q = 0; q < nu; q++)
                 for (int c = 0; c < W; c++)
-                    if ((p->virt >> c) & 1u) O.trace_rows[q * W + c] = fe_mul(O.trace_rows[q * W + c], p->virt_last[c]);
+                    if ((p->tc.virt >> c) & 1u) O.trace_rows[q * W + c] = fe_mul(O.trace_rows[q * W + c], p->tc.virt_last[c]);
         off += nu * W;
         O.comp_rows.assign(got + off, got + off + nu * CK);
         off += nu * CK;
@@ -3024,6 +2111,39 @@ extern "C" void zk_diag_mul_limbs_host(const uint8_t *a, const uint8_t *b, uint8
     for (size_t i = 0; i < count; i++) fe_to_bytes(fe_mul_limbs(fe_from_bytes(a + 16 * i), fe_from_bytes(b + 16 * i)), out + 16 * i);
 }
 extern "C" void zk_diag_blake3_host(const uint8_t *in, size_t len, uint8_t out[32]) { b3::hash_bytes(in, len, out); }
+
+// Host: the upload plan of a host-trace commitment (upload_plan.hpp).  in[13] = have, sparse, nw8, nw32, clk_off,
+// fixed_off, snap, snap_mask, hint_ok, no_virtual, lat_sched, detect, switches (bit 0 ZK_SPARSE, 1 ZK_NARROW, 2 ZK_CLOCK,
+// 3 ZK_FIXED, 4 ZK_FIXED_FUSE, 5 ZK_VIRTUAL); n the trace length.  masks[8] = hint, nw8, nw32, clk, fixm, virt, snap_now,
+// lat; counts[7] = nd, nh, nhv, nn, np, ngroups, fuse_nb; cols[4 W] = dense, hin, hnv, nar (W each); width[W];
+// off[W + 1] (off[W] = pack_bytes); pb[W + 1]; gsz[W].  Returns the plan's status.
+extern "C" int zk_diag_upload_plan(const uint32_t *in, size_t n, uint32_t *masks, int32_t *counts, int32_t *cols,
+                                   int32_t *width, uint64_t *off, int32_t *pb, int32_t *gsz) {
+    UploadPlanIn q;
+    q.have = in[0], q.sparse = in[1], q.nw8 = in[2], q.nw32 = in[3], q.clk_off = in[4], q.fixed_off = in[5];
+    q.snap = in[6], q.snap_mask = in[7], q.hint_ok = in[8], q.no_virtual = in[9], q.lat_sched = in[10], q.detect = in[11];
+    q.sparse_on = in[12] & 1u, q.narrow_on = in[12] & 2u, q.clock_on = in[12] & 4u, q.fixed_on = in[12] & 8u;
+    q.fixed_fuse_on = in[12] & 16u, q.virtual_on = in[12] & 32u;
+    q.n = n;
+    const UploadPlan u = upload_plan(q);
+    const uint32_t m[8] = {u.hint, u.nw8, u.nw32, u.clk, u.fixm, u.virt, u.snap_now, u.lat};
+    const int32_t k[7] = {u.nd, u.nh, u.nhv, u.nn, u.np, u.ngroups, u.fuse_nb};
+    memcpy(masks, m, sizeof m);
+    memcpy(counts, k, sizeof k);
+    for (int i = 0; i < W; i++) {
+        cols[i] = i < u.nd ? u.dense[i] : -1;
+        cols[W + i] = i < u.nh ? u.hin[i] : -1;
+        cols[2 * W + i] = i < u.nhv ? u.hnv[i] : -1;
+        cols[3 * W + i] = i < u.nn ? u.nar[i] : -1;
+        width[i] = i < u.nn ? u.width[i] : 0;
+        off[i] = i < u.nn ? u.off[i] : 0;
+        gsz[i] = i < u.ngroups ? u.gsz[i] : 0;
+    }
+    off[W] = u.pack_bytes;
+    for (int i = 0; i <= W; i++) pb[i] = i <= u.np ? u.pb[i] : -1;
+    if (u.status != ZK_OK) ZK_FAIL(u.status, "too many upload groups");
+    return ZK_OK;
+}
 
 // GPU elementwise field op: 0 add, 1 sub, 2 mul, 3 inv(a), 4 a^b (b as a 128-bit exponent), 5 lazy add,
 // 6 canonical form of a, 7 multiply by b in two-part form, 8 .. 10 the butterflies' addsub2 forms.

@@ -1,7 +1,8 @@
 // prover_internal.hpp -- host-side state and protocol steps shared by the single-GPU prover
-// (prover.hip) and the coset-sharded multi-GPU prover (shard.hip).
+// (prover.hip, trace_commit.hip) and the coset-sharded multi-GPU prover (shard.hip).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <atomic>
@@ -14,6 +15,7 @@
 #include "../../include/zkvm_gpu.h"
 #include "air_shape.hpp"
 #include "host_field.hpp"
+#include "upload_plan.hpp"
 #include "zk_internal.hpp"
 
 namespace zk {
@@ -42,9 +44,6 @@ extern thread_local std::string g_err;
     } while (0)
 
 static constexpr int W = ZK_TRACE_WIDTH;
-// a host-resident trace is uploaded in up to this many column groups (trace_lde_commit; shard.hip: one per round
-// of its column split, ceil(W / G) rounds)
-static constexpr int ZK_UPLOAD_GROUPS_MAX = 14;
 static constexpr int NUM_TCONS = 20;
 static constexpr int NUM_ASSERTS = 22;
 
@@ -54,6 +53,24 @@ static constexpr int NUM_ASSERTS = 22;
         if ((p)->shard_world > 1)                                                                                 \
             ZK_FAIL(ZK_ERR_INVALID_ARG, "this prover was created for one rank of a sharded proof (zk_prover_create_shard)"); \
     } while (0)
+
+// a switch of the environment: on unless set to "0" (each read once per process, by a function-local static)
+inline bool env_switch(const char *name) {
+    const char *e = getenv(name);
+    return !(e && !strcmp(e, "0"));
+}
+
+// contiguous runs of an ascending column list: f(first column, count) -> status, until one is not ZK_OK
+template <class F>
+int for_runs(const int *cols, int k, F f) {
+    for (int i = 0; i < k;) {
+        int j = i + 1;
+        while (j < k && cols[j] == cols[j - 1] + 1) j++;
+        ZK_TRY(f(cols[i], j - i));
+        i = j;
+    }
+    return ZK_OK;
+}
 
 inline int ilog2(size_t n) {
     int r = 0;
@@ -122,7 +139,7 @@ struct zk_prover {
     int device = 0;
     hipStream_t st = nullptr;
     // upload stream: a host-resident trace goes up here in column groups, each group's event gating its
-    // interpolation and coset LDE on st (trace_lde_commit), so PCIe overlaps the group before it.  One stream per
+    // interpolation and coset LDE on st (trace_commit.hip), so PCIe overlaps the group before it.  One stream per
     // device shared by all its provers (shared_upload_stream: the link is one resource, and the process then needs
     // P + 1 hardware queues for P provers instead of 2P; A/B at HIP's default 4 queues: 12.44 vs 12.64 ms per proof
     // for a stream per prover, profiles/r04_ab_queues_pass1.txt).
@@ -130,7 +147,7 @@ struct zk_prover {
     hipStream_t up = nullptr;
     std::mutex *up_mu = nullptr;
     // proofs in flight on this device (process-wide, beside the upload stream), and whether this proof started alone:
-    // then trace_lde_commit takes the latency schedule (upload_sched: zk_prover_set_upload_schedule; AUTO: the
+    // then the trace commitment takes the latency schedule (upload_sched: zk_prover_set_upload_schedule; AUTO: the
     // latency schedule iff no other proof is in flight on the device)
     std::atomic<int> *dev_busy = nullptr;
     bool lat_sched = false;
@@ -214,7 +231,7 @@ struct zk_prover {
     };
     static constexpr int ZK_HINT_SETS = 8;
     HintSet hint_sets[ZK_HINT_SETS];
-    // Fixed columns (host-resident traces, trace_lde_commit): columns 1 .. 11 (opcode bits, hash flag, sponge, stack
+    // Fixed columns (host-resident traces, trace_commit.hip): columns 1 .. 11 (opcode bits, hash flag, sponge, stack
     // depth) depend on the program and lwe_size only, up to the random last row, so each is f_c + last[c] e_(n-1) with
     // f_c the same from proof to proof of one program.  The first proof of a hint set that runs with fresh hints (the
     // prover's second of that program) snapshots f_c's coefficients and LDE from its own polys / LDE into device
@@ -238,28 +255,30 @@ struct zk_prover {
     };
     static constexpr int ZK_FIXED_SNAPS = 2;
     FixedSnap fix_snaps[ZK_FIXED_SNAPS];
-    int fix_pending = -1;      // the snapshot this proof took: kept if the proof completes unrefuted (prove_impl)
-    uint32_t fix_used = 0;     // the columns the last proof took as fixed (zk_prover_upload_fixed)
-    bool fix_bad = false;      // ... and the host compare refuted them
     uint64_t hint_stamp = 0;
     uint32_t hint_redos = 0;  // proofs voided by a refuted hint and redone (zk_prover_proof_info)
-    uint32_t sp_hinted = 0, sp_bad = 0;
-    bool sp_used = false;  // the last trace_lde_commit ran the detection (its flags are in sp_h)
     unsigned *sp_h = nullptr;  // pinned: the detection's flags, [0, W) nonzero, [W, 2W) 8-bit, [2W, 3W) 32-bit
     uint8_t *h_pack = nullptr;
     size_t h_pack_cap = 0;
-    uint64_t up_bytes = 0;                        // zk_prover_upload_stats of the last host-column proof
-    uint32_t up_sparse = 0, up_nw8 = 0, up_nw32 = 0;
-    // Clock column (host-resident traces, trace_lde_commit): column 0 derived from the AIR's clock instead of
-    // uploaded and transformed (clk_used: the last proof did; clk_bad: the host check refuted it; HintSet::clk_off: a
-    // (length, program) whose traces refuted it, not speculated again)
-    bool clk_used = false, clk_bad = false;
-    // Virtual columns of the last host-trace commitment (trace_lde_commit): hinted sparse columns no constraint reads,
-    // whose LDE is never written -- the row hashing and the openings form their values from the last row and e_(n-1)'s
-    // LDE (virt_lagr) instead
-    uint32_t virt = 0;
-    fe virt_last[28] = {};
-    const fe *virt_lagr = nullptr;
+    // What the last proof's trace commitment did (trace_commit.hip): cleared when a proof starts and before it is
+    // redone without hints; the upload record and the virtual columns also by every commitment
+    struct TraceOutcome {
+        bool sp_used = false;  // the detection ran (its flags are in sp_h)
+        uint32_t sp_hinted = 0, sp_bad = 0;  // the columns taken as sparse; those the host check found were not
+        // column 0 derived from the AIR's clock instead of uploaded and transformed; the host check refuted it
+        // (HintSet::clk_off: a (length, program) whose traces refuted it, not speculated again)
+        bool clk_used = false, clk_bad = false;
+        uint32_t fix_used = 0;  // the columns taken as fixed (zk_prover_upload_fixed)
+        bool fix_bad = false;   // ... and the host compare refuted them
+        int fix_pending = -1;   // the snapshot this proof took: kept if the proof completes unrefuted
+        uint64_t up_bytes = 0;  // zk_prover_upload_stats
+        uint32_t up_sparse = 0, up_nw8 = 0, up_nw32 = 0;
+        // Virtual columns: hinted sparse columns no constraint reads, whose LDE is never written -- the row hashing
+        // and the openings form their values from the last row and e_(n-1)'s LDE (virt_lagr) instead
+        uint32_t virt = 0;
+        fe virt_last[28] = {};
+        const fe *virt_lagr = nullptr;
+    } tc;
     // Sharded host-trace hints (shard.hip S2): the sparse columns and the clock a previous sharded proof of this length
     // and world found (from all-gathered flags, so every rank holds the same), checked by the ranks' host threads
     uint32_t sh_sparse = 0, sh_nw8 = 0, sh_nw32 = 0;  // (and the narrow ones: the owner rank uploads them packed)
@@ -352,7 +371,7 @@ struct DeviceBusy {
     DeviceBusy &operator=(const DeviceBusy &) = delete;
 };
 
-// Upload gating (trace_lde_commit, shard.hip S2): the host thread waits for upload event ev before it enqueues the
+// Upload gating (trace_commit.hip, shard.hip S2): the host thread waits for upload event ev before it enqueues the
 // kernels that read the group (the next group's copy is already queued).  The compute stream never parks on a
 // cross-stream wait, which with fewer hardware queues than streams holds up the kernels of whatever stream shares its
 // queue (A/B at 4 queues, 4 provers: 11.77 vs 11.99 ms per proof for a device-side stream wait;
@@ -392,10 +411,29 @@ struct FixedCols {
     const fe *lagr_lde;      // B n, coset-major
     fe last[W];              // the last row
 };
-// zk_prove_device of p->d_trace (whose dynamic columns hold the trace) with the preprocessed columns of fx
+// Where the trace comes from: resident in HBM (zk_prove_device), or W host columns (zk_prove, zk_prove_columns,
+// zk_lde_new: the reference's TraceTable / ColMatrix, vm/src/lib.rs:18, 26).
+struct TraceSrc {
+    const fe *dev = nullptr;
+    const uint8_t *const *cols = nullptr;
+    const FixedCols *fixed = nullptr;  // with dev: only the dynamic columns are in dev (zk_vm_prove)
+    bool hint_ok = true;               // host columns: the sparse hint of the previous proof may be used
+    bool no_virtual = false;           // every trace LDE column written (stage dumps read them)
+    const uint8_t *key = nullptr;      // host columns: the program hash the hints are keyed by (with n)
+    uint32_t lwe = 0;                  // ... and its lwe_size (the fixed columns depend on it too)
+};
+// S2 (trace_commit.hip): the trace's polys, LDE and row commitment; the root is read back with the next d2h_flush
+int trace_lde_commit(zk_prover *p, Plan *pl, const TraceSrc &src, size_t n, uint8_t root[32]);
+// The hints' bookkeeping after a proof of host columns (status rc).  refuted: settles the snapshot the proof took; true
+// if a hint was refuted -- the set forgets its classes, p->tc is cleared and the caller proves again with hint_ok = false.
+// learn: a completed proof's findings become the next proof's hints.
+bool trace_hints_refuted(zk_prover *p, const TraceSrc &src, size_t n, int rc);
+void trace_hints_learn(zk_prover *p, const TraceSrc &src, size_t n, int rc);
+int ensure_pack(zk_prover *p, size_t bytes);  // pinned, mapped h_pack of at least `bytes` (the packed narrow columns)
 // Sparse trace columns (SparseCols) for this proof: allocates the flags on first use and clears them on p->st; *sp
 // stays null when ZK_SPARSE=0 or the plan is too small for the four-step NTT.
 int sparse_begin(zk_prover *p, Plan *pl, SparseCols *out, const SparseCols **sp);
+// zk_prove_device of p->d_trace (whose dynamic columns hold the trace) with the preprocessed columns of fx
 int prove_fixed(zk_prover *p, size_t n, const zk_options *opt, const zk_pub_inputs *pub, const FixedCols *fx,
                 uint8_t *proof_out, size_t *proof_len);
 // polys / lde of the preprocessed columns (all but 12 .. 12 + md - 1): f_c + last[c] e_(n-1) (vm_gpu.hip); B: the LDE
@@ -423,7 +461,7 @@ bool same_rows(const uint8_t *col, const uint8_t *snap, size_t r0, size_t r1, in
 // zk_vm_prove, before its host stack pass: fixed_axpy of fx into p->polys / p->lde and the BLAKE3 blocks of the rows'
 // first columns that hold no live stack register (0 .. 2: columns 0 .. 11), on p->st; sets p->fix_prefix_blocks
 int fixed_prefix(zk_prover *p, size_t n, uint32_t B, const FixedCols &fx);
-// Host-trace column classes shared by the single-GPU and the sharded prover (prover.hip): ZK_SPARSE / ZK_CLOCK
+// Host-trace column classes shared by the single-GPU and the sharded prover (trace_commit.hip): ZK_SPARSE / ZK_CLOCK
 // switches, the identity column's tables of a plan (the AIR clock: built once), and the host checks of a column's
 // rows [r0, r1): all zero, or row i holding i
 bool sparse_on();

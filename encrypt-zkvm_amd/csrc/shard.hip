@@ -640,10 +640,8 @@ int prove_sharded(Ctx &X, const uint8_t *trace, const zk_options *opt, const zk_
         // all-gathered: every rank forms their coefficients and local LDE from the last row (fills).  Each rank's host
         // threads check its 1/G row range of them; the flags are all-gathered with the hints of the next proof, and a
         // refuted hint voids the proof on every rank (prove_sharded_entry redoes it without hints).
-        static const bool hints_on = [] {  // ZK_SHARD_HINTS=0: every column uploaded, interpolated and all-gathered
-            const char *e = getenv("ZK_SHARD_HINTS");
-            return !(e && !strcmp(e, "0"));
-        }();
+        // ZK_SHARD_HINTS=0: every column uploaded, interpolated and all-gathered
+        static const bool hints_on = env_switch("ZK_SHARD_HINTS");
         // (keyed by length, world and program: column classes are a property of the program)
         const bool fresh = hints_on && X.hint_ok && sparse_on() && X.pl[0]->lagr && H->sh_hint_n == n && H->sh_hint_g == G &&
                            !memcmp(H->sh_hint_key, pub->program_hash, 32);
@@ -663,30 +661,17 @@ int prove_sharded(Ctx &X, const uint8_t *trace, const zk_options *opt, const zk_
             if (spp[l]) spc[l].wstride = W;
             if (clk) ZK_TRY(clock_tables(X.P[l], X.pl[l]));
         }
-        if (S | (clk ? 1u : 0u)) {
-            constexpr size_t R = (size_t)1 << 18;
-            std::vector<std::pair<int, size_t>> tasks;  // (local rank, first row)
-            for (int l = 0; l < nlp; l++) {
+        constexpr size_t R = (size_t)1 << 18;  // rows per host task
+        for (int c = 0; c < W; c++) {
+            const bool sparse = (S >> c) & 1u, clock = clk && c == 0;
+            if (!sparse && !clock) continue;
+            const uint8_t *cp = trace + (size_t)c * col;
+            for (int l = 0; l < nlp; l++) {  // the rank's row range
                 const size_t r0 = n * (size_t)X.rank[l] / (size_t)G, r1 = std::min(n - 1, n * (size_t)(X.rank[l] + 1) / G);
-                for (size_t t = r0; t < r1; t += R) tasks.push_back({l, t});
-            }
-            int nt = 0;
-            for (int c = 0; c < W; c++) nt += ((S >> c) & 1u) || (clk && c == 0) ? 1 : 0;
-            checked.reset(nt * (int)tasks.size());
-            for (int c = 0; c < W; c++) {
-                const bool sparse = (S >> c) & 1u, clock = clk && c == 0;
-                if (!sparse && !clock) continue;
-                const uint8_t *cp = trace + (size_t)c * col;
-                for (const auto &tk : tasks) {
-                    const int l = tk.first;
-                    const size_t t0 = tk.second;
-                    const size_t r1 = std::min(n - 1, std::min(n * (size_t)(X.rank[l] + 1) / G, t0 + R));
-                    std::atomic<uint32_t> *b = &bad[l];
-                    HostPool::get().submit([=, &checked] {
-                        if (!(clock ? clock_rows(cp, t0, r1) : zero_rows(cp, t0, r1))) b->fetch_or(1u << c);
-                        checked.count_down();
-                    });
-                }
+                std::atomic<uint32_t> *b = &bad[l];
+                row_tasks(checked, c, r0, r1, R, [=](int cc, size_t a, size_t e) {
+                    if (!(clock ? clock_rows(cp, a, e) : zero_rows(cp, a, e))) b->fetch_or(1u << cc);
+                });
             }
         }
         // narrow columns (8- or 32-bit before the last row): their owner's host threads pack rows 0 .. n-2 into its
@@ -706,36 +691,19 @@ int prove_sharded(Ctx &X, const uint8_t *trace, const zk_options *opt, const zk_
                 bytes += ((size_t)nc.width[nc.count] * n + 15) & ~(size_t)15;
                 nc.count++;
             }
-            zk_prover *p = X.P[l];
-            if (nc.count && bytes > p->h_pack_cap) {  // (the previous proof's copies from it have drained: CopyGuard)
-                if (p->h_pack) (void)hipHostFree(p->h_pack);
-                p->h_pack = nullptr;
-                p->h_pack_cap = 0;
-                ZK_CHECK_HIP(hipHostMalloc((void **)&p->h_pack, bytes, hipHostMallocMapped | hipHostMallocCoherent));
-                p->h_pack_cap = bytes;
+            ZK_TRY(ensure_pack(X.P[l], bytes));
+        }
+        for (int l = 0; l < nlp; l++)
+            for (int k = 0; k < nar[l].count; k++) {
+                const uint8_t *cp = trace + (size_t)nar[l].col[k] * col;
+                uint8_t *dst = X.P[l]->h_pack + nar[l].off[k];
+                const int width = nar[l].width[k];
+                std::atomic<uint32_t> *b = &pack_bad[l];
+                row_tasks(packed, nar[l].col[k], 0, n - 1, R, [=](int c, size_t r0, size_t r1) {
+                    if (!pack_rows(cp, r0, r1, width, dst)) b->fetch_or(1u << c);
+                    if (r1 == n - 1) memset(dst + (size_t)width * (n - 1), 0, width);  // (the last row's slot)
+                });
             }
-        }
-        {
-            constexpr size_t R = (size_t)1 << 18;
-            const size_t per = (n - 1 + R - 1) / R;
-            int total = 0;
-            for (int l = 0; l < nlp; l++) total += nar[l].count * (int)per;
-            packed.reset(total);
-            for (int l = 0; l < nlp; l++)
-                for (int k = 0; k < nar[l].count; k++)
-                    for (size_t t = 0; t < per; t++) {
-                        const size_t r0 = t * R, r1 = std::min(n - 1, r0 + R);
-                        const uint8_t *cp = trace + (size_t)nar[l].col[k] * col;
-                        uint8_t *dst = X.P[l]->h_pack + nar[l].off[k];
-                        const int width = nar[l].width[k], c = nar[l].col[k];
-                        std::atomic<uint32_t> *b = &pack_bad[l];
-                        HostPool::get().submit([=, &packed] {
-                            if (!pack_rows(cp, r0, r1, width, dst)) b->fetch_or(1u << c);
-                            if (r1 == n - 1) memset(dst + (size_t)width * (n - 1), 0, width);  // (the last row's slot)
-                            packed.count_down();
-                        });
-                    }
-        }
     } else if (X.fixed) {
         // vm::prove: the dynamic stack columns only (12 .. 12 + md - 1); the program-only columns and the zero registers
         // from the per-program preprocessed columns of this rank's cosets (one streaming pass, after the rounds)
@@ -907,16 +875,13 @@ int prove_sharded(Ctx &X, const uint8_t *trace, const zk_options *opt, const zk_
         for (int l = 0; l < nlp; l++) {
             zk_prover *p = X.P[l];
             ZK_CHECK_HIP(hipSetDevice(p->device));
-            for (int a = 0; a < nrep;) {
-                int b = a + 1;
-                while (b < nrep && U[b] == U[b - 1] + 1) b++;
-                const int c0 = U[a];
-                ntt(p->st, X.pl[l]->Tn, p->d_trace + (size_t)c0 * n, n, p->polys + (size_t)c0 * n, n, b - a, true, nullptr,
+            ZK_TRY(for_runs(U, nrep, [&](int c0, int k) {
+                ntt(p->st, X.pl[l]->Tn, p->d_trace + (size_t)c0 * n, n, p->polys + (size_t)c0 * n, n, k, true, nullptr,
                     &inv_n, p->tmp);
-                ntt_lde(p->st, X.pl[l]->Tn, X.pl[l]->ct, p->polys + (size_t)c0 * n, n, b - a, X.rank[l] * Bl, 1, Bl,
+                ntt_lde(p->st, X.pl[l]->Tn, X.pl[l]->ct, p->polys + (size_t)c0 * n, n, k, X.rank[l] * Bl, 1, Bl,
                         p->lde + (size_t)c0 * Bl * n, (size_t)Bl * n, n, p->tmp);
-                a = b;
-            }
+                return ZK_OK;
+            }));
         }
     }
     for (int k = 0; k < rounds; k++) {

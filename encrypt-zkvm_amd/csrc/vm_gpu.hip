@@ -199,7 +199,7 @@ __global__ void __launch_bounds__(256) k_vm_fixed(const Op *code, size_t len, co
 // the preprocessed columns (FixedCols): out[col][i] = F[src][i] (0 when src < 0) + w[wsi] base[i] for the ncol entries
 // listed, over `count` points of planes of `stride` (coefficients: n; LDE: B n).  Streaming, HBM-bound: per point the
 // Lagrange value once, then per entry one read (nonzero f_c) and one write.  Entries are arbitrary: zk_vm_prove reads
-// plane c of its 12 preprocessed columns into column c; the host-trace fixed class (prover.hip) reads compact snapshot
+// plane c of its 12 preprocessed columns into column c; the host-trace fixed class (trace_commit.hip) reads compact snapshot
 // slots into trace columns, and, to take a snapshot, trace columns into slots with w = -last (f_c = column - last e_(n-1)).
 // F, base and out never overlap.
 struct AxpyCols {
@@ -537,10 +537,9 @@ int zk_vm_prove(zk_prover *p, zk_program *prog, const uint8_t *public_in, size_t
     fe outs[NREG], last[28];
     read_last(last_row, last);
     // ZK_VM_PREPROCESS=0: every column from the device trace (no per-program preprocessed columns)
-    const char *pe = getenv("ZK_VM_PREPROCESS");
     // zk_prover_set_validate(p, 1): Trace::validate needs every column of the written trace in HBM, so the call takes
     // the all-columns path and zk_prove_device validates before it proves (the same proof bytes either way)
-    const bool pre = !(pe && !strcmp(pe, "0")) && opt->blowup <= p->max_b && opt->blowup >= 8 && !p->validate;
+    const bool pre = env_switch("ZK_VM_PREPROCESS") && opt->blowup <= p->max_b && opt->blowup >= 8 && !p->validate;
     size_t n = 0;
     zk_program::Fixed f{};
     uint32_t md = 0;
@@ -598,8 +597,7 @@ int zk_vm_prove_sharded(zk_comm *comm, zk_prover **provers, int nlocal, zk_progr
     size_t n = 0;
     const int G = comm->world;
     // ZK_VM_PREPROCESS=0: every column from the device trace, as zk_vm_prove
-    const char *pe = getenv("ZK_VM_PREPROCESS");
-    const bool pre = !(pe && !strcmp(pe, "0")) && opt->blowup == 8 && (G == 1 || G == 2 || G == 4 || G == 8);
+    const bool pre = env_switch("ZK_VM_PREPROCESS") && opt->blowup == 8 && (G == 1 || G == 2 || G == 4 || G == 8);
     std::vector<FixedCols> fx(pre ? nlocal : 0);
     // Processor::run + trace on every local rank, each into its own trace buffer (the loopback communicator drives
     // several ranks from one process; one RCCL process holds one); with the preprocessed columns (built once per

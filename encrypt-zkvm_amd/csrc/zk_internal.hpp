@@ -186,7 +186,7 @@ void commit_rows_coset_major(hipStream_t st, const fe *base, int ncols, int log_
                              uint8_t *nodes);
 // blocks b0 .. b1 - 1 of the leaf hashes of all B n rows of a coset-major column set of ncols (a multiple of 4,
 // <= 64) columns: columns 4 b .. 4 b + 3 compressed into the chaining value each leaf slot carries between launches
-// Virtual trace columns (host traces, prover.hip): sparse columns whose LDE is never written; the row hashing forms
+// Virtual trace columns (host traces, trace_commit.hip): sparse columns whose LDE is never written; the row hashing forms
 // column c's value at LDE point (coset r, position q) as last[c] * lagr_lde[r n + q]
 struct VirtCols {
     uint32_t mask = 0;
@@ -199,7 +199,7 @@ void hash_rows_blocks(hipStream_t st, const fe *base, int ncols, int log_n, int 
 //   FORM        lde column c = src[c] + ws_dev[wsi[c]] * lagr_lde  (src[c]: a coset-major plane of B n), stored and hashed
 //   FORM_NOSRC  lde column c = ws_dev[wsi[c]] * lagr_lde, stored and hashed
 //   LOAD        lde column c is already written: hashed only
-// (the fixed / preprocessed columns and the clock: prover.hip trace_lde_commit, fixed_prefix).  ncols as hash_rows_blocks.
+// (the fixed / preprocessed columns and the clock: trace_commit.hip, prover.hip fixed_prefix).  ncols as hash_rows_blocks.
 struct FixedHashCols {
     enum : uint8_t { FORM = 0, FORM_NOSRC = 1, LOAD = 2 };
     static constexpr int MAXC = 28;  // the trace width: 7 blocks

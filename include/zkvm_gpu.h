@@ -322,7 +322,8 @@ int zk_prover_exchange_stats_ex(zk_prover *p, const char **names, float *ms, flo
 int zk_prover_shard_schedule(zk_prover *p, char *buf, size_t cap, size_t *len);
 /* The host-to-device trace traffic of the last proof from host columns (zk_prove / zk_prove_columns): bytes copied,
  * the columns taken as sparse (zero but the last row: their last value only), and the columns uploaded packed as 8-
- * or 32-bit integers (narrow; each value checked on the host first).  Bit c = trace column c. */
+ * or 32-bit integers (narrow; each value checked on the host first).  Bit c = trace column c.  Every proof starts a
+ * new record, so after a proof of a device-resident trace (zk_prove_device, zk_vm_prove) all four read zero. */
 int zk_prover_upload_stats(zk_prover *p, uint64_t *bytes, uint32_t *sparse_cols, uint32_t *narrow8_cols,
                            uint32_t *narrow32_cols);
 /* the columns of the last host-column proof that were derived from the AIR instead of uploaded and transformed: bit 0,

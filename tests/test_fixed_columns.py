@@ -1,4 +1,4 @@
-"""Fixed columns of a host-resident trace (prover.hip zk_prover::FixedSnap).
+"""Fixed columns of a host-resident trace (trace_commit.hip, zk_prover::FixedSnap).
 
 Trace columns 1 .. 11 (opcode bits, hash flag, sponge, stack depth) depend on the program and lwe_size only, up to the
 random last row.  A prover's second proof of a (trace length, program) -- the first one that runs with learned hints --

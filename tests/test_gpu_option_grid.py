@@ -199,15 +199,17 @@ def test_option_changes_on_one_warm_prover(oracle):
     """One trace under changing options on one prover: every proof is the oracle's, no hint is refuted, and the fixed
     snapshot is retaken exactly after a change of blowup.
 
-    The expected upload_stats()["fixed"] sequence follows from prover.hip:
-      * hints are kept per (trace length, program hash) -- prove_impl sets src.key = pub->program_hash and
-        trace_lde_commit looks the set up with hint_find(p, n, src.key) -- so the options are not part of the key, and
-        a completed proof under any options leaves H->have set (prove_impl, hint_slot) for the next one;
+    The expected upload_stats()["fixed"] sequence follows from trace_commit.hip and upload_plan.hpp:
+      * hints are kept per (trace length, program hash) -- prove_impl (prover.hip) sets src.key = pub->program_hash
+        and HostTraceCommit::classify looks the set up with hint_find(p, n, src.key) -- so the options are not part of
+        the key, and a completed proof under any options leaves h->have set (trace_hints_learn, hint_slot) for the
+        next one;
       * the first proof has no hint set ("fresh" is false): nothing fixed, no snapshot.  The second is fresh with
-        H->snap < 0: FS stays null, fixm = FS ? FS->mask & ~hint : 0 is 0, snap_now = fix_ok && !FS takes the
-        snapshot after the LDE is written (fixed_slot(p, owner, n, B, ..) records the plan's B), and prove_impl hands
-        it to the hint set (hint_sets[owner].snap = si) because the proof stood.  The third finds FS: FIXED;
-      * trace_lde_commit accepts the set's snapshot only `if (s.live && s.n == n && s.B == B && s.lwe == src.lwe)`;
+        H->snap < 0: FS stays null, the plan's fixm = snap ? snap_mask & ~hint : 0 is 0, snap_now = fix_ok && !snap
+        takes the snapshot after the LDE is written (fixed_slot(p, owner, n, B, ..) records the plan's B), and
+        trace_hints_refuted hands it to the hint set (hint_sets[owner].snap = si) because the proof stood.  The third
+        finds FS: FIXED;
+      * classify accepts the set's snapshot only `if (s.live && s.n == n && s.B == B && s.lwe == src.lwe)`;
         otherwise `fixed_drop(p, H->snap)` forgets it, FS stays null, this proof forms nothing from it (fixed == [])
         and snap_now retakes it at the new B, so the proof after that is FIXED again.  B is the plan's blowup
         (1 << pl->log_b): only a change of blowup (or lwe_size) takes this branch.  The field extension and the FRI

@@ -1,4 +1,4 @@
-"""Column hints keyed by (trace length, program hash) (prover.hip hint_find / hint_slot).
+"""Column hints keyed by (trace length, program hash) (trace_commit.hip hint_find / hint_slot).
 
 A host-resident trace's column classes -- sparse (zero but the last row), narrow (8- / 32-bit before the last row),
 the AIR clock -- are learned from one proof and used by the next proof of the same length AND program, so a server

@@ -1,6 +1,6 @@
 """The off path of every column-hint kill switch, against the oracle's full-size pin.
 
-The single-GPU host path learns column classes from one proof and uses them for the next (prover.hip):
+The single-GPU host path learns column classes from one proof and uses them for the next (trace_commit.hip):
 sparse columns skip their NTTs (ZK_SPARSE), narrow columns go up packed (ZK_NARROW), the AIR clock is derived instead
 of uploaded (ZK_CLOCK), hinted sparse columns get no LDE in memory (ZK_VIRTUAL); the sharded host path has the same
 hints (ZK_SHARD_HINTS).  (Round 6 folded ZK_LATENCY_SCHED and ZK_VM_PREFIX into their measured defaults: the upload
