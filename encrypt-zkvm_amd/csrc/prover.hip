@@ -1994,6 +1994,14 @@ static int query_committed_rows(zk_prover *p, const fe *base, int ncols, size_t 
     std::vector<uint64_t> pos(positions, positions + k);
     for (uint64_t x : pos)
         if (x >= N) ZK_FAIL(ZK_ERR_INVALID_ARG, "query position out of range");
+    {
+        // MerkleTree::prove_batch refuses a repeated index (MerkleTreeError::DuplicateLeafIndex): the batch proof
+        // holds one path per distinct leaf pair, and a verifier rebuilds the root from distinct positions
+        std::vector<uint64_t> sorted(pos);
+        std::sort(sorted.begin(), sorted.end());
+        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+            ZK_FAIL(ZK_ERR_INVALID_ARG, "duplicate query position");
+    }
     ZK_CHECK_HIP(hipMemcpyAsync(p->gather_idx, pos.data(), k * 8, hipMemcpyHostToDevice, p->st));
     gather_rows(p->st, base, ncols, ilog2(n), ilog2(B), p->gather_idx, k, p->gather_out);
     ZK_CHECK_HIP(hipMemcpyAsync(rows_out, p->gather_out, k * ncols * 16, hipMemcpyDeviceToHost, p->st));
@@ -2270,5 +2278,113 @@ extern "C" int zk_diag_lde(int device, const uint8_t *in, size_t n, int ncols, u
     ntt_lde(p->st, pl->Tn, pl->ct, coeffs, n, ncols, r0, rstride, ncos, p->lde, (size_t)ncos * n, n, p->tmp);
     ZK_CHECK_HIP(hipStreamSynchronize(p->st));
     ZK_CHECK_HIP(hipMemcpy(out, p->lde, (size_t)ncols * ncos * n * 16, hipMemcpyDeviceToHost));
+    return ZK_OK;
+}
+
+// ---- the back half of a proof, each stage through its production launcher on inputs of the caller's choice
+// (tests/test_gpu_back_half.py; the reference is tests/back_half_ref.py).  Like zk_diag_lde: a prover of its own on
+// `device`, the inputs uploaded into its buffers, the launcher on its stream, the result read back.
+static bool diag_read_fe(const uint8_t *b, int ext, fe2 *out) {
+    out->a = fe_from_bytes(b);
+    out->b = ext == 2 ? fe_from_bytes(b + 16) : fe_zero();
+    return fe_canonical(out->a) && fe_canonical(out->b);
+}
+static int diag_back_half_args(const char *who, const void *tpolys, const void *cpolys, int ccols, size_t n, int ext,
+                               const uint8_t *z, const uint8_t *zg, const void *out, fe2 *zv, fe2 *zgv) {
+    const bool ok = tpolys && cpolys && z && zg && out && n >= 16 && !(n & (n - 1)) && n <= ((size_t)1 << 22) &&
+                    (ext == 1 ? ccols >= 1 && ccols <= 8 : ext == 2 && ccols >= 2 && ccols <= 16 && ccols % 2 == 0);
+    if (!ok || !diag_read_fe(z, ext, zv) || !diag_read_fe(zg, ext, zgv))
+        ZK_FAIL(ZK_ERR_INVALID_ARG, std::string(who) + ": n a power of two in [16, 2^22]; ext 1 with 1 .. 8 composition "
+                                    "columns or ext 2 with 2, 4 .. 16 base columns; z and zg canonical");
+    return ZK_OK;
+}
+static int diag_back_half_upload(zk_prover *p, const uint8_t *tpolys, const uint8_t *cpolys, int ccols, size_t n, int ext) {
+    if (ext == 2) ZK_TRY(ensure_ext(p));
+    ZK_CHECK_HIP(hipMemcpy(p->polys, tpolys, (size_t)W * n * 16, hipMemcpyHostToDevice));
+    ZK_CHECK_HIP(hipMemcpy(p->cpolys, cpolys, (size_t)ccols * n * 16, hipMemcpyHostToDevice));
+    return ZK_OK;
+}
+
+// The OOD frame of 28 trace polynomials and ccols composition polynomials (n coefficients each, column-major; over E,
+// ext = 2, ccols counts the base columns) at the points z and zg, given independently (16 bytes each, 32 over E):
+// ood_eval / ood_eval_ext with the (rank, G) share of the coefficient range.  out: (56 + ccols) elements
+// [T(z)]_28 ++ [T(zg)]_28 ++ [H(z)]_ccols; over E the a components of all, then the b components.
+extern "C" int zk_diag_ood(int device, const uint8_t *tpolys, const uint8_t *cpolys, int ccols, size_t n, int ext,
+                           const uint8_t *z, const uint8_t *zg, int rank, int G, uint8_t *out) {
+    fe2 zv, zgv;
+    ZK_TRY(diag_back_half_args("zk_diag_ood", tpolys, cpolys, ccols, n, ext, z, zg, out, &zv, &zgv));
+    if (G < 1 || G > 64 || rank < 0 || rank >= G) ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_ood: 0 <= rank < G <= 64");
+    zk_prover *p = nullptr;
+    ZK_TRY(zk_prover_create(device, n, 8, &p));
+    std::unique_ptr<zk_prover, void (*)(zk_prover *)> guard(p, zk_prover_destroy);
+    ZK_TRY(diag_back_half_upload(p, tpolys, cpolys, ccols, n, ext));
+    if (ext == 1) ood_eval(p->st, p->polys, W, p->cpolys, ccols, ilog2(n), zv.a, zgv.a, p->ood_tab, p->partials, p->ood, rank, G);
+    else ood_eval_ext(p->st, p->polys, W, p->cpolys, ccols, ilog2(n), zv, zgv, p->x_tab, p->x_partials, p->ood, rank, G);
+    ZK_CHECK_HIP(hipStreamSynchronize(p->st));
+    ZK_CHECK_HIP(hipMemcpy(out, p->ood, (size_t)ext * (2 * W + ccols) * 16, hipMemcpyDeviceToHost));
+    return ZK_OK;
+}
+
+// The DEEP polynomial's coefficients through deep_poly / deep_poly_ext: alpha_t (28) weigh the trace polynomials,
+// alpha_c the composition columns (ccols of them; over E ccols / 2 E columns H_j = P_2j + X P_2j+1, and every
+// coefficient and point is 32 bytes).  out: n coefficients; over E the a plane, then the b plane.  z = 0 or zg = 0 is
+// refused: the kernels scale by powers of their inverses.
+extern "C" int zk_diag_deep(int device, const uint8_t *tpolys, const uint8_t *cpolys, int ccols, size_t n, int ext,
+                            const uint8_t *z, const uint8_t *zg, const uint8_t *alpha_t, const uint8_t *alpha_c,
+                            uint8_t *out) {
+    fe2 zv, zgv;
+    ZK_TRY(diag_back_half_args("zk_diag_deep", tpolys, cpolys, ccols, n, ext, z, zg, out, &zv, &zgv));
+    if (!alpha_t || !alpha_c) ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_deep: null argument");
+    if ((fe_is_zero(zv.a) && fe_is_zero(zv.b)) || (fe_is_zero(zgv.a) && fe_is_zero(zgv.b)))
+        ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_deep: z and zg must be non-zero (their inverses are taken)");
+    const int C = ccols / ext;
+    DeepConsts D;
+    DeepConstsE DE;
+    memset(&D, 0, sizeof D);
+    memset(&DE, 0, sizeof DE);
+    for (int c = 0; c < W + C; c++) {
+        fe2 v;
+        if (!diag_read_fe((c < W ? alpha_t + 16 * ext * c : alpha_c + 16 * ext * (c - W)), ext, &v))
+            ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_deep: non-canonical coefficient");
+        (c < W ? D.alpha_t[c] : D.alpha_c[c - W]) = v.a;
+        (c < W ? DE.alpha_t[c] : DE.alpha_c[c - W]) = v;
+    }
+    D.z = zv.a, D.zg = zgv.a;
+    DE.z = zv, DE.zg = zgv, DE.zb2 = fe_mul(zv.b, zv.b), DE.zgb2 = fe_mul(zgv.b, zgv.b);
+    zk_prover *p = nullptr;
+    ZK_TRY(zk_prover_create(device, n, 8, &p));
+    std::unique_ptr<zk_prover, void (*)(zk_prover *)> guard(p, zk_prover_destroy);
+    ZK_TRY(diag_back_half_upload(p, tpolys, cpolys, ccols, n, ext));
+    const fe *Dk;
+    if (ext == 1) {
+        ZK_CHECK_HIP(hipMemcpy(p->deep_consts, &D, sizeof D, hipMemcpyHostToDevice));
+        Dk = deep_poly(p->st, p->polys, p->cpolys, C, ilog2(n), p->deep_consts, zv.a, zgv.a, p->dscratch);
+    } else {
+        ZK_CHECK_HIP(hipMemcpy(p->x_deep_consts, &DE, sizeof DE, hipMemcpyHostToDevice));
+        Dk = deep_poly_ext(p->st, p->polys, p->cpolys, C, ilog2(n), p->x_deep_consts, zv, zgv, p->x_dscratch);
+    }
+    ZK_CHECK_HIP(hipStreamSynchronize(p->st));
+    ZK_CHECK_HIP(hipMemcpy(out, Dk, (size_t)ext * n * 16, hipMemcpyDeviceToHost));
+    return ZK_OK;
+}
+
+// One grind_launch over the nonces [start, start + count) with the result preset to ~0: *best_out = the smallest
+// nonce whose BLAKE3(seed32 || nonce_le64) starts with >= bits trailing zero bits, ~0 when the window holds none.
+extern "C" int zk_diag_grind(int device, const uint8_t *seed32, uint64_t start, uint32_t count, int bits,
+                             uint64_t *best_out) {
+    if (!seed32 || !best_out || count == 0 || bits < 0 || bits > 64 || start > UINT64_MAX - count)
+        ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_grind: count >= 1, 0 <= bits <= 64, start + count below 2^64");
+    zk_prover *p = nullptr;
+    ZK_TRY(zk_prover_create(device, 16, 8, &p));
+    std::unique_ptr<zk_prover, void (*)(zk_prover *)> guard(p, zk_prover_destroy);
+    ZK_CHECK_HIP(p->arena.alloc(&p->pow_seed, 8));
+    ZK_CHECK_HIP(p->arena.alloc(&p->pow_best, 1));
+    unsigned long long best = ~0ULL;
+    ZK_CHECK_HIP(hipMemcpy(p->pow_seed, seed32, 32, hipMemcpyHostToDevice));
+    ZK_CHECK_HIP(hipMemcpy(p->pow_best, &best, 8, hipMemcpyHostToDevice));
+    grind_launch(p->st, p->pow_seed, start, count, bits, p->pow_best);
+    ZK_CHECK_HIP(hipStreamSynchronize(p->st));
+    ZK_CHECK_HIP(hipMemcpy(&best, p->pow_best, 8, hipMemcpyDeviceToHost));
+    *best_out = best;
     return ZK_OK;
 }

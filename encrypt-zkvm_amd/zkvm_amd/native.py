@@ -275,6 +275,13 @@ def lib():
         L.zk_diag_make_ws_host.restype = None
         # (device, in, n, ncols, blowup, r0, rstride, ncos, from_evals, out)
         L.zk_diag_lde.argtypes = [i32, vp, sz, i32, u32, i32, i32, i32, i32, vp]
+        if hasattr(L, "zk_diag_ood"):  # (an A/B library of an earlier commit has none of the three)
+            # (device, tpolys, cpolys, ccols, n, ext, z, zg, rank, G, out)
+            L.zk_diag_ood.argtypes = [i32, vp, vp, i32, sz, i32, vp, vp, i32, i32, vp]
+            # (device, tpolys, cpolys, ccols, n, ext, z, zg, alpha_t, alpha_c, out)
+            L.zk_diag_deep.argtypes = [i32, vp, vp, i32, sz, i32, vp, vp, vp, vp, vp]
+            # (device, seed32, start, count, bits, best_out)
+            L.zk_diag_grind.argtypes = [i32, vp, C.c_uint64, u32, i32, C.POINTER(C.c_uint64)]
         _lib = L
     return _lib
 

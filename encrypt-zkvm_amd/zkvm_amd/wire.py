@@ -109,9 +109,6 @@ def parse_proof(buf: bytes, off: int = 0) -> tuple[ProofView, int]:
     nq, blowup, grind, ext, fold, remdeg = r.u8(), r.u8(), r.u8(), r.u8(), r.u8(), r.u8()
     nu = r.u8()
     coms = r.take(r.u16())
-    for _ in range(r.u8()):  # trace segments: values + batch proof
-        r.take(r.u32())
-        r.take(r.u32())
     sections = {}
 
     def sect(name, width):
@@ -120,6 +117,9 @@ def parse_proof(buf: bytes, off: int = 0) -> tuple[ProofView, int]:
         r.take(ln)
         sections[name] = (at, width, ln)
 
+    for s in range(r.u8()):  # trace segments: values + batch proof (this AIR has the main segment only)
+        sect(f"trace_values_{s}" if s else "trace_values", 4)
+        sect(f"trace_proof_{s}" if s else "trace_proof", 4)
     sect("constraint_values", 4)
     sect("constraint_proof", 4)
     sect("ood_trace_states", 2)

@@ -234,7 +234,12 @@ int zk_lde_new(zk_prover *p, const uint8_t *trace, size_t width, size_t n, uint3
                uint8_t root[32]);
 /* TraceLde::read_main_trace_frame_into: rows lde_step and (lde_step + blowup) mod N */
 int zk_lde_read_frame(zk_trace_lde *lde, size_t lde_step, uint8_t *cur, uint8_t *next);
-/* TraceLde::query: rows at positions (width elements each) + batch Merkle proof bytes */
+/* TraceLde::query: rows at positions (width elements each, in the caller's order) + batch Merkle proof bytes
+ * (u8 number of paths, then per path u8 length and its 32-byte digests: BatchMerkleProof's serialization).  The
+ * positions (1 .. 255 of them, any order) must be distinct: a repeated one is ZK_ERR_INVALID_ARG, as
+ * MerkleTree::prove_batch refuses it (DuplicateLeafIndex).  proof_len: in, the capacity of proof_out; out, the
+ * proof's length -- also with ZK_ERR_BUFFER_TOO_SMALL, after which a call with that capacity succeeds.
+ * zk_comp_query takes the same. */
 int zk_lde_query(zk_trace_lde *lde, const uint64_t *positions, size_t k, uint8_t *rows_out, uint8_t *proof_out,
                  size_t *proof_len);
 void zk_lde_free(zk_trace_lde *lde);

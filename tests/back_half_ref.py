@@ -1,0 +1,282 @@
+"""Plain-integer reference of the back half of a proof, for tests/test_gpu_back_half.py (not a test module).
+
+Everything after the constraint commitment, restated over Python integers mod p = 2^128 - 45 2^40 + 1 and, over the
+quadratic extension E = F[X] / (X^2 - X - 1), over pairs (a, b) = a + b X:
+
+  * Horner evaluation of a polynomial with base coefficients at a base or an E point (the OOD frame);
+  * the DEEP quotient by synthetic division: A = sum alpha_i T_i, S = A + sum gamma_j H_j (over E the composition
+    column H_j = P_2j + X P_2j+1), D = (S - S(z)) / (x - z) + (A - A(zg)) / (x - zg), n coefficients with D_{n-1} = 0;
+  * the grinding search: BLAKE3(seed || nonce_le64), the trailing zero bits of its first little-endian u64, the
+    smallest hit of a window;
+  * BatchMerkleProof::get_root: the root rebuilt from opened rows, their positions and the serialized batch proof
+    (u8 number of paths, per path u8 length and 32-byte digests: what verifier.cpp parses and wire.py cuts out).
+
+The hash is the CPU oracle's BLAKE3 (oracle.blake3, pinned against the specification by tests/test_blake3_pin.py);
+tests/test_back_half_ref_cpu.py checks each part of this file against the oracle and the golden proofs.
+"""
+from operator import mul
+
+P = 2**128 - 45 * 2**40 + 1
+NO_NONCE = 2**64 - 1
+
+
+# ---------------------------------------------------------------- E = F[X] / (X^2 - X - 1)
+def e_add(x, y):
+    return ((x[0] + y[0]) % P, (x[1] + y[1]) % P)
+
+
+def e_sub(x, y):
+    return ((x[0] - y[0]) % P, (x[1] - y[1]) % P)
+
+
+def e_mul(x, y):
+    """(a + b X)(c + d X) = (a c + b d) + (a d + b c + b d) X"""
+    (a, b), (c, d) = x, y
+    bd = b * d
+    return ((a * c + bd) % P, (a * d + b * c + bd) % P)
+
+
+def e_inv(x):
+    """conjugate / norm: the conjugate of X is 1 - X, N(a + b X) = a^2 + a b - b^2"""
+    a, b = x
+    ni = pow((a * a + a * b - b * b) % P, P - 2, P)
+    return ((a + b) * ni % P, -b * ni % P)
+
+
+def e_pow(x, e):
+    r = (1, 0)
+    while e:
+        if e & 1:
+            r = e_mul(r, x)
+        x = e_mul(x, x)
+        e >>= 1
+    return r
+
+
+# ---------------------------------------------------------------- evaluation
+def horner(coeffs, x):
+    """sum_k coeffs[k] x^k for integers mod p"""
+    acc = 0
+    for c in reversed(coeffs):
+        acc = (acc * x + c) % P
+    return acc
+
+
+def horner_ext(coeffs, z):
+    """the same at an E point z = (a, b); coeffs are base elements or E pairs"""
+    acc = (0, 0)
+    for c in reversed(coeffs):
+        acc = e_mul(acc, z)
+        acc = e_add(acc, c) if isinstance(c, tuple) else ((acc[0] + c) % P, acc[1])
+    return acc
+
+
+def powers(x, n):
+    out = [1] * n
+    for k in range(1, n):
+        out[k] = out[k - 1] * x % P
+    return out
+
+
+def powers_ext(z, n):
+    out = [(1, 0)] * n
+    for k in range(1, n):
+        out[k] = e_mul(out[k - 1], z)
+    return out
+
+
+def eval_with_powers(coeffs, pw):
+    """Horner's value as the dot product with a power table (one reduction; many polynomials at one point)"""
+    return sum(map(mul, coeffs, pw)) % P
+
+
+def ood_frame(tpolys, cpolys, z, zg, ext):
+    """[T(z)] ++ [T(zg)] ++ [H(z)] for base-coefficient polynomials; over E (z, zg pairs) a list of pairs"""
+    n = len(tpolys[0])
+    if ext == 1:
+        pz, pg = powers(z, n), powers(zg, n)
+        return ([eval_with_powers(t, pz) for t in tpolys] + [eval_with_powers(t, pg) for t in tpolys] +
+                [eval_with_powers(c, pz) for c in cpolys])
+    pz, pg = powers_ext(z, n), powers_ext(zg, n)
+    za, zb = [v[0] for v in pz], [v[1] for v in pz]
+    ga, gb = [v[0] for v in pg], [v[1] for v in pg]
+    return ([(eval_with_powers(t, za), eval_with_powers(t, zb)) for t in tpolys] +
+            [(eval_with_powers(t, ga), eval_with_powers(t, gb)) for t in tpolys] +
+            [(eval_with_powers(c, za), eval_with_powers(c, zb)) for c in cpolys])
+
+
+# ---------------------------------------------------------------- DEEP
+def divide_out(f, c, ext):
+    """(F(x) - F(c)) / (x - c) by synthetic division: the n coefficients (the top one 0) and the remainder F(c)"""
+    n = len(f)
+    if ext == 1:
+        q = [0] * n
+        acc = 0
+        for k in range(n - 1, 0, -1):
+            acc = (acc * c + f[k]) % P
+            q[k - 1] = acc
+        return q, (acc * c + f[0]) % P
+    q = [(0, 0)] * n
+    acc = (0, 0)
+    for k in range(n - 1, 0, -1):
+        acc = e_add(e_mul(acc, c), f[k])
+        q[k - 1] = acc
+    return q, e_add(e_mul(acc, c), f[0])
+
+
+def deep_combine(tpolys, cpolys, alpha_t, alpha_c, ext):
+    """the coefficients of A = sum alpha_i T_i and S = A + sum gamma_j H_j (over E: lists of pairs, and
+    H_j = P_2j + X P_2j+1 of the base columns cpolys)"""
+    if ext == 1:
+        A = [sum(map(mul, alpha_t, col)) % P for col in zip(*tpolys)]
+        S = [(a + sum(map(mul, alpha_c, col))) % P for a, col in zip(A, zip(*cpolys))]
+        return A, S
+    aa, ab = [v[0] for v in alpha_t], [v[1] for v in alpha_t]
+    A = [(sum(map(mul, aa, col)) % P, sum(map(mul, ab, col)) % P) for col in zip(*tpolys)]
+    # gamma (p0 + p1 X) with gamma = (c, d): (c p0 + d p1) + (d p0 + (c + d) p1) X, so each component of S is a
+    # dot product of a row of base coefficients (test_back_half_ref_cpu checks this against e_mul term by term)
+    ga = [g[t] for g in alpha_c for t in (0, 1)]
+    gb = [v for g in alpha_c for v in (g[1], g[0] + g[1])]
+    S = [((a[0] + sum(map(mul, ga, col))) % P, (a[1] + sum(map(mul, gb, col))) % P)
+         for a, col in zip(A, zip(*cpolys))]
+    return A, S
+
+
+def deep_quotient(tpolys, cpolys, z, zg, alpha_t, alpha_c, ext):
+    """D = (S - S(z)) / (x - z) + (A - A(zg)) / (x - zg): n coefficients (ints; over E pairs)"""
+    A, S = deep_combine(tpolys, cpolys, alpha_t, alpha_c, ext)
+    q1, _ = divide_out(S, z, ext)
+    q2, _ = divide_out(A, zg, ext)
+    if ext == 1:
+        return [(x + y) % P for x, y in zip(q1, q2)]
+    return [e_add(x, y) for x, y in zip(q1, q2)]
+
+
+# ---------------------------------------------------------------- grinding
+def nonce_zeros(blake3, seed, nonce):
+    """trailing zero bits of the first little-endian u64 of BLAKE3(seed || nonce_le64) (64 for a zero word)"""
+    head = int.from_bytes(blake3(seed + nonce.to_bytes(8, "little"))[:8], "little")
+    return (head & -head).bit_length() - 1 if head else 64
+
+
+def grind_hits(blake3, seed, start, count, bits):
+    """every nonce of [start, start + count) that passes, ascending"""
+    return [v for v in range(start, start + count) if nonce_zeros(blake3, seed, v) >= bits]
+
+
+def grind(blake3, seed, start, count, bits):
+    """the smallest passing nonce of the window, NO_NONCE (~0) when it has none"""
+    for v in range(start, start + count):
+        if nonce_zeros(blake3, seed, v) >= bits:
+            return v
+    return NO_NONCE
+
+
+def zeros_table(blake3, seed, start, count):
+    """nonce_zeros of every nonce of the window, hashed once for searches that share it"""
+    return [nonce_zeros(blake3, seed, v) for v in range(start, start + count)]
+
+
+def grind_in_table(table, start, count, bits):
+    """grind() over the first `count` nonces of a window whose zeros_table is `table`"""
+    for t in range(count):
+        if table[t] >= bits:
+            return start + t
+    return NO_NONCE
+
+
+def proof_query_seed(blake3, view, program_hash, stack_outputs):
+    """The coin seed a proof ground its nonce on, replayed from the proof itself (view: wire.parse_proof's): the seed
+    of the context and public-input elements, merged in turn with the trace root, the constraint root, the digests of
+    the OOD trace frame and of the OOD constraint values, the FRI layer roots and the remainder commitment (drawing
+    from the coin leaves its seed alone).  The proof's nonce must be the first of 1, 2, ... that passes on it."""
+    def el(v):
+        return int(v).to_bytes(16, "little")
+
+    def body(name):
+        at, width, ln = view.sections[name]
+        return view.raw[at + width:at + width + ln]
+
+    k = view.field_extension
+    ctx = [view.trace_width << 16, view.trace_len, P % 2**64, P >> 64,
+           (k << 16) | (view.fri_folding << 8) | view.fri_rem_max_deg, view.grinding, view.blowup, view.num_queries]
+    seed = blake3(b"".join(map(el, ctx + list(program_hash)[:2] + list(stack_outputs)[:16])))
+    coms = [view.commitments[i:i + 32] for i in range(0, len(view.commitments), 32)]
+    states = body("ood_trace_states")[1:]  # after the frame-count byte: per column T_c(z) then T_c(zg)
+    es = 16 * k
+    tz = b"".join(states[2 * es * c:2 * es * c + es] for c in range(view.trace_width))
+    tzg = b"".join(states[2 * es * c + es:2 * es * c + 2 * es] for c in range(view.trace_width))
+    for d in coms[:2] + [blake3(tz + tzg), blake3(body("ood_evaluations"))] + coms[2:]:
+        seed = blake3(seed + d)
+    return seed
+
+
+# ---------------------------------------------------------------- batch Merkle openings
+def parse_batch_proof(proof):
+    """the per-path digest lists of a serialized BatchMerkleProof; ValueError unless the bytes are exactly that"""
+    if not proof:
+        raise ValueError("empty batch proof")
+    paths, o = [], 1
+    for _ in range(proof[0]):
+        if o >= len(proof):
+            raise ValueError("truncated batch proof")
+        k = proof[o]
+        o += 1
+        if o + 32 * k > len(proof):
+            raise ValueError("truncated path")
+        paths.append([proof[o + 32 * t:o + 32 * t + 32] for t in range(k)])
+        o += 32 * k
+    if o != len(proof):
+        raise ValueError("trailing bytes after the batch proof")
+    return paths
+
+
+def batch_root(blake3, leaves, positions, proof, depth):
+    """BatchMerkleProof::get_root: leaves[t] is the digest of the leaf at positions[t] (distinct positions, any
+    order) of a tree of 2^depth leaves; returns the root the proof bytes rebuild, ValueError when they cannot"""
+    if len(set(positions)) != len(positions) or len(leaves) != len(positions):
+        raise ValueError("positions must be distinct, one leaf each")
+    if any(not 0 <= i < 1 << depth for i in positions):
+        raise ValueError("position out of range")
+    at = dict(zip(positions, leaves))
+    norm = sorted({i & ~1 for i in positions})
+    paths = [list(p) for p in parse_batch_proof(proof)]
+    if len(paths) != len(norm):
+        raise ValueError("wrong number of paths")
+
+    def take(i):
+        if not paths[i]:
+            raise ValueError("path too short")
+        return paths[i].pop(0)
+
+    nodes, nxt = {}, []
+    for i, l in enumerate(norm):
+        left = at[l] if l in at else take(i)
+        right = at[l + 1] if l + 1 in at else take(i)
+        k = ((1 << depth) + l) >> 1
+        nodes[k] = blake3(left + right)
+        nxt.append(k)
+    for _ in range(1, depth):
+        cur, nxt, i = nxt, [], 0
+        while i < len(cur):
+            node, sib = cur[i], cur[i] ^ 1
+            if i + 1 < len(cur) and cur[i + 1] == sib:
+                sd = nodes[sib]
+                i += 1
+            else:
+                # the digest comes from the path at the node's index in this level's list, as MerkleTree::prove_batch
+                # files it (the list shrinks as siblings merge, the path vectors do not move)
+                sd = take(i)
+            nodes[node >> 1] = blake3(sd + nodes[node]) if node & 1 else blake3(nodes[node] + sd)
+            nxt.append(node >> 1)
+            i += 1
+    if any(paths):
+        raise ValueError("unused digests in the batch proof")
+    return nodes[1] if depth > 0 else None
+
+
+def row_digest(blake3, row):
+    """the leaf of an opened row: BLAKE3 over its elements' 16-byte encodings (row: ints or the bytes themselves)"""
+    if isinstance(row, (bytes, bytearray)):
+        return blake3(bytes(row))
+    return blake3(b"".join(int(v).to_bytes(16, "little") for v in row))

@@ -11,6 +11,7 @@ import random
 import numpy as np
 import pytest
 
+import back_half_ref
 from zkvm_amd import native
 from zkvm_amd.prover import (GpuProver, ProofOptions, bytes_elems, elems_bytes, make_pub_inputs, vm_trace)
 from zkvm_amd.workloads import LR_PROGRAM, cipher_mix_program, make_workload, push_add_program, ops_for_trace_len
@@ -333,6 +334,10 @@ def test_plug_points(gpu, oracle):
     pbuf = C.create_string_buffer(1 << 16)
     native.check(L.zk_lde_query(h, pos, 3, rows, pbuf, C.byref(plen)))
     assert rows.raw == b"".join(lde[p].tobytes() for p in (1, 17, 900))
+    # the batch proof and the rows rebuild the committed root
+    leaves = [back_half_ref.row_digest(oracle.blake3, rows.raw[448 * q:448 * q + 448]) for q in range(3)]
+    assert back_half_ref.batch_root(oracle.blake3, leaves, [1, 17, 900], pbuf.raw[:plen.value],
+                                    (8 * n).bit_length() - 1) == root.raw
     out = C.create_string_buffer(16 * 8 * n)
     native.check(L.zk_eval_constraints(h, C.byref(pub), bytes(orec.coeff_t), bytes(orec.coeff_b), out))
     assert out.raw == od["composition"].tobytes()
@@ -364,6 +369,10 @@ def test_plug_point_constraint_commitment(gpu, oracle):
     native.check(L.zk_comp_query(cc, pos, 4, rows, pbuf, C.byref(plen)))
     assert rows.raw == b"".join(clde[p].tobytes() for p in (0, 3, 8 * n - 1, 77))
     assert 0 < plen.value < (1 << 16)
+    rb = 16 * ncols
+    leaves = [back_half_ref.row_digest(oracle.blake3, rows.raw[rb * q:rb * q + rb]) for q in range(4)]
+    assert back_half_ref.batch_root(oracle.blake3, leaves, [0, 3, 8 * n - 1, 77], pbuf.raw[:plen.value],
+                                    (8 * n).bit_length() - 1) == root.raw
     L.zk_comp_free(cc)
     # a composition of too high a degree is refused: more columns' worth of coefficients than num_cols
     rc = L.zk_commit_composition(h, comp.ctypes.data, ncols - 1, C.byref(cc), root, None)
