@@ -1345,6 +1345,89 @@ static int prove_impl(zk_prover *p, TraceSrc src, size_t n, const zk_options *op
     return rc;
 }
 
+zk_record zk::record_init(size_t n, size_t N, int C) {
+    zk_record R;
+    memset(&R, 0, sizeof R);
+    R.trace_len = (uint32_t)n;
+    R.lde_len = (uint32_t)N;
+    R.width = W;
+    R.num_ccols = (uint32_t)C;
+    return R;
+}
+
+int zk::fri_lead_layers(zk_prover *p, const Plan *pl, int KX, uint32_t fold, uint32_t B, size_t N, int l0, int lb0,
+                        fe *next, uint8_t *dig, FriLayers &Y, Coin &coin, zk_record &R, unsigned &degree_flag,
+                        HostTimer *ht) {
+    const int nl = (int)R.num_fri_layers;
+    // the constant part of the fold constants is uploaded once; each layer's coin writes alpha into it
+    void *fc = planes(p, KX).fold_consts;
+    fe *alpha_dev = nullptr;
+    if (KX == 1) {
+        const FoldConsts F = fold_consts(fe_zero(), fold);
+        ZK_TRY(h2d_small(p, fc, &F, sizeof F));
+        alpha_dev = &((FoldConsts *)fc)->alpha;
+    } else {
+        const FoldConstsE F = fold_consts_ext(fe2_zero(), fold);
+        ZK_TRY(h2d_small(p, fc, &F, sizeof F));
+        alpha_dev = &((FoldConstsE *)fc)->alpha.a;
+    }
+    ZK_TRY(h2d_small(p, p->fri_seed, coin.seed, 32));  // (the next reseed restarts the counter)
+    for (int l = l0; l < nl; l++) {
+        const size_t L = Y.len[l], rows = L / fold;
+        Y.leaves[l] = dig;
+        Y.nodes[l] = dig + 32 * rows;
+        dig += 64 * rows;
+        const int lb = l == l0 ? lb0 : 0;
+        if (KX == 1) commit_fri_layer(p->st, Y.vals[l], L, (int)fold, Y.leaves[l], Y.nodes[l], lb);
+        else commit_fri_layer_ext(p->st, Y.vals[l], L, (int)fold, Y.leaves[l], Y.nodes[l], lb);
+        fri_coin_launch(p->st, (uint32_t *)p->fri_seed, Y.nodes[l] + 32, KX, alpha_dev, p->fri_alphas + 2 * l);
+        if (KX == 1) fri_fold_launch(p->st, Y.vals[l], L, (int)fold, fc, pl->TN, N / L, next, lb);
+        else fri_fold_ext_launch(p->st, Y.vals[l], L, (int)fold, fc, pl->TN, N / L, next, lb);
+        Y.vals[l + 1] = next;
+        Y.len[l + 1] = rows;
+        next += KX * rows;
+    }
+    // one round trip for the whole commit phase: roots, device alphas, the last layer
+    std::vector<fe> rv(KX * Y.len[nl]), dalpha(2 * nl);
+    for (int l = l0; l < nl; l++) ZK_TRY(d2h_small(p, R.fri_roots[l], Y.nodes[l] + 32, 32));
+    if (nl > l0) ZK_TRY(d2h_small(p, dalpha.data() + 2 * l0, p->fri_alphas + 2 * l0, 2 * (nl - l0) * sizeof(fe)));
+    ZK_TRY(d2h_small(p, rv.data(), Y.vals[nl], rv.size() * sizeof(fe)));
+    ZK_TRY(d2h_flush(p));
+    if (ht) ht->start();
+    // host replay of the same transcript (it continues into the remainder, grinding and queries)
+    for (int l = l0; l < nl; l++) {
+        coin.reseed(R.fri_roots[l]);
+        const fe2 alpha = KX == 1 ? fe2{coin.draw(), fe_zero()} : coin.draw_ext(2);
+        fe_to_bytes(alpha.a, R.fri_alphas[l]);
+        if (!fe_eq(alpha.a, dalpha[2 * l]) || (KX == 2 && !fe_eq(alpha.b, dalpha[2 * l + 1])))
+            ZK_FAIL(ZK_ERR_DEVICE, "device FRI transcript diverged from the host transcript");
+    }
+    if (ht) {
+        ht->stop("fri_replay");
+        ht->start();
+    }
+    if (KX == 1) return remainder_step(rv, B, coin, R, degree_flag);
+    return remainder_step_ext(rv, B, coin, R, degree_flag, Y.rem_flat);
+}
+
+void Openings::unpack(const fe *got, size_t nu, int CK, const std::vector<std::vector<uint64_t>> &fri_pos,
+                      uint32_t fold, int KX, size_t off_dig) {
+    trace_rows.assign(got, got + nu * W);
+    size_t off = nu * W;
+    comp_rows.assign(got + off, got + off + nu * CK);
+    off += nu * CK;
+    for (size_t l = 0; l < fri_rows.size(); l++) {
+        fri_rows[l].assign(got + off, got + off + fri_pos[l].size() * fold * KX);
+        off += fri_pos[l].size() * fold * KX;
+    }
+    const uint8_t *dg = (const uint8_t *)(got + off_dig);
+    for (size_t b = 0; b < plans.size(); b++) {
+        const size_t bytes = 32 * plans[b].count();
+        digests[b].assign(dg, dg + bytes);
+        dg += bytes;
+    }
+}
+
 static int prove_once(zk_prover *p, const TraceSrc &src, size_t n, const zk_options *opt, const zk_pub_inputs *pub,
                       uint8_t *proof_out, size_t *proof_len, zk_record *rec, const zk_dump *dump) {
     if (!p || !proof_len) ZK_FAIL(ZK_ERR_INVALID_ARG, "null argument");
@@ -1378,12 +1461,7 @@ static int prove_once(zk_prover *p, const TraceSrc &src, size_t n, const zk_opti
     const int C = num_comp_cols(n);
     if (C > 8) ZK_FAIL(ZK_ERR_INVALID_ARG, "composition column count exceeds 8");
     const fe g = h_root_of_unity(log_n);
-    zk_record R;
-    memset(&R, 0, sizeof R);
-    R.trace_len = (uint32_t)n;
-    R.lde_len = (uint32_t)N;
-    R.width = W;
-    R.num_ccols = (uint32_t)C;
+    zk_record R = record_init(n, N, C);
     stage_begin(p);
     stage_mark(p, "start");
 
@@ -1403,9 +1481,8 @@ static int prove_once(zk_prover *p, const TraceSrc &src, size_t n, const zk_opti
     // (a, b): the evaluator runs once per plane with that component of every coefficient.
     const int KX = (int)opt->field_extension, CK = C * KX;
     if (KX == 2) ZK_TRY(ensure_ext(p));
-    fe *comp = KX == 2 ? p->x_comp : p->comp, *ctmp = KX == 2 ? p->x_ctmp : p->ctmp;
-    fe *clde = KX == 2 ? p->x_clde : p->clde, *deep = KX == 2 ? p->x_deep : p->deep;
-    fe *fri = KX == 2 ? p->x_fri : p->fri;
+    const Planes pb = planes(p, KX);
+    fe *comp = pb.comp, *ctmp = pb.ctmp, *clde = pb.clde, *deep = pb.deep;
     // The assertion terms are not evaluated per row here: S4 adds them in coefficient form (unless the
     // caller dumps the composition values, which must then include them).
     const bool bnd_rows = dump && dump->composition;
@@ -1492,65 +1569,11 @@ static int prove_once(zk_prover *p, const TraceSrc &src, size_t n, const zk_opti
         for (int l = 0; l < nl; l++) tot += (s /= fold);
         if (tot > p->max_n * p->max_b) ZK_FAIL(ZK_ERR_INVALID_ARG, "FRI layers exceed the prover's buffers");
     }
-    std::vector<const fe *> layer_vals(nl + 1);
-    std::vector<uint8_t *> layer_leaves(nl), layer_nodes(nl);
-    std::vector<size_t> layer_len(nl + 1);
-    std::vector<fe> rem_flat;
+    FriLayers Y(nl);
     const fe *deep0 = lb0 ? (KX == 2 ? p->x_ulde : p->ulde) : deep;
-    layer_vals[0] = deep0;
-    layer_len[0] = N;
-    {
-        // The layer coins run on the device (fri_coin_launch): no host round trip per layer.  The
-        // constant part of the fold constants is uploaded once; each layer's coin writes alpha into it.
-        fe *next = fri;
-        uint8_t *dig = p->fri_dig;
-        fe *alpha_dev = nullptr;
-        if (KX == 1) {
-            const FoldConsts F = fold_consts(fe_zero(), fold);
-            ZK_TRY(h2d_small(p, p->fold_consts, &F, sizeof F));
-            alpha_dev = &((FoldConsts *)p->fold_consts)->alpha;
-        } else {
-            const FoldConstsE F = fold_consts_ext(fe2_zero(), fold);
-            ZK_TRY(h2d_small(p, p->x_fold_consts, &F, sizeof F));
-            alpha_dev = &((FoldConstsE *)p->x_fold_consts)->alpha.a;
-        }
-        ZK_TRY(h2d_small(p, p->fri_seed, coin.seed, 32));
-        for (int l = 0; l < nl; l++) {
-            const size_t L = layer_len[l], rows = L / fold;
-            layer_leaves[l] = dig;
-            layer_nodes[l] = dig + 32 * rows;
-            dig += 64 * rows;
-            const int lb = l ? 0 : lb0;
-            if (KX == 1) commit_fri_layer(p->st, layer_vals[l], L, (int)fold, layer_leaves[l], layer_nodes[l], lb);
-            else commit_fri_layer_ext(p->st, layer_vals[l], L, (int)fold, layer_leaves[l], layer_nodes[l], lb);
-            fri_coin_launch(p->st, (uint32_t *)p->fri_seed, layer_nodes[l] + 32, KX, alpha_dev, p->fri_alphas + 2 * l);
-            if (KX == 1) fri_fold_launch(p->st, layer_vals[l], L, (int)fold, p->fold_consts, pl->TN, N / L, next, lb);
-            else fri_fold_ext_launch(p->st, layer_vals[l], L, (int)fold, p->x_fold_consts, pl->TN, N / L, next, lb);
-            layer_vals[l + 1] = next;
-            layer_len[l + 1] = rows;
-            next += KX * rows;
-        }
-        // one round trip for the whole commit phase: roots, device alphas, the last layer
-        const size_t L = layer_len[nl];
-        std::vector<fe> rv(KX * L), dalpha(2 * nl);
-        for (int l = 0; l < nl; l++) ZK_TRY(d2h_small(p, R.fri_roots[l], layer_nodes[l] + 32, 32));
-        if (nl) ZK_TRY(d2h_small(p, dalpha.data(), p->fri_alphas, 2 * nl * sizeof(fe)));
-        ZK_TRY(d2h_small(p, rv.data(), layer_vals[nl], rv.size() * sizeof(fe)));
-        ZK_TRY(d2h_flush(p));
-        HT.start();
-        // host replay of the same transcript (it continues into the remainder, grinding and queries)
-        for (int l = 0; l < nl; l++) {
-            coin.reseed(R.fri_roots[l]);
-            const fe2 alpha = KX == 1 ? fe2{coin.draw(), fe_zero()} : coin.draw_ext(2);
-            fe_to_bytes(alpha.a, R.fri_alphas[l]);
-            if (!fe_eq(alpha.a, dalpha[2 * l]) || (KX == 2 && !fe_eq(alpha.b, dalpha[2 * l + 1])))
-                ZK_FAIL(ZK_ERR_DEVICE, "device FRI transcript diverged from the host transcript");
-        }
-        HT.stop("fri_replay");
-        HT.start();
-        if (KX == 1) ZK_TRY(remainder_step(rv, B, coin, R, degree_flag));
-        else ZK_TRY(remainder_step_ext(rv, B, coin, R, degree_flag, rem_flat));
-    }
+    Y.vals[0] = deep0;
+    Y.len[0] = N;
+    ZK_TRY(fri_lead_layers(p, pl, KX, fold, B, N, 0, lb0, pb.fri, p->fri_dig, Y, coin, R, degree_flag, &HT));
     stage_mark(p, "fri");
 
     HT.stop("remainder");
@@ -1572,7 +1595,7 @@ static int prove_once(zk_prover *p, const TraceSrc &src, size_t n, const zk_opti
     O.reset(2 + nl);
     plan_batch(N, pos, O.plans[0]);
     O.plans[1] = O.plans[0];  // the composition tree opens the same positions
-    for (int l = 0; l < nl; l++) plan_batch(layer_len[l] / fold, fri_pos[l], O.plans[2 + l]);
+    for (int l = 0; l < nl; l++) plan_batch(Y.len[l] / fold, fri_pos[l], O.plans[2 + l]);
     uint64_t *addr = p->h_gather_idx;
     size_t na = 0;
     auto fe_at = [&](const fe *base, size_t idx) { addr[na++] = (uint64_t)(uintptr_t)(base + idx); };
@@ -1589,18 +1612,18 @@ static int prove_once(zk_prover *p, const TraceSrc &src, size_t n, const zk_opti
     for (size_t q = 0; q < nu; q++) row_at(p->lde, W, pos[q]);
     for (size_t q = 0; q < nu; q++) row_at(clde, CK, pos[q]);
     for (int l = 0; l < nl; l++) {
-        const size_t rows = layer_len[l] / fold;
+        const size_t rows = Y.len[l] / fold;
         for (uint64_t r : fri_pos[l])
             for (uint32_t k = 0; k < fold; k++)
                 for (int j = 0; j < KX; j++) {
                     const uint64_t i = r + k * rows;  // natural index in layer l
-                    fe_at(layer_vals[l], j * layer_len[l] + ((l || !lb0) ? i : ((i & (B - 1)) << log_n) + (i >> log_b)));
+                    fe_at(Y.vals[l], j * Y.len[l] + ((l || !lb0) ? i : ((i & (B - 1)) << log_n) + (i >> log_b)));
                 }
     }
     const size_t off_dig = na;
     for (int b = 0; b < 2 + nl; b++) {
-        const uint8_t *lv = b == 0 ? p->leaves : b == 1 ? p->cleaves : layer_leaves[b - 2];
-        const uint8_t *nd = b == 0 ? p->nodes : b == 1 ? p->cnodes : layer_nodes[b - 2];
+        const uint8_t *lv = b == 0 ? p->leaves : b == 1 ? p->cleaves : Y.leaves[b - 2];
+        const uint8_t *nd = b == 0 ? p->nodes : b == 1 ? p->cnodes : Y.nodes[b - 2];
         for (auto &path : O.plans[b].paths)
             for (auto &e : path) {
                 const uint8_t *d = (e.first ? nd : lv) + 32 * e.second;
@@ -1613,34 +1636,17 @@ static int prove_once(zk_prover *p, const TraceSrc &src, size_t n, const zk_opti
     gather_chunks(p->st, p->gather_idx, na, p->gather_out);
     ZK_CHECK_HIP(hipMemcpyAsync(p->h_gather_out, p->gather_out, na * sizeof(fe), hipMemcpyDeviceToHost, p->st));
     ZK_CHECK_HIP(hipStreamSynchronize(p->st));
-    {
-        const fe *got = p->h_gather_out;
-        size_t off = 0;
-        O.trace_rows.assign(got, got + nu * W);
-        if (p->tc.virt)  // virtual columns: the gather read e_(n-1)'s LDE there; times the column's last row
-            for (size_t q = 0; q < nu; q++)
-                for (int c = 0; c < W; c++)
-                    if ((p->tc.virt >> c) & 1u) O.trace_rows[q * W + c] = fe_mul(O.trace_rows[q * W + c], p->tc.virt_last[c]);
-        off += nu * W;
-        O.comp_rows.assign(got + off, got + off + nu * CK);
-        off += nu * CK;
-        for (int l = 0; l < nl; l++) {
-            O.fri_rows[l].assign(got + off, got + off + fri_pos[l].size() * fold * KX);
-            off += fri_pos[l].size() * fold * KX;
-        }
-        const uint8_t *dg = (const uint8_t *)(got + off_dig);
-        for (int b = 0; b < 2 + nl; b++) {
-            const size_t bytes = 32 * O.plans[b].count();
-            O.digests[b].assign(dg, dg + bytes);
-            dg += bytes;
-        }
-    }
+    O.unpack(p->h_gather_out, nu, CK, fri_pos, fold, KX, off_dig);
+    if (p->tc.virt)  // virtual columns: the gather read e_(n-1)'s LDE there; times the column's last row
+        for (size_t q = 0; q < nu; q++)
+            for (int c = 0; c < W; c++)
+                if ((p->tc.virt >> c) & 1u) O.trace_rows[q * W + c] = fe_mul(O.trace_rows[q * W + c], p->tc.virt_last[c]);
     stage_mark(p, "queries");
 
     // S9: proof bytes [P13, P14]
     HT.start();
     std::vector<uint8_t> &bytes = p->proof_bytes;
-    serialize_proof(n, opt, C, R, h.data(), O, KX == 2 ? &rem_flat : nullptr, bytes);
+    serialize_proof(n, opt, C, R, h.data(), O, KX == 2 ? &Y.rem_flat : nullptr, bytes);
     HT.stop("serialize");
     stage_mark(p, "serialize");
     ZK_CHECK_HIP(hipStreamSynchronize(p->st));
@@ -1661,7 +1667,7 @@ static int prove_once(zk_prover *p, const TraceSrc &src, size_t n, const zk_opti
             ZK_CHECK_HIP(hipMemcpy(dump->deep, deep, N * 16, hipMemcpyDeviceToHost));
         }
         if (dump->fri_layer1 && nl > 0)
-            ZK_CHECK_HIP(hipMemcpy(dump->fri_layer1, layer_vals[1], layer_len[1] * 16, hipMemcpyDeviceToHost));
+            ZK_CHECK_HIP(hipMemcpy(dump->fri_layer1, Y.vals[1], Y.len[1] * 16, hipMemcpyDeviceToHost));
     }
     p->last_n = n;
     p->last_b = B;
@@ -2150,6 +2156,42 @@ extern "C" int zk_diag_upload_plan(const uint32_t *in, size_t n, uint32_t *masks
     off[W] = u.pack_bytes;
     for (int i = 0; i <= W; i++) pb[i] = i <= u.np ? u.pb[i] : -1;
     if (u.status != ZK_OK) ZK_FAIL(u.status, "too many upload groups");
+    return ZK_OK;
+}
+
+// Host: the rounds of the sharded trace split (shard_plan.hpp shard_round_plan) over the columns U[nU] (ascending), G ranks,
+// the first `rep` columns replicated.  out[(3 + 2 G) k ..] for round k: first split index, real, inplace, then per rank
+// g its column (-1: none) and the column its chunk of an in-place all-gather lands on (-1: a staged round); *rounds.
+extern "C" int zk_diag_shard_rounds(const int32_t *U, int nU, int G, int rep, int32_t *out, size_t cap, int32_t *rounds) {
+    if (!U || !out || !rounds || nU < 0 || nU > W || rep < 0 || rep > nU || (G != 2 && G != 4 && G != 8))
+        ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_shard_rounds: up to 28 columns, 0 <= rep <= nU, G = 2, 4 or 8");
+    const ShardRounds r = shard_round_plan(U, nU, G, rep);
+    if (cap < (size_t)r.rounds * (3 + 2 * G)) ZK_FAIL(ZK_ERR_BUFFER_TOO_SMALL, "zk_diag_shard_rounds: out too small");
+    for (int k = 0; k < r.rounds; k++) {
+        int32_t *o = out + (size_t)k * (3 + 2 * G);
+        o[0] = G * k, o[1] = r.real(k), o[2] = r.inplace(k);
+        for (int g = 0; g < G; g++) {
+            o[3 + g] = r.column(k, g);
+            o[3 + G + g] = r.inplace(k) ? r.first(k) + g : -1;
+        }
+    }
+    *rounds = r.rounds;
+    return ZK_OK;
+}
+
+// Host: where a Merkle tree of M leaves split over G ranks keeps leaf (is_node 0) or heap node idx[i] (shard_plan.hpp
+// TreeGeom::locate): out[3 i ..] = owner rank (-1: the host's top), buffer (1 subtree heap, 2 block buffer), byte offset.
+extern "C" int zk_diag_shard_locate(uint64_t M, int G, int is_node, const uint64_t *idx, size_t count, int64_t *out) {
+    if (!idx || !out || (G != 2 && G != 4 && G != 8) || M < 8 * (uint64_t)G || (M & (M - 1)))
+        ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_shard_locate: G = 2, 4 or 8, M a power of two >= 8 G");
+    TreeGeom T;
+    T.shape(M, G);
+    for (size_t i = 0; i < count; i++) {
+        if (is_node ? (idx[i] < 1 || idx[i] >= M) : idx[i] >= M)
+            ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_shard_locate: leaf index below M, heap node index in 1 .. M - 1");
+        const TreeGeom::Loc L = T.locate(is_node, idx[i]);
+        out[3 * i] = L.owner, out[3 * i + 1] = L.which, out[3 * i + 2] = (int64_t)L.off;
+    }
     return ZK_OK;
 }
 

@@ -15,6 +15,7 @@
 #include "../../include/zkvm_gpu.h"
 #include "air_shape.hpp"
 #include "host_field.hpp"
+#include "shard_plan.hpp"
 #include "upload_plan.hpp"
 #include "zk_internal.hpp"
 
@@ -647,7 +648,35 @@ struct Openings {
         plans.resize(nplans);
         digests.resize(nplans);
     }
+    // the gathered chunks in request order (nu trace rows, nu composition rows of CK elements, each layer's fold rows
+    // of KX planes; from off_dig every plan's digests, two chunks each) into the rows and digests
+    void unpack(const fe *got, size_t nu, int CK, const std::vector<std::vector<uint64_t>> &fri_pos, uint32_t fold,
+                int KX, size_t off_dig);
 };
+// the working set of a proof with KX planes: the E-valued buffers (KX = 2: planar, ensure_ext) or the base field's
+struct Planes {
+    fe *comp, *ctmp, *clde, *deep, *fri;
+    void *fold_consts, *air_consts;
+};
+inline Planes planes(const zk_prover *p, int KX) {
+    if (KX == 2) return {p->x_comp, p->x_ctmp, p->x_clde, p->x_deep, p->x_fri, p->x_fold_consts, p->x_air};
+    return {p->comp, p->ctmp, p->clde, p->deep, p->fri, p->fold_consts, p->air_consts};
+}
+zk_record record_init(size_t n, size_t N, int C);  // a proof's record: the shape fields set, the rest zero
+// S6 from layer l0 on, on one GPU (a single-GPU proof: from 0; a sharded proof's lead rank: from the gathered layer):
+// vals[l0] / len[l0] hold layer l0, stored with the low lb0 index bits major (FriLayout).  Commit, device coin and fold
+// per layer, `next` and `dig` the cursors of the layer values and digests; one flush of the roots, the device alphas and
+// the last layer; the host replays the transcript and commits the remainder (rem_flat: KX = 2).  ht: ZK_HOST_TIMING.
+struct HostTimer;
+struct FriLayers {
+    std::vector<const fe *> vals;
+    std::vector<uint8_t *> leaves, nodes;
+    std::vector<size_t> len;
+    std::vector<fe> rem_flat;
+    explicit FriLayers(int nl) : vals(nl + 1), leaves(nl), nodes(nl), len(nl + 1) {}
+};
+int fri_lead_layers(zk_prover *p, const Plan *pl, int KX, uint32_t fold, uint32_t B, size_t N, int l0, int lb0, fe *next,
+                    uint8_t *dig, FriLayers &Y, Coin &coin, zk_record &R, unsigned &degree_flag, HostTimer *ht = nullptr);
 // S9: Proof::to_bytes [P13, P14].  E values are k = opt->field_extension base elements each:
 // ood_flat = [T(z)]_W ++ [T(zg)]_W ++ [H(z)]_C flattened, comp_rows nu x C*k, fri_rows |pos| x fold*k;
 // the remainder is R.remainder (k = 1) or rem_flat (rem_len x k).

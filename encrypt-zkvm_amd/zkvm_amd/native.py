@@ -268,6 +268,10 @@ def lib():
         # (in[13], n, masks[8], counts[7], cols[4 W], width[W], off[W + 1], pb[W + 1], gsz[W])
         if hasattr(L, "zk_diag_upload_plan"):  # (an A/B library of an earlier commit, ZKVM_GPU_LIB, has none)
             L.zk_diag_upload_plan.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp, vp]
+        if hasattr(L, "zk_diag_shard_rounds"):
+            # (U[nU], nU, G, rep, out[rounds (3 + 2 G)], cap, rounds) / (M, G, is_node, idx[count], count, out[3 count])
+            L.zk_diag_shard_rounds.argtypes = [vp, i32, i32, i32, vp, sz, vp]
+            L.zk_diag_shard_locate.argtypes = [C.c_uint64, i32, i32, vp, sz, vp]
         L.zk_diag_field_op.argtypes = [i32, i32, vp, vp, vp, sz]
         L.zk_diag_blake3_rows.argtypes = [i32, vp, i32, sz, vp]
         L.zk_diag_ntt.argtypes = [i32, vp, sz, i32, i32, vp, vp]

@@ -123,6 +123,33 @@ def test_sharded_fri_layer1_folds_2_14(world, fold, rem, ext):
 
 
 @pytest.mark.gpu
+def test_sharded_gathered_layer1_in_place_2_13():
+    """Layer 1 too short to shard (2^13 / 16^2 = 32 positions per coset, under 8 per rank at 8 ranks) with a layer after
+    it, over the base field: layer 1 is all-gathered in place, coset-major, and the lead rank commits and folds it as its
+    first layer (no golden case takes this branch; over E, staged, pushadd12_quad_q43_f4 at 4 ranks does): byte-identical
+    to one GPU."""
+    from zkvm_amd.prover import vm_trace
+    from zkvm_amd.workloads import make_workload, ops_for_trace_len
+    src = ops_for_trace_len(13, "pushadd")
+    w = make_workload(src, seed=13)
+    trace, outputs, h = vm_trace(src, w.public, w.secret, w.server_key, w.last_row)
+    pub = make_pub_inputs(h, outputs, w.server_key.lwe_size(), w.server_key.parameters.delta)
+    opts = ProofOptions(fri_folding_factor=16, fri_remainder_max_degree=127)
+    g = GpuProver(0, max_trace_len=trace.shape[1])
+    try:
+        single, _, _, rc = g.prove(trace, pub, opts)
+    finally:
+        g.close()
+    assert rc == 0
+    sp = ShardedProver.loopback(8, max_trace_len=trace.shape[1])
+    try:
+        got, _ = sp.prove(trace, pub, opts)
+    finally:
+        sp.close()
+    assert got == single
+
+
+@pytest.mark.gpu
 def test_sharded_rccl_world1_and_device_trace():
     """The RCCL communicator (one rank on this GPU) and the device-resident trace path."""
     c = next(c for c in CASES if c["name"] == "cipher20")
