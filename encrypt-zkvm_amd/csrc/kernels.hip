@@ -29,9 +29,10 @@ static inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) 
 __device__ __forceinline__ fe ld_fe(const fe *p) { return *p; }
 __device__ __forceinline__ void st_fe(fe *p, fe v) { *p = v; }
 
-// w_n^t from split tables (t < n)
-__device__ __forceinline__ fe pow_split(const fe *lo, const fe *hi, size_t t) {
-    return fe_mul(lo[t & 2047], hi[t >> 11]);
+// w_n^t from split tables (t < n), base or challenge-field values
+template <class T>
+__device__ __forceinline__ T pow_split(const T *lo, const T *hi, size_t t) {
+    return ChalOf<T>::mul(lo[t & 2047], hi[t >> 11]);
 }
 
 // ================================================================ NTT engine
@@ -1242,19 +1243,25 @@ FriLayout fri_layout(size_t L, int lb) {
     return FriLayout{lb, lg - lb};
 }
 
+// row r of a layer over KX planes of L: [e(r + k rows)]_k, each value hashed as its KX components
+template <int KX>
 __global__ void __launch_bounds__(256) k_hash_fri_rows(const fe *layer, size_t L, int fold, FriLayout f, uint8_t *leaves) {
     const size_t rows = L / fold;
     for (size_t r = blockIdx.x * (size_t)blockDim.x + threadIdx.x; r < rows; r += (size_t)gridDim.x * blockDim.x) {
         uint32_t h[8];
-        b3::hash_elements(fold, [&](int k) { return layer[fri_at(f, r + (size_t)k * rows)]; }, h);
+        b3::hash_elements(KX * fold, [&](int t) { return layer[(size_t)(t % KX) * L + fri_at(f, r + (size_t)(t / KX) * rows)]; }, h);
         store_digest(leaves + 32 * r, h);
     }
 }
 
-void commit_fri_layer(hipStream_t st, const fe *layer, size_t L, int fold, uint8_t *leaves, uint8_t *nodes, int lb) {
+void commit_fri_layer(hipStream_t st, int KX, const fe *layer, size_t L, int fold, uint8_t *leaves, uint8_t *nodes, int lb) {
     const size_t rows = L / fold;
     const FriLayout f = fri_layout(L, lb);
-    ZK_PROF(st, "hash_fri_rows", 16.0 * L + 32.0 * rows, hipLaunchKernelGGL(k_hash_fri_rows, dim3(cdiv(rows, 256)), dim3(256), 0, st, layer, L, fold, f, leaves));
+    const dim3 grid(cdiv(rows, 256));
+    if (KX == 1)
+        ZK_PROF(st, "hash_fri_rows", 16.0 * L + 32.0 * rows, hipLaunchKernelGGL(k_hash_fri_rows<1>, grid, dim3(256), 0, st, layer, L, fold, f, leaves));
+    else
+        ZK_PROF(st, "hash_fri_rows_ext", 32.0 * L + 32.0 * rows, hipLaunchKernelGGL(k_hash_fri_rows<2>, grid, dim3(256), 0, st, layer, L, fold, f, leaves));
     merkle_tree(st, leaves, rows, nodes);
 }
 
@@ -2228,21 +2235,13 @@ void comp_cross_mapped(hipStream_t st, const CrossMap &m, const NttTables &T8n, 
 // group of OOD_GROUP polynomials so a proof launches ~5x the waves of one poly sweep.
 constexpr int OOD_GROUP = 7;
 
-__device__ __forceinline__ fe wave_sum(fe v) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) {
-        fe o;
-        o.lo = __shfl_xor(v.lo, s, 64);
-        o.hi = __shfl_xor(v.hi, s, 64);
-        v = fe_add(v, o);
-    }
-    return v;
-}
-
-__global__ void k_ood_tables(fe z, fe zg, uint64_t chunk, int nw, fe *tab) {
+template <int KX>
+__global__ void k_ood_tables(typename Chal<KX>::T z, typename Chal<KX>::T zg, uint64_t chunk, int nw,
+                             typename Chal<KX>::T *tab) {
+    typedef typename Chal<KX>::T T;
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= 128 + 2 * nw) return;
-    fe x;
+    T x;
     uint64_t e;
     if (t < 128) {
         x = t < 64 ? z : zg;
@@ -2252,14 +2251,19 @@ __global__ void k_ood_tables(fe z, fe zg, uint64_t chunk, int nw, fe *tab) {
         x = u < nw ? z : zg;
         e = chunk * (uint64_t)(u < nw ? u : u - nw);
     }
-    tab[t] = fe_exp(x, e);
+    tab[t] = Chal<KX>::exp(x, e);
 }
 
-template <int E>
+// C counts base columns (over E: 2 per composition column); np = 2W + C values per plane of partials
+template <int KX, int E>
 __global__ void __launch_bounds__(256) k_ood_eval(const fe *tpolys, int W, const fe *cpolys, int C, size_t n,
-                                                  const fe *tab, int nw, int w0, int w1, fe *partials) {
+                                                  const typename Chal<KX>::T *tab, int nw, int w0, int w1,
+                                                  fe *partials) {
+    typedef Chal<KX> X;
+    typedef typename X::T T;
     const int gw = w0 + (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);  // waves [w0, w1) of nw
     const int lane = threadIdx.x & 63;
+    const size_t plane = (size_t)(2 * W + C) * nw;
     const int tgroups = (W + OOD_GROUP - 1) / OOD_GROUP;
     const int g = blockIdx.y;
     const bool comp = g >= tgroups;
@@ -2268,16 +2272,16 @@ __global__ void __launch_bounds__(256) k_ood_eval(const fe *tpolys, int W, const
     const size_t base = (size_t)gw * 64 * E + lane;
     // a lane's E coefficients sit 64 apart: sum_e v_e (x^64)^e as a lazy dot product against the powers
     // (x^64)^e in LDS (one unreduced product per coefficient instead of a reduced Horner step)
-    __shared__ fe Y[2][E];
+    __shared__ T Y[2][E];
     if (threadIdx.x < 2 * E) {
         const int which = threadIdx.x / E, e = threadIdx.x % E;
-        const fe y = which ? fe_mul(tab[127], tab[65]) : fe_mul(tab[63], tab[1]);  // x^64
-        Y[which][e] = fe_exp(y, (uint64_t)e);
+        const T y = which ? X::mul(tab[127], tab[65]) : X::mul(tab[63], tab[1]);  // x^64
+        Y[which][e] = X::exp(y, (uint64_t)e);
     }
     __syncthreads();
     if (gw >= w1) return;
-    const fe wz = fe_mul(tab[lane], tab[128 + gw]);
-    const fe wzg = comp ? fe_zero() : fe_mul(tab[64 + lane], tab[128 + nw + gw]);
+    const T wz = X::mul(tab[lane], tab[128 + gw]);
+    const T wzg = comp ? X::zero() : X::mul(tab[64 + lane], tab[128 + nw + gw]);
     for (int p = p0; p < p1; p++) {
         const fe *c = (comp ? cpolys : tpolys) + (size_t)p * n;
         fe v[E];
@@ -2286,45 +2290,43 @@ __global__ void __launch_bounds__(256) k_ood_eval(const fe *tpolys, int W, const
             const size_t k = base + 64 * (size_t)e;
             v[e] = k < n ? c[k] : fe_zero();
         }
-        acc288 az = acc288_zero();
-#pragma unroll
-        for (int e = 0; e < E; e++) acc288_madd(az, v[e], Y[0][e]);
-        const fe hz = wave_sum(fe_mul(acc288_reduce(az), wz));
-        if (lane == 0) partials[(size_t)(comp ? 2 * W + p : p) * nw + gw] = hz;
+        const T hz = wave_sum(X::mul(dot_base<E>(v, Y[0]), wz));
+        if (lane == 0) X::st(partials + (size_t)(comp ? 2 * W + p : p) * nw + gw, plane, hz);
         if (!comp) {
-            acc288 ag = acc288_zero();
-#pragma unroll
-            for (int e = 0; e < E; e++) acc288_madd(ag, v[e], Y[1][e]);
-            const fe hg = wave_sum(fe_mul(acc288_reduce(ag), wzg));
-            if (lane == 0) partials[(size_t)(W + p) * nw + gw] = hg;
+            const T hg = wave_sum(X::mul(dot_base<E>(v, Y[1]), wzg));
+            if (lane == 0) X::st(partials + (size_t)(W + p) * nw + gw, plane, hg);
         }
     }
 }
 
 int ood_waves(size_t n) { return (int)std::max<size_t>(1, n / 1024); }
 
-// part = (rank, G): only this rank's share of the coefficient range (waves [rank nw / G, (rank + 1) nw / G)), so that
-// the G partial sums of each value add up to it (the sharded prover all-gathers them); (0, 1) = the whole range
-void ood_eval(hipStream_t st, const fe *tpolys, int W, const fe *cpolys, int C, int log_n, fe z, fe zg, fe *tab,
+template <class T>
+void ood_eval(hipStream_t st, const fe *tpolys, int W, const fe *cpolys, int C, int log_n, T z, T zg, fe *tab,
               fe *partials, fe *out, int rank, int G) {
+    constexpr int KX = ChalOf<T>::KX;
     const size_t n = (size_t)1 << log_n;
     const int E = n >= 1024 ? 16 : std::max<int>(1, (int)(n / 64));
     const int nw = (int)((n + 64 * E - 1) / (64 * E));
     const int w0 = (int)((int64_t)nw * rank / G), w1 = (int)((int64_t)nw * (rank + 1) / G);
-    hipLaunchKernelGGL(k_ood_tables, dim3(cdiv(128 + 2 * nw, 256)), dim3(256), 0, st, z, zg, (uint64_t)64 * E, nw, tab);
+    T *t = reinterpret_cast<T *>(tab);
+    hipLaunchKernelGGL(k_ood_tables<KX>, dim3(cdiv(128 + 2 * nw, 256)), dim3(256), 0, st, z, zg, (uint64_t)64 * E, nw, t);
     const dim3 grid(std::max(1u, cdiv(w1 - w0, 4)), (W + OOD_GROUP - 1) / OOD_GROUP + 1);
-#define ZK_OOD(EE) hipLaunchKernelGGL((k_ood_eval<EE>), grid, dim3(256), 0, st, tpolys, W, cpolys, C, n, tab, nw, w0, w1, partials)
+    const char *name = KX == 1 ? "ood_eval" : "ood_eval_ext";
+#define ZK_OOD(EE) ZK_PROF(st, name, bytes, hipLaunchKernelGGL((k_ood_eval<KX, EE>), grid, dim3(256), 0, st, tpolys, W, cpolys, C, n, t, nw, w0, w1, partials))
     const double bytes = 16.0 * (W + C) * (double)n * (w1 - w0) / nw;
     switch (E) {
-        case 16: ZK_PROF(st, "ood_eval", bytes, ZK_OOD(16)); break;
-        case 8: ZK_PROF(st, "ood_eval", bytes, ZK_OOD(8)); break;
-        case 4: ZK_PROF(st, "ood_eval", bytes, ZK_OOD(4)); break;
-        case 2: ZK_PROF(st, "ood_eval", bytes, ZK_OOD(2)); break;
-        default: ZK_PROF(st, "ood_eval", bytes, ZK_OOD(1)); break;
+        case 16: ZK_OOD(16); break;
+        case 8: ZK_OOD(8); break;
+        case 4: ZK_OOD(4); break;
+        case 2: ZK_OOD(2); break;
+        default: ZK_OOD(1); break;
     }
 #undef ZK_OOD
-    sum_partials(st, partials, 2 * W + C, nw, out, w0, w1);
+    sum_partials(st, partials, KX * (2 * W + C), nw, out, w0, w1);
 }
+template void ood_eval<fe>(hipStream_t, const fe *, int, const fe *, int, int, fe, fe, fe *, fe *, fe *, int, int);
+template void ood_eval<fe2>(hipStream_t, const fe *, int, const fe *, int, int, fe2, fe2, fe *, fe *, fe *, int, int);
 
 __global__ void k_sum_partials(const fe *partials, int nblk, int b0, int b1, fe *out) {
     __shared__ fe red[256];
@@ -2357,18 +2359,21 @@ void sum_partials(hipStream_t st, const fe *partials, int npolys, int nblk, fe *
 // LDE columns, without reading those columns (3.7 GB at 2^20) or inverting 8n denominators.
 constexpr int DIV_T = 256, DIV_E = 8, DIV_CH = DIV_T * DIV_E;
 static_assert(DIV_CH == ZK_DEEP_RANGE_QUANTUM, "a sharded DEEP range is whole phase-3 chunks");
+static_assert(DIV_T == ZK_DEEP_BLOCK, "DeepScratch counts phase-1 blocks");
 
 // base^e for e < 2048 (lo) and base^(2048 u) for u < H (hi), 4 bases: z, zg, 1/z, 1/zg
+template <int KX>
 struct DeepPowBases {
-    fe b[4];
+    typename Chal<KX>::T b[4];
 };
-__global__ void k_deep_pow_tables(DeepPowBases pb, size_t H, fe *out) {
+template <int KX>
+__global__ void k_deep_pow_tables(DeepPowBases<KX> pb, size_t H, typename Chal<KX>::T *out) {
     const size_t per = 2048 + H;
     const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (t >= 4 * per) return;
     const size_t b = t / per, e = t % per;
     const uint64_t ex = e < 2048 ? e : 2048 * (uint64_t)(e - 2048);
-    out[t] = fe_exp(pb.b[b], ex, 0);
+    out[t] = Chal<KX>::exp(pb.b[b], ex);
 }
 
 __device__ __forceinline__ fe block_sum256(fe v, fe *red) {
@@ -2384,31 +2389,49 @@ __device__ __forceinline__ fe block_sum256(fe v, fe *red) {
 
 // phase 1: g1, g2 and per-256 totals (one coefficient per thread)
 // [kbase, kend): the coefficient range of this launch (a sharded rank's share; 0, n otherwise); n is the column stride
+template <int KX>
 __global__ void __launch_bounds__(DIV_T) k_deep_div_g(const fe *tpolys, const fe *cpolys, int ccols, size_t n,
-                                                     const DeepConsts *D, const fe *pw, size_t H, fe *g1, fe *g2,
-                                                     fe *bs, size_t kbase, size_t kend) {
+                                                     const DeepConsts<KX> *D, const typename Chal<KX>::T *pw, size_t H,
+                                                     typename Chal<KX>::T *g1, typename Chal<KX>::T *g2, fe *bs,
+                                                     size_t kbase, size_t kend) {
+    typedef Chal<KX> X;
+    typedef typename X::T T;
     __shared__ fe red[DIV_T / 64];
     const size_t per = 2048 + H;
     const size_t k = kbase + blockIdx.x * (size_t)DIV_T + threadIdx.x;
-    fe v1 = fe_zero(), v2 = fe_zero();
+    T v1 = X::zero(), v2 = X::zero();
     if (k < kend) {
-        acc288 aA = acc288_zero(), aH = acc288_zero();
+        typename X::Acc aA = X::acc_zero();
 #pragma unroll 4
-        for (int c = 0; c < 28; c++) acc288_madd(aA, D->alpha_t[c], ld_fe(tpolys + (size_t)c * n + k));
-        for (int j = 0; j < ccols; j++) acc288_madd(aH, D->alpha_c[j], ld_fe(cpolys + (size_t)j * n + k));
-        const fe A = acc288_reduce(aA);
-        const fe S = fe_add(A, acc288_reduce(aH));
-        v1 = fe_mul(S, pow_split(pw, pw + 2048, k));
-        v2 = fe_mul(A, pow_split(pw + per, pw + per + 2048, k));
+        for (int c = 0; c < 28; c++) X::madd(aA, D->alpha_t[c], ld_fe(tpolys + (size_t)c * n + k));
+        typename X::Acc aH = X::acc_zero();
+        if constexpr (KX == 1) {
+            for (int j = 0; j < ccols; j++) X::madd(aH, D->alpha_c[j], ld_fe(cpolys + (size_t)j * n + k));
+        } else {
+            // over E the composition columns stay base columns: E column j is P_2j + X P_2j+1, and
+            // (c.a + c.b X)(h0 + h1 X) = (c.a h0 + c.b h1) + (c.a h1 + c.b (h0 + h1)) X
+            for (int j = 0; j < ccols; j++) {
+                const fe h0 = ld_fe(cpolys + (size_t)(2 * j) * n + k), h1 = ld_fe(cpolys + (size_t)(2 * j + 1) * n + k);
+                const fe2 ac = D->alpha_c[j];
+                acc288_madd(aH.a, ac.a, h0);
+                acc288_madd(aH.a, ac.b, h1);
+                acc288_madd(aH.b, ac.a, h1);
+                acc288_madd(aH.b, ac.b, fe_add(h0, h1));
+            }
+        }
+        const T A = X::reduce(aA);
+        const T S = X::add(A, X::reduce(aH));
+        v1 = X::mul(S, pow_split(pw, pw + 2048, k));
+        v2 = X::mul(A, pow_split(pw + per, pw + per + 2048, k));
         g1[k] = v1;
         g2[k] = v2;
     }
-    v1 = block_sum256(v1, red);
-    v2 = block_sum256(v2, red);
-    if (threadIdx.x == 0) {
-        bs[2 * blockIdx.x] = v1;
-        bs[2 * blockIdx.x + 1] = v2;
-    }
+    fe s[2 * KX];  // the block's sums of g1, then of g2, by component
+#pragma unroll
+    for (int c = 0; c < 2 * KX; c++) s[c] = block_sum256(X::comp(c < KX ? v1 : v2, c % KX), red);
+    if (threadIdx.x == 0)
+#pragma unroll
+        for (int c = 0; c < 2 * KX; c++) bs[2 * KX * blockIdx.x + c] = s[c];
 }
 
 // phase 2 (one block): carry[j] = sum of the totals of blocks after j (exclusive suffix), NC components
@@ -2454,37 +2477,51 @@ __global__ void __launch_bounds__(1024) k_deep_div_scan(fe *bs, int nb, fe *tota
         }
 }
 
-// phase 3: thread owns 8 consecutive coefficients; D_k = z^-(k+1) suf1_k + zg^-(k+1) suf2_k.
-// ADD: D_k is added into Dk[k] (the boundary quotient into composition column 0).  rem_flag (optional):
-// set when sum_m g1_m or sum_m g2_m -- the remainders F1(z), F2(zg) of the divisions -- is nonzero.
+// phase 3: thread owns 8 consecutive coefficients; D_k = z^-(k+1) suf1_k + zg^-(k+1) suf2_k, stored into the KX planes
+// of Dk (plane stride `plane`).  ADD: D_k is added into Dk[k] (the boundary quotient into composition column 0).
+// rem_flag (optional): set when sum_m g1_m or sum_m g2_m -- the remainders F1(z), F2(zg) of the divisions -- is nonzero.
+// Both serve the boundary quotient, which is taken per coefficient plane: KX = 1 only.
 // [kbase, n): the coefficient range (a sharded rank's share ends at n = its range end); ext (optional): the sums
 // of g1, g2 over every coefficient past the range (the later ranks' totals)
-template <bool ADD>
-__global__ void __launch_bounds__(DIV_T) k_deep_div_q(const fe *g1, const fe *g2, const fe *carry, int nb1, size_t n,
-                                                     fe z, fe zg, const fe *pw, size_t H, fe *Dk, unsigned *rem_flag,
-                                                     size_t kbase, const fe *ext) {
-    __shared__ fe t1[DIV_T], t2[DIV_T];
+template <int KX, bool ADD>
+__global__ void __launch_bounds__(DIV_T) k_deep_div_q(const typename Chal<KX>::T *g1, const typename Chal<KX>::T *g2,
+                                                     const fe *carry, int nb1, size_t n, typename Chal<KX>::T z,
+                                                     typename Chal<KX>::T zg, const typename Chal<KX>::T *pw, size_t H,
+                                                     fe *Dk, size_t plane, unsigned *rem_flag, size_t kbase,
+                                                     const fe *ext) {
+    typedef Chal<KX> X;
+    typedef typename X::T T;
+    static_assert(KX == 1 || !ADD, "the boundary quotient is per plane");
+    // the 16 values a thread sums are held for the second pass over F (the loops over them are unrolled, so that they
+    // stay in registers); over E (32 fe) they are read again: holding them would roughly double the kernel's registers
+    constexpr bool HOLD = KX == 1;
+    __shared__ T t1[DIV_T], t2[DIV_T];
     const size_t per = 2048 + H;
-    const fe *ilo = pw + 2 * per, *ihi = ilo + 2048, *jlo = pw + 3 * per, *jhi = jlo + 2048;
+    const T *ilo = pw + 2 * per, *ihi = ilo + 2048, *jlo = pw + 3 * per, *jhi = jlo + 2048;
     const size_t k0 = kbase + blockIdx.x * (size_t)DIV_CH + (size_t)threadIdx.x * DIV_E;
-    fe a[DIV_E], b[DIV_E];
-    fe s1 = fe_zero(), s2 = fe_zero();
-#pragma unroll
+    T a[HOLD ? DIV_E : 1], b[HOLD ? DIV_E : 1];
+    T s1 = X::zero(), s2 = X::zero();
+#pragma unroll HOLD ? DIV_E : 1
     for (int e = 0; e < DIV_E; e++) {
         const size_t k = k0 + e;
-        a[e] = k < n ? ld_fe(g1 + k) : fe_zero();
-        b[e] = k < n ? ld_fe(g2 + k) : fe_zero();
-        s1 = fe_add(s1, a[e]);
-        s2 = fe_add(s2, b[e]);
+        if constexpr (HOLD) {
+            a[e] = k < n ? g1[k] : X::zero();
+            b[e] = k < n ? g2[k] : X::zero();
+            s1 = X::add(s1, a[e]);
+            s2 = X::add(s2, b[e]);
+        } else if (k < n) {
+            s1 = X::add(s1, g1[k]);
+            s2 = X::add(s2, g2[k]);
+        }
     }
     t1[threadIdx.x] = s1;
     t2[threadIdx.x] = s2;
     __syncthreads();
     for (int d = 1; d < DIV_T; d <<= 1) {
-        fe x = t1[threadIdx.x], y = t2[threadIdx.x];
+        T x = t1[threadIdx.x], y = t2[threadIdx.x];
         if (threadIdx.x + d < DIV_T) {
-            x = fe_add(x, t1[threadIdx.x + d]);
-            y = fe_add(y, t2[threadIdx.x + d]);
+            x = X::add(x, t1[threadIdx.x + d]);
+            y = X::add(y, t2[threadIdx.x + d]);
         }
         __syncthreads();
         t1[threadIdx.x] = x;
@@ -2493,26 +2530,27 @@ __global__ void __launch_bounds__(DIV_T) k_deep_div_q(const fe *g1, const fe *g2
     }
     // R = sum of g over m >= k0 + 8: later threads of this chunk + the phase-1 blocks after it
     const int cb = min((int)blockIdx.x * (DIV_CH / DIV_T) + DIV_CH / DIV_T - 1, nb1 - 1);
-    fe r1 = fe_add(carry[2 * cb], threadIdx.x + 1 < DIV_T ? t1[threadIdx.x + 1] : fe_zero());
-    fe r2 = fe_add(carry[2 * cb + 1], threadIdx.x + 1 < DIV_T ? t2[threadIdx.x + 1] : fe_zero());
+    T r1 = X::add(X::ld(carry + 2 * KX * cb, 1), threadIdx.x + 1 < DIV_T ? t1[threadIdx.x + 1] : X::zero());
+    T r2 = X::add(X::ld(carry + 2 * KX * cb + KX, 1), threadIdx.x + 1 < DIV_T ? t2[threadIdx.x + 1] : X::zero());
     if (ext) {
-        r1 = fe_add(r1, ext[0]);
-        r2 = fe_add(r2, ext[1]);
+        r1 = X::add(r1, X::ld(ext, 1));
+        r2 = X::add(r2, X::ld(ext + KX, 1));
     }
-    fe pz = pow_split(ilo, ihi, k0 + DIV_E), pg = pow_split(jlo, jhi, k0 + DIV_E);  // z^-(k+1) at k = k0 + 7
-#pragma unroll
+    T pz = pow_split(ilo, ihi, k0 + DIV_E), pg = pow_split(jlo, jhi, k0 + DIV_E);  // z^-(k+1) at k = k0 + 7
+#pragma unroll HOLD ? DIV_E : 1
     for (int e = DIV_E - 1; e >= 0; e--) {
         const size_t k = k0 + e;
         if (k < n) {
-            const fe q = fe_add(fe_mul(pz, r1), fe_mul(pg, r2));
-            Dk[k] = ADD ? fe_add(ld_fe(Dk + k), q) : q;
+            const T q = X::add(X::mul(pz, r1), X::mul(pg, r2));
+            X::st(Dk + k, plane, ADD ? X::add(X::ld(Dk + k, plane), q) : q);
+            if constexpr (!HOLD) r1 = X::add(r1, g1[k]), r2 = X::add(r2, g2[k]);
         }
-        r1 = fe_add(r1, a[e]);
-        r2 = fe_add(r2, b[e]);
-        pz = fe_mul(pz, z);
-        pg = fe_mul(pg, zg);
+        if constexpr (HOLD) r1 = X::add(r1, a[e]), r2 = X::add(r2, b[e]);
+        pz = X::mul(pz, z);
+        pg = X::mul(pg, zg);
     }
-    if (rem_flag && k0 == 0 && !(fe_is_zero(r1) && fe_is_zero(r2))) atomicOr(rem_flag, 1u);
+    if constexpr (KX == 1)
+        if (rem_flag && k0 == 0 && !(fe_is_zero(r1) && fe_is_zero(r2))) atomicOr(rem_flag, 1u);
 }
 
 // coset-major LDE -> natural order
@@ -2528,58 +2566,64 @@ void lde_cosets(hipStream_t st, const NttTables &Tn, const CosetTables &CT, cons
     ntt_lde(st, Tn, CT, coeffs, 0, 1, (int)r0, (int)stride, count, out, 0, n, ntt_tmp);
 }
 
-// Scratch layout (deep_poly_scratch): pw (4 power tables) | g1 (n) | g2 (n) | Dk (n) | block sums.
-// A range [k0, k0 + kn) of a sharded rank (deep_range_*): the same buffers indexed by global coefficient; the range
-// totals go to the block-sum area's tail (deep_range_total).
-static void deep_tables(hipStream_t st, size_t n, fe z, fe zg, fe *pw) {
-    const size_t H = n / 2048 + 2;  // hi[] covers every t < nb * 2048 + 8
-    DeepPowBases pb;
+// The scratch is a DeepScratch (zk_internal.hpp).  A range [k0, k0 + kn) of a sharded rank (deep_range_*) uses the same
+// buffers indexed by global coefficient; its block sums start at bs and its totals go to DeepScratch::total.
+template <class T>
+static void deep_tables(hipStream_t st, size_t n, T z, T zg, fe *scratch) {
+    constexpr int KX = ChalOf<T>::KX;
+    const DeepScratch S(scratch, n, KX);
+    DeepPowBases<KX> pb;
     pb.b[0] = z;
     pb.b[1] = zg;
-    pb.b[2] = fe_inv(z);
-    pb.b[3] = fe_inv(zg);
-    hipLaunchKernelGGL(k_deep_pow_tables, dim3(cdiv(4 * (2048 + H), 256)), dim3(256), 0, st, pb, H, pw);
+    pb.b[2] = ChalOf<T>::inv(z);
+    pb.b[3] = ChalOf<T>::inv(zg);
+    hipLaunchKernelGGL(k_deep_pow_tables<KX>, dim3(cdiv(4 * (2048 + S.H), 256)), dim3(256), 0, st, pb, S.H, (T *)S.pw);
 }
-static void deep_phase1(hipStream_t st, const fe *tpolys, const fe *cpolys, int ccols, size_t n, const DeepConsts *D,
-                        fe *scratch, size_t k0, size_t kn, fe *total) {
-    const size_t H = n / 2048 + 2, nb1 = (kn + DIV_T - 1) / DIV_T;
-    fe *pw = scratch, *g1 = pw + 4 * (2048 + H), *g2 = g1 + n, *bs = g2 + 2 * n;
-    ZK_PROF(st, "deep_combine", (16.0 * (28 + ccols) + 32.0) * kn,
-            hipLaunchKernelGGL(k_deep_div_g, dim3((unsigned)nb1), dim3(DIV_T), 0, st, tpolys, cpolys, ccols, n, D, pw, H,
-                               g1, g2, bs, k0, k0 + kn));
-    hipLaunchKernelGGL(k_deep_div_scan<2>, dim3(1), dim3(1024), 0, st, bs, (int)nb1, total);
+template <class T>
+static void deep_phase1(hipStream_t st, const fe *tpolys, const fe *cpolys, int ccols, size_t n,
+                        const void *deep_consts_dev, fe *scratch, size_t k0, size_t kn, fe *total) {
+    constexpr int KX = ChalOf<T>::KX;
+    const DeepScratch S(scratch, n, KX);
+    const size_t nb1 = (kn + DIV_T - 1) / DIV_T;
+    ZK_PROF(st, "deep_combine", (16.0 * (28 + KX * ccols) + 32.0 * KX) * kn,
+            hipLaunchKernelGGL(k_deep_div_g<KX>, dim3((unsigned)nb1), dim3(DIV_T), 0, st, tpolys, cpolys, ccols, n,
+                               (const DeepConsts<KX> *)deep_consts_dev, (const T *)S.pw, S.H, (T *)S.g1, (T *)S.g2, S.bs, k0,
+                               k0 + kn));
+    hipLaunchKernelGGL(k_deep_div_scan<2 * KX>, dim3(1), dim3(1024), 0, st, S.bs, (int)nb1, total);
 }
-static void deep_phase3(hipStream_t st, size_t n, fe z, fe zg, fe *scratch, size_t k0, size_t kn, const fe *ext) {
-    const size_t H = n / 2048 + 2, nb = (kn + DIV_CH - 1) / DIV_CH, nb1 = (kn + DIV_T - 1) / DIV_T;
-    fe *pw = scratch, *g1 = pw + 4 * (2048 + H), *g2 = g1 + n, *Dk = g2 + n, *bs = Dk + n;
-    ZK_PROF(st, "deep_divide", 48.0 * kn,
-            hipLaunchKernelGGL(k_deep_div_q<false>, dim3((unsigned)nb), dim3(DIV_T), 0, st, g1, g2, bs, (int)nb1, k0 + kn, z,
-                               zg, pw, H, Dk, nullptr, k0, ext));
+template <class T>
+static void deep_phase3(hipStream_t st, size_t n, T z, T zg, fe *scratch, size_t k0, size_t kn, const fe *ext) {
+    constexpr int KX = ChalOf<T>::KX;
+    const DeepScratch S(scratch, n, KX);
+    const size_t nb = (kn + DIV_CH - 1) / DIV_CH, nb1 = (kn + DIV_T - 1) / DIV_T;
+    ZK_PROF(st, "deep_divide", KX * 48.0 * kn,
+            hipLaunchKernelGGL((k_deep_div_q<KX, false>), dim3((unsigned)nb), dim3(DIV_T), 0, st, (const T *)S.g1,
+                               (const T *)S.g2, S.bs, (int)nb1, k0 + kn, z, zg, (const T *)S.pw, S.H, S.out, n, nullptr, k0,
+                               ext));
 }
+template <class T>
 const fe *deep_poly(hipStream_t st, const fe *tpolys, const fe *cpolys, int ccols, int log_n,
-                    const void *deep_consts_dev, fe z, fe zg, fe *scratch) {
-    const size_t n = (size_t)1 << log_n, H = n / 2048 + 2;
-    deep_tables(st, n, z, zg, scratch);
-    deep_phase1(st, tpolys, cpolys, ccols, n, (const DeepConsts *)deep_consts_dev, scratch, 0, n, nullptr);
-    deep_phase3(st, n, z, zg, scratch, 0, n, nullptr);
-    return scratch + 4 * (2048 + H) + 2 * n;
-}
-static fe *deep_range_total(fe *scratch, size_t n, int nc) {
-    const size_t H = n / 2048 + 2;
-    return scratch + 4 * (2048 + H) + 3 * n + (size_t)nc * ((n + DIV_T - 1) / DIV_T);
-}
-const fe *deep_range_begin(hipStream_t st, const fe *tpolys, const fe *cpolys, int ccols, int log_n,
-                           const void *deep_consts_dev, fe z, fe zg, fe *scratch, size_t k0, size_t kn) {
+                    const void *deep_consts_dev, T z, T zg, fe *scratch) {
     const size_t n = (size_t)1 << log_n;
     deep_tables(st, n, z, zg, scratch);
-    fe *total = deep_range_total(scratch, n, 2);
-    deep_phase1(st, tpolys, cpolys, ccols, n, (const DeepConsts *)deep_consts_dev, scratch, k0, kn, total);
+    deep_phase1<T>(st, tpolys, cpolys, ccols, n, deep_consts_dev, scratch, 0, n, nullptr);
+    deep_phase3(st, n, z, zg, scratch, 0, n, nullptr);
+    return DeepScratch(scratch, n, ChalOf<T>::KX).out;
+}
+template <class T>
+const fe *deep_range_begin(hipStream_t st, const fe *tpolys, const fe *cpolys, int ccols, int log_n,
+                           const void *deep_consts_dev, T z, T zg, fe *scratch, size_t k0, size_t kn) {
+    const size_t n = (size_t)1 << log_n;
+    deep_tables(st, n, z, zg, scratch);
+    fe *total = DeepScratch(scratch, n, ChalOf<T>::KX).total;
+    deep_phase1<T>(st, tpolys, cpolys, ccols, n, deep_consts_dev, scratch, k0, kn, total);
     return total;
 }
-const fe *deep_range_end(hipStream_t st, int log_n, fe z, fe zg, fe *scratch, size_t k0, size_t kn, const fe *ext) {
-    const size_t n = (size_t)1 << log_n, H = n / 2048 + 2;
+template <class T>
+const fe *deep_range_end(hipStream_t st, int log_n, T z, T zg, fe *scratch, size_t k0, size_t kn, const fe *ext) {
+    const size_t n = (size_t)1 << log_n;
     deep_phase3(st, n, z, zg, scratch, k0, kn, ext);
-    return scratch + 4 * (2048 + H) + 2 * n;
+    return DeepScratch(scratch, n, ChalOf<T>::KX).out;
 }
 
 // ---- boundary terms in coefficient form.  The assertion part of the composition,
@@ -2633,29 +2677,29 @@ __global__ void __launch_bounds__(DIV_T) k_bnd_div_g(const fe *tpolys, size_t n,
 
 static void bnd_tables_phase1(hipStream_t st, const fe *tpolys, size_t n, const AirConsts &K, fe c, fe *scratch,
                               size_t k0, size_t kn, fe *total) {
-    const size_t H = n / 2048 + 2, nb1 = (kn + DIV_T - 1) / DIV_T;
-    fe *pw = scratch, *g1 = pw + 4 * (2048 + H), *g2 = g1 + n, *bs = g2 + 2 * n;  // layout of deep_poly's scratch
-    DeepPowBases pb;
+    const DeepScratch S(scratch, n, 1);
+    const size_t nb1 = (kn + DIV_T - 1) / DIV_T;
+    DeepPowBases<1> pb;
     pb.b[0] = fe_one();
     pb.b[1] = c;
     pb.b[2] = fe_one();
     pb.b[3] = fe_inv(c);
-    hipLaunchKernelGGL(k_deep_pow_tables, dim3(cdiv(4 * (2048 + H), 256)), dim3(256), 0, st, pb, H, pw);
+    hipLaunchKernelGGL(k_deep_pow_tables<1>, dim3(cdiv(4 * (2048 + S.H), 256)), dim3(256), 0, st, pb, S.H, S.pw);
     BndPoly bp;
     memcpy(bp.cb, K.coeff_b, sizeof bp.cb);
     bp.bnd1 = K.bnd1;
     ZK_PROF(st, "boundary_poly", (16.0 * 12 + 32.0) * kn,
-            hipLaunchKernelGGL(k_bnd_div_g, dim3((unsigned)nb1), dim3(DIV_T), 0, st, tpolys, n, bp, pw, H, g1, g2, bs, k0,
-                               k0 + kn));
-    hipLaunchKernelGGL(k_deep_div_scan<2>, dim3(1), dim3(1024), 0, st, bs, (int)nb1, total);
+            hipLaunchKernelGGL(k_bnd_div_g, dim3((unsigned)nb1), dim3(DIV_T), 0, st, tpolys, n, bp, S.pw, S.H, S.g1, S.g2,
+                               S.bs, k0, k0 + kn));
+    hipLaunchKernelGGL(k_deep_div_scan<2>, dim3(1), dim3(1024), 0, st, S.bs, (int)nb1, total);
 }
 static void bnd_phase3(hipStream_t st, size_t n, fe c, fe *scratch, size_t k0, size_t kn, const fe *ext, fe *col0,
                        unsigned *flag) {
-    const size_t H = n / 2048 + 2, nb = (kn + DIV_CH - 1) / DIV_CH, nb1 = (kn + DIV_T - 1) / DIV_T;
-    fe *pw = scratch, *g1 = pw + 4 * (2048 + H), *g2 = g1 + n, *bs = g2 + 2 * n;
+    const DeepScratch S(scratch, n, 1);
+    const size_t nb = (kn + DIV_CH - 1) / DIV_CH, nb1 = (kn + DIV_T - 1) / DIV_T;
     ZK_PROF(st, "boundary_poly", 64.0 * kn,
-            hipLaunchKernelGGL(k_deep_div_q<true>, dim3((unsigned)nb), dim3(DIV_T), 0, st, g1, g2, bs, (int)nb1, k0 + kn,
-                               fe_one(), c, pw, H, col0, flag, k0, ext));
+            hipLaunchKernelGGL((k_deep_div_q<1, true>), dim3((unsigned)nb), dim3(DIV_T), 0, st, S.g1, S.g2, S.bs, (int)nb1,
+                               k0 + kn, fe_one(), c, S.pw, S.H, col0, 0, flag, k0, ext));
 }
 
 void boundary_poly_add(hipStream_t st, const fe *tpolys, int log_n, const AirConsts &K, fe c, fe *scratch, fe *col0,
@@ -2670,7 +2714,7 @@ void boundary_poly_add(hipStream_t st, const fe *tpolys, int log_n, const AirCon
 const fe *boundary_range_begin(hipStream_t st, const fe *tpolys, int log_n, const AirConsts &K, fe c, fe *scratch,
                                size_t k0, size_t kn) {
     const size_t n = (size_t)1 << log_n;
-    fe *total = deep_range_total(scratch, n, 2);
+    fe *total = DeepScratch(scratch, n, 1).total;
     bnd_tables_phase1(st, tpolys, n, K, c, scratch, k0, kn, total);
     return total;
 }
@@ -2679,195 +2723,31 @@ void boundary_range_end(hipStream_t st, int log_n, fe c, fe *scratch, size_t k0,
     bnd_phase3(st, (size_t)1 << log_n, c, scratch, k0, kn, ext, col0, flag);
 }
 
+template <class T>
 void deep_coeff_launch(hipStream_t st, const NttTables &Tn, const fe *tpolys, const fe *cpolys, int ccols, int log_n,
-                       int log_b, const void *deep_consts_dev, fe z, fe zg, const CosetTables &CT, fe *scratch,
+                       int log_b, const void *deep_consts_dev, T z, T zg, const CosetTables &CT, fe *scratch,
                        fe *ulde, fe *ntt_tmp, fe *out) {
+    constexpr int KX = ChalOf<T>::KX;
     const size_t n = (size_t)1 << log_n, B = (size_t)1 << log_b, N = n << log_b;
     const fe *Dk = deep_poly(st, tpolys, cpolys, ccols, log_n, deep_consts_dev, z, zg, scratch);
-    lde_cosets(st, Tn, CT, Dk, n, 0, 1, (int)B, ulde, ntt_tmp);
+    for (int plane = 0; plane < KX; plane++) lde_cosets(st, Tn, CT, Dk + plane * n, n, 0, 1, (int)B, ulde + plane * N, ntt_tmp);
     if (!out) return;  // FRI layer 0 is read coset-major from ulde
     unsigned pb2 = cdiv(N, 256);
     if (pb2 > 65536) pb2 = 65536;
-    ZK_PROF(st, "deep", 32.0 * N, hipLaunchKernelGGL(k_coset_to_natural, dim3(pb2), dim3(256), 0, st, ulde, log_n, log_b, out));
-}
-
-// ---- the same over E (FieldExtension::Quadratic): alpha_t, alpha_c, z, zg are E values; the
-// composition column c is the E polynomial P_c0 + X P_c1 (base columns 2c, 2c + 1).  D is E-valued:
-// its two base planes are LDE'd separately and written planar (a plane, then b plane).
-struct DeepPowBasesE {
-    fe2 b[4];
-};
-__global__ void k_deep_pow_tables_ext(DeepPowBasesE pb, size_t H, fe2 *out) {
-    const size_t per = 2048 + H;
-    const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (t >= 4 * per) return;
-    const size_t b = t / per, e = t % per;
-    out[t] = fe2_exp(pb.b[b], e < 2048 ? e : 2048 * (uint64_t)(e - 2048));
-}
-__device__ __forceinline__ fe2 pow_split2(const fe2 *lo, const fe2 *hi, size_t t) {
-    return fe2_mul(lo[t & 2047], hi[t >> 11]);
-}
-
-__global__ void __launch_bounds__(DIV_T) k_deep_div_g_ext(const fe *tpolys, const fe *cpolys, int ccols, size_t n,
-                                                         const DeepConstsE *D, const fe2 *pw, size_t H, fe2 *g1,
-                                                         fe2 *g2, fe *bs, size_t kbase, size_t kend) {
-    __shared__ fe red[DIV_T / 64];
-    const size_t per = 2048 + H;
-    const size_t k = kbase + blockIdx.x * (size_t)DIV_T + threadIdx.x;
-    fe2 v1 = fe2_zero(), v2 = fe2_zero();
-    if (k < kend) {
-        acc288 aA = acc288_zero(), aB = acc288_zero();
-#pragma unroll 4
-        for (int c = 0; c < 28; c++) {
-            const fe v = ld_fe(tpolys + (size_t)c * n + k);
-            acc288_madd(aA, D->alpha_t[c].a, v);
-            acc288_madd(aB, D->alpha_t[c].b, v);
-        }
-        acc288 hA = acc288_zero(), hB = acc288_zero();
-        for (int j = 0; j < ccols; j++) {
-            const fe h0 = ld_fe(cpolys + (size_t)(2 * j) * n + k), h1 = ld_fe(cpolys + (size_t)(2 * j + 1) * n + k);
-            const fe2 ac = D->alpha_c[j];
-            acc288_madd(hA, ac.a, h0);  // (ac.a + ac.b X)(h0 + h1 X) = (ac.a h0 + ac.b h1) + (ac.a h1 + ac.b (h0 + h1)) X
-            acc288_madd(hA, ac.b, h1);
-            acc288_madd(hB, ac.a, h1);
-            acc288_madd(hB, ac.b, fe_add(h0, h1));
-        }
-        const fe2 A = fe2{acc288_reduce(aA), acc288_reduce(aB)};
-        const fe2 S = fe2_add(A, fe2{acc288_reduce(hA), acc288_reduce(hB)});
-        v1 = fe2_mul(S, pow_split2(pw, pw + 2048, k));
-        v2 = fe2_mul(A, pow_split2(pw + per, pw + per + 2048, k));
-        g1[k] = v1;
-        g2[k] = v2;
-    }
-    const fe s0 = block_sum256(v1.a, red), s1 = block_sum256(v1.b, red), s2 = block_sum256(v2.a, red),
-             s3 = block_sum256(v2.b, red);
-    if (threadIdx.x == 0) {
-        bs[4 * blockIdx.x] = s0;
-        bs[4 * blockIdx.x + 1] = s1;
-        bs[4 * blockIdx.x + 2] = s2;
-        bs[4 * blockIdx.x + 3] = s3;
-    }
-}
-
-__global__ void __launch_bounds__(DIV_T) k_deep_div_q_ext(const fe2 *g1, const fe2 *g2, const fe *carry, int nb1,
-                                                         size_t n, fe2 z, fe2 zg, const fe2 *pw, size_t H, fe *Da,
-                                                         fe *Db, size_t kbase, const fe *ext) {
-    __shared__ fe2 t1[DIV_T], t2[DIV_T];
-    const size_t per = 2048 + H;
-    const fe2 *ilo = pw + 2 * per, *ihi = ilo + 2048, *jlo = pw + 3 * per, *jhi = jlo + 2048;
-    const size_t k0 = kbase + blockIdx.x * (size_t)DIV_CH + (size_t)threadIdx.x * DIV_E;
-    fe2 s1 = fe2_zero(), s2 = fe2_zero();
-    for (int e = 0; e < DIV_E; e++) {
-        const size_t k = k0 + e;
-        if (k < n) {
-            s1 = fe2_add(s1, g1[k]);
-            s2 = fe2_add(s2, g2[k]);
-        }
-    }
-    t1[threadIdx.x] = s1;
-    t2[threadIdx.x] = s2;
-    __syncthreads();
-    for (int d = 1; d < DIV_T; d <<= 1) {
-        fe2 x = t1[threadIdx.x], y = t2[threadIdx.x];
-        if (threadIdx.x + d < DIV_T) {
-            x = fe2_add(x, t1[threadIdx.x + d]);
-            y = fe2_add(y, t2[threadIdx.x + d]);
-        }
-        __syncthreads();
-        t1[threadIdx.x] = x;
-        t2[threadIdx.x] = y;
-        __syncthreads();
-    }
-    const int cb = min((int)blockIdx.x * (DIV_CH / DIV_T) + DIV_CH / DIV_T - 1, nb1 - 1);
-    fe2 r1 = fe2_add(fe2{carry[4 * cb], carry[4 * cb + 1]}, threadIdx.x + 1 < DIV_T ? t1[threadIdx.x + 1] : fe2_zero());
-    fe2 r2 = fe2_add(fe2{carry[4 * cb + 2], carry[4 * cb + 3]}, threadIdx.x + 1 < DIV_T ? t2[threadIdx.x + 1] : fe2_zero());
-    if (ext) {
-        r1 = fe2_add(r1, fe2{ext[0], ext[1]});
-        r2 = fe2_add(r2, fe2{ext[2], ext[3]});
-    }
-    fe2 pz = pow_split2(ilo, ihi, k0 + DIV_E), pg = pow_split2(jlo, jhi, k0 + DIV_E);
-    for (int e = DIV_E - 1; e >= 0; e--) {
-        const size_t k = k0 + e;
-        if (k < n) {
-            const fe2 d = fe2_add(fe2_mul(pz, r1), fe2_mul(pg, r2));
-            Da[k] = d.a;
-            Db[k] = d.b;
-            r1 = fe2_add(r1, g1[k]);
-            r2 = fe2_add(r2, g2[k]);
-        }
-        pz = fe2_mul(pz, z);
-        pg = fe2_mul(pg, zg);
-    }
-}
-
-// scratch layout (E): pw (4 E power tables) | g1 (n E) | g2 (n E) | Da (n) | Db (n) | block sums (4 per block)
-static void deep_tables_ext(hipStream_t st, size_t n, fe2 z, fe2 zg, fe *scratch) {
-    const size_t H = n / 2048 + 2;
-    DeepPowBasesE pb;
-    pb.b[0] = z;
-    pb.b[1] = zg;
-    pb.b[2] = fe2_inv(z);
-    pb.b[3] = fe2_inv(zg);
-    hipLaunchKernelGGL(k_deep_pow_tables_ext, dim3(cdiv(4 * (2048 + H), 256)), dim3(256), 0, st, pb, H, (fe2 *)scratch);
-}
-static void deep_phase1_ext(hipStream_t st, const fe *tpolys, const fe *cpolys, int ccols, size_t n,
-                            const DeepConstsE *D, fe *scratch, size_t k0, size_t kn, fe *total) {
-    const size_t H = n / 2048 + 2, nb1 = (kn + DIV_T - 1) / DIV_T;
-    fe2 *pw = (fe2 *)scratch, *g1 = pw + 4 * (2048 + H), *g2 = g1 + n;
-    fe *bs = (fe *)(g2 + n) + 2 * n;
-    ZK_PROF(st, "deep_combine", (16.0 * (28 + 2 * ccols) + 64.0) * kn,
-            hipLaunchKernelGGL(k_deep_div_g_ext, dim3((unsigned)nb1), dim3(DIV_T), 0, st, tpolys, cpolys, ccols, n, D, pw,
-                               H, g1, g2, bs, k0, k0 + kn));
-    hipLaunchKernelGGL(k_deep_div_scan<4>, dim3(1), dim3(1024), 0, st, bs, (int)nb1, total);
-}
-static void deep_phase3_ext(hipStream_t st, size_t n, fe2 z, fe2 zg, fe *scratch, size_t k0, size_t kn, const fe *ext) {
-    const size_t H = n / 2048 + 2, nb = (kn + DIV_CH - 1) / DIV_CH, nb1 = (kn + DIV_T - 1) / DIV_T;
-    fe2 *pw = (fe2 *)scratch, *g1 = pw + 4 * (2048 + H), *g2 = g1 + n;
-    fe *Da = (fe *)(g2 + n), *Db = Da + n, *bs = Db + n;
-    ZK_PROF(st, "deep_divide", 96.0 * kn,
-            hipLaunchKernelGGL(k_deep_div_q_ext, dim3((unsigned)nb), dim3(DIV_T), 0, st, g1, g2, bs, (int)nb1, k0 + kn, z, zg,
-                               pw, H, Da, Db, k0, ext));
-}
-const fe *deep_poly_ext(hipStream_t st, const fe *tpolys, const fe *cpolys, int ccols, int log_n,
-                        const void *deep_consts_dev, fe2 z, fe2 zg, fe *scratch) {
-    const size_t n = (size_t)1 << log_n, H = n / 2048 + 2;
-    deep_tables_ext(st, n, z, zg, scratch);
-    deep_phase1_ext(st, tpolys, cpolys, ccols, n, (const DeepConstsE *)deep_consts_dev, scratch, 0, n, nullptr);
-    deep_phase3_ext(st, n, z, zg, scratch, 0, n, nullptr);
-    return (fe *)((fe2 *)scratch + 4 * (2048 + H) + 2 * n);  // planes Da, Da + n
-}
-static fe *deep_range_total_ext(fe *scratch, size_t n) {
-    const size_t H = n / 2048 + 2;
-    return (fe *)((fe2 *)scratch + 4 * (2048 + H) + 2 * n) + 2 * n + 4 * ((n + DIV_T - 1) / DIV_T);
-}
-const fe *deep_range_begin_ext(hipStream_t st, const fe *tpolys, const fe *cpolys, int ccols, int log_n,
-                               const void *deep_consts_dev, fe2 z, fe2 zg, fe *scratch, size_t k0, size_t kn) {
-    const size_t n = (size_t)1 << log_n;
-    deep_tables_ext(st, n, z, zg, scratch);
-    fe *total = deep_range_total_ext(scratch, n);
-    deep_phase1_ext(st, tpolys, cpolys, ccols, n, (const DeepConstsE *)deep_consts_dev, scratch, k0, kn, total);
-    return total;
-}
-const fe *deep_range_end_ext(hipStream_t st, int log_n, fe2 z, fe2 zg, fe *scratch, size_t k0, size_t kn,
-                             const fe *ext) {
-    const size_t n = (size_t)1 << log_n, H = n / 2048 + 2;
-    deep_phase3_ext(st, n, z, zg, scratch, k0, kn, ext);
-    return (fe *)((fe2 *)scratch + 4 * (2048 + H) + 2 * n);
-}
-
-void deep_coeff_ext_launch(hipStream_t st, const NttTables &Tn, const fe *tpolys, const fe *cpolys, int ccols,
-                           int log_n, int log_b, const void *deep_consts_dev, fe2 z, fe2 zg, const CosetTables &CT,
-                           fe *scratch, fe *ulde, fe *ntt_tmp, fe *out) {
-    const size_t n = (size_t)1 << log_n, B = (size_t)1 << log_b, N = n << log_b;
-    const fe *Dk = deep_poly_ext(st, tpolys, cpolys, ccols, log_n, deep_consts_dev, z, zg, scratch);
-    for (int plane = 0; plane < 2; plane++) lde_cosets(st, Tn, CT, Dk + plane * n, n, 0, 1, (int)B, ulde + plane * N, ntt_tmp);
-    if (!out) return;
-    unsigned pb2 = cdiv(N, 256);
-    if (pb2 > 65536) pb2 = 65536;
-    for (int plane = 0; plane < 2; plane++)
+    for (int plane = 0; plane < KX; plane++)
         ZK_PROF(st, "deep", 32.0 * N,
                 hipLaunchKernelGGL(k_coset_to_natural, dim3(pb2), dim3(256), 0, st, ulde + plane * N, log_n, log_b, out + plane * N));
 }
+#define ZK_DEEP_INSTANCES(T)                                                                                           \
+    template const fe *deep_poly<T>(hipStream_t, const fe *, const fe *, int, int, const void *, T, T, fe *);          \
+    template const fe *deep_range_begin<T>(hipStream_t, const fe *, const fe *, int, int, const void *, T, T, fe *,    \
+                                           size_t, size_t);                                                            \
+    template const fe *deep_range_end<T>(hipStream_t, int, T, T, fe *, size_t, size_t, const fe *);                    \
+    template void deep_coeff_launch<T>(hipStream_t, const NttTables &, const fe *, const fe *, int, int, int,          \
+                                       const void *, T, T, const CosetTables &, fe *, fe *, fe *, fe *);
+ZK_DEEP_INSTANCES(fe)
+ZK_DEEP_INSTANCES(fe2)
+#undef ZK_DEEP_INSTANCES
 
 // ================================================================ FRI transcript on the device
 // DefaultRandomCoin<Blake3_256> for the FRI commit phase without a host round trip per layer:
@@ -2912,239 +2792,46 @@ void fri_coin_launch(hipStream_t st, uint32_t *seed_dev, const uint8_t *root_dev
 // V_m = sum_k v_k * zeta^(-k m), m < F: idft_small (fri_small.hpp)
 
 // One FRI fold: row r = [e(r + k*rows)] at x_r * zeta^k -> the degree-respecting projection at alpha:
-// sum_m V_m (alpha / x_r)^m / F, with x_r = offset * w_L^r.
-template <int F>
-__global__ void __launch_bounds__(256) k_fri_fold(const fe *layer, size_t L, const FoldConsts *Fc, const fe *wi_lo,
+// sum_m V_m (alpha / x_r)^m / F, with x_r = offset * w_L^r.  Over E the interpolation is F-linear, so each component
+// plane goes through idft_small; beta = alpha / x_r is alpha times a base element, and so is the final 1 / F.
+template <int KX, int F>
+__global__ void __launch_bounds__(256) k_fri_fold(const fe *layer, size_t L, const FoldConsts<KX> *Fc, const fe *wi_lo,
                                                   const fe *wi_hi, size_t wstride, FriLayout f, fe *next) {
+    typedef Chal<KX> X;
+    typedef typename X::T T;
     const size_t rows = L / F;
     for (size_t r = blockIdx.x * (size_t)blockDim.x + threadIdx.x; r < rows; r += (size_t)gridDim.x * blockDim.x) {
-        fe v[F];
-#pragma unroll
-        for (int k = 0; k < F; k++) v[k] = layer[fri_at(f, r + (size_t)k * rows)];
-        // beta = alpha / x_r, 1/x_r = offset^-1 * w_L^-r = offset^-1 * w_N^(-r*wstride)
-        const fe beta = fe_mul(Fc->alpha, fe_mul(Fc->inv_offset, pow_split(wi_lo, wi_hi, r * wstride)));
-        idft_small<F>(v, Fc->zinv);
-        fe acc = v[F - 1];
-#pragma unroll
-        for (int m = F - 2; m >= 0; m--) acc = fe_add(fe_mul(acc, beta), v[m]);
-        next[r] = fe_mul(acc, Fc->inv_fold);
-    }
-}
-
-void fri_fold_launch(hipStream_t st, const fe *layer, size_t L, int fold, const void *fold_consts_dev,
-                     const NttTables &TN, size_t wstride, fe *next, int lb) {
-    unsigned blocks = cdiv(L / fold, 256);
-    if (blocks > 65536) blocks = 65536;
-    const FoldConsts *F = (const FoldConsts *)fold_consts_dev;
-    const FriLayout fl = fri_layout(L, lb);
-#define ZK_FOLD(FF) ZK_PROF(st, "fri_fold", 16.0 * L + 16.0 * (L / fold), hipLaunchKernelGGL((k_fri_fold<FF>), dim3(blocks), dim3(256), 0, st, layer, L, F, TN.inv_lo, TN.inv_hi, wstride, fl, next))
-    switch (fold) {
-        case 2: ZK_FOLD(2); break;
-        case 4: ZK_FOLD(4); break;
-        case 8: ZK_FOLD(8); break;
-        default: ZK_FOLD(16); break;
-    }
-#undef ZK_FOLD
-}
-
-// ================================================================ FieldExtension::Quadratic (K5-K7 over E)
-// OOD over E points: the same wave layout as k_ood_eval, E-valued powers.
-__global__ void k_ood_tables_ext(fe2 z, fe2 zg, uint64_t chunk, int nw, fe2 *tab) {
-    const int t = blockIdx.x * blockDim.x + threadIdx.x;
-    if (t >= 128 + 2 * nw) return;
-    fe2 x;
-    uint64_t e;
-    if (t < 128) {
-        x = t < 64 ? z : zg;
-        e = t & 63;
-    } else {
-        const int u = t - 128;
-        x = u < nw ? z : zg;
-        e = chunk * (uint64_t)(u < nw ? u : u - nw);
-    }
-    tab[t] = fe2_exp(x, e);
-}
-
-// sum_e v_e y_e over E with base coefficients v: two lazy dot products (a and b components of y)
-template <int E>
-__device__ __forceinline__ fe2 dot_base_ext(const fe *v, const fe2 *y) {
-    acc288 aa = acc288_zero(), ab = acc288_zero();
-#pragma unroll
-    for (int e = 0; e < E; e++) {
-        const fe2 w = y[e];
-        acc288_madd(aa, v[e], w.a);
-        acc288_madd(ab, v[e], w.b);
-    }
-    return fe2{acc288_reduce(aa), acc288_reduce(ab)};
-}
-
-template <int E>
-__global__ void __launch_bounds__(256) k_ood_eval_ext(const fe *tpolys, int W, const fe *cpolys, int C, size_t n,
-                                                      const fe2 *tab, int nw, int w0, int w1, fe *partials) {
-    const int gw = w0 + (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);  // waves [w0, w1) of nw
-    const int lane = threadIdx.x & 63;
-    const int np = 2 * W + C;
-    const int tgroups = (W + OOD_GROUP - 1) / OOD_GROUP;
-    const int g = blockIdx.y;
-    const bool comp = g >= tgroups;
-    const int p0 = comp ? 0 : g * OOD_GROUP;
-    const int p1 = comp ? C : min(W, p0 + OOD_GROUP);
-    const size_t base = (size_t)gw * 64 * E + lane;
-    // powers (x^64)^e in LDS: the lane's strided sum is a base x E dot product (see k_ood_eval)
-    __shared__ fe2 Y[2][E];
-    if (threadIdx.x < 2 * E) {
-        const int which = threadIdx.x / E, e = threadIdx.x % E;
-        const fe2 y = which ? fe2_mul(tab[127], tab[65]) : fe2_mul(tab[63], tab[1]);  // x^64
-        Y[which][e] = fe2_exp(y, (uint64_t)e);
-    }
-    __syncthreads();
-    if (gw >= w1) return;
-    const fe2 wz = fe2_mul(tab[lane], tab[128 + gw]);
-    const fe2 wzg = comp ? fe2_zero() : fe2_mul(tab[64 + lane], tab[128 + nw + gw]);
-    for (int p = p0; p < p1; p++) {
-        const fe *c = (comp ? cpolys : tpolys) + (size_t)p * n;
-        fe v[E];
-#pragma unroll
-        for (int e = 0; e < E; e++) {
-            const size_t k = base + 64 * (size_t)e;
-            v[e] = k < n ? c[k] : fe_zero();
-        }
-        const fe2 hz = fe2_mul(dot_base_ext<E>(v, Y[0]), wz);
-        const fe sa = wave_sum(hz.a), sb = wave_sum(hz.b);
-        const int slot = comp ? 2 * W + p : p;
-        if (lane == 0) {
-            partials[(size_t)slot * nw + gw] = sa;
-            partials[(size_t)(np + slot) * nw + gw] = sb;
-        }
-        if (!comp) {
-            const fe2 hg = fe2_mul(dot_base_ext<E>(v, Y[1]), wzg);
-            const fe ga = wave_sum(hg.a), gb = wave_sum(hg.b);
-            if (lane == 0) {
-                partials[(size_t)(W + p) * nw + gw] = ga;
-                partials[(size_t)(np + W + p) * nw + gw] = gb;
-            }
-        }
-    }
-}
-
-void ood_eval_ext(hipStream_t st, const fe *tpolys, int W, const fe *cpolys, int C, int log_n, fe2 z, fe2 zg,
-                  fe *tab, fe *partials, fe *out, int rank, int G) {
-    const size_t n = (size_t)1 << log_n;
-    const int E = n >= 1024 ? 16 : std::max<int>(1, (int)(n / 64));
-    const int nw = (int)((n + 64 * E - 1) / (64 * E));
-    const int w0 = (int)((int64_t)nw * rank / G), w1 = (int)((int64_t)nw * (rank + 1) / G);
-    fe2 *t2 = reinterpret_cast<fe2 *>(tab);
-    hipLaunchKernelGGL(k_ood_tables_ext, dim3(cdiv(128 + 2 * nw, 256)), dim3(256), 0, st, z, zg, (uint64_t)64 * E, nw, t2);
-    const dim3 grid(std::max(1u, cdiv(w1 - w0, 4)), (W + OOD_GROUP - 1) / OOD_GROUP + 1);
-#define ZK_OOD(EE) hipLaunchKernelGGL((k_ood_eval_ext<EE>), grid, dim3(256), 0, st, tpolys, W, cpolys, C, n, t2, nw, w0, w1, partials)
-    const double bytes = 16.0 * (W + C) * (double)n * (w1 - w0) / nw;
-    switch (E) {
-        case 16: ZK_PROF(st, "ood_eval_ext", bytes, ZK_OOD(16)); break;
-        case 8: ZK_PROF(st, "ood_eval_ext", bytes, ZK_OOD(8)); break;
-        case 4: ZK_PROF(st, "ood_eval_ext", bytes, ZK_OOD(4)); break;
-        case 2: ZK_PROF(st, "ood_eval_ext", bytes, ZK_OOD(2)); break;
-        default: ZK_PROF(st, "ood_eval_ext", bytes, ZK_OOD(1)); break;
-    }
-#undef ZK_OOD
-    sum_partials(st, partials, 2 * (2 * W + C), nw, out, w0, w1);
-}
-
-// 1 / (N(x - z) N(x - zg)): N(x - z) = (x - z.a)(x - z.a - z.b) - z.b^2 (the norm of x - z, X^2 = X + 1)
-__device__ __forceinline__ fe norm_pair_denominator(const fe *xr, const fe *wlo, const fe *whi, size_t i, int log_n,
-                                                    fe2 z, fe2 zg, fe zb2, fe zgb2) {
-    const fe x = fe_mul(xr[i >> log_n], pow_split(wlo, whi, i & (((size_t)1 << log_n) - 1)));
-    const fe xa = fe_sub(x, z.a), ga = fe_sub(x, zg.a);
-    const fe d1 = fe_sub(fe_mul(xa, fe_sub(xa, z.b)), zb2);
-    const fe d2 = fe_sub(fe_mul(ga, fe_sub(ga, zg.b)), zgb2);
-    return fe_mul(d1, d2);
-}
-
-__global__ void __launch_bounds__(256) k_batch_inv_norm_pairs(const fe *xr, int log_b, int log_n, const fe *wlo,
-                                                              const fe *whi, fe2 z, fe2 zg, fe zb2, fe zgb2, fe *out,
-                                                              size_t total_threads) {
-    const size_t N = (size_t)1 << (log_n + log_b);
-    const size_t T = total_threads;
-    const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (t >= T) return;
-    fe acc = fe_one();
-#pragma unroll 4
-    for (int k = 0; k < INV_K; k++) {
-        const size_t i = t + (size_t)k * T;
-        if (i < N) {
-            acc = fe_mul(acc, norm_pair_denominator(xr, wlo, whi, i, log_n, z, zg, zb2, zgb2));
-            out[i] = acc;
-        }
-    }
-    fe inv = fe_inv(acc);
-#pragma unroll 4
-    for (int k = INV_K - 1; k >= 0; k--) {
-        const size_t i = t + (size_t)k * T;
-        if (i >= N) continue;
-        const fe d = norm_pair_denominator(xr, wlo, whi, i, log_n, z, zg, zb2, zgb2);
-        out[i] = k > 0 ? fe_mul(inv, out[i - T]) : inv;
-        inv = fe_mul(inv, d);
-    }
-}
-
-void batch_inv_norm_pairs(hipStream_t st, const NttTables &Tn, const fe *xr, int log_b, int log_n, fe2 z, fe2 zg,
-                          fe *out) {
-    const size_t N = (size_t)1 << (log_n + log_b);
-    const size_t threads = (N + INV_K - 1) / INV_K;
-    const fe zb2 = fe_mul(z.b, z.b), zgb2 = fe_mul(zg.b, zg.b);
-    ZK_PROF(st, "batch_inv_ext", 16.0 * N, hipLaunchKernelGGL(k_batch_inv_norm_pairs, dim3(cdiv(threads, 256)), dim3(256), 0, st, xr,
-                                                    log_b, log_n, Tn.fwd_lo, Tn.fwd_hi, z, zg, zb2, zgb2, out, threads));
-}
-
-// FRI row r over E: [e(r + k rows)]_k, each value hashed as (a, b)
-__global__ void __launch_bounds__(256) k_hash_fri_rows_ext(const fe *layer, size_t L, int fold, FriLayout f, uint8_t *leaves) {
-    const size_t rows = L / fold;
-    for (size_t r = blockIdx.x * (size_t)blockDim.x + threadIdx.x; r < rows; r += (size_t)gridDim.x * blockDim.x) {
-        uint32_t h[8];
-        b3::hash_elements(2 * fold, [&](int t) { return layer[(size_t)(t & 1) * L + fri_at(f, r + (size_t)(t >> 1) * rows)]; }, h);
-        store_digest(leaves + 32 * r, h);
-    }
-}
-
-void commit_fri_layer_ext(hipStream_t st, const fe *layer, size_t L, int fold, uint8_t *leaves, uint8_t *nodes, int lb) {
-    const size_t rows = L / fold;
-    const FriLayout f = fri_layout(L, lb);
-    ZK_PROF(st, "hash_fri_rows_ext", 32.0 * L + 32.0 * rows, hipLaunchKernelGGL(k_hash_fri_rows_ext, dim3(cdiv(rows, 256)), dim3(256), 0, st, layer, L, fold, f, leaves));
-    merkle_tree(st, leaves, rows, nodes);
-}
-
-// FRI fold over E: the interpolation is F-linear, so each component goes through idft_small and the
-// resulting E coefficients are evaluated at beta = alpha / x_r by an E Horner.
-template <int F>
-__global__ void __launch_bounds__(256) k_fri_fold_ext(const fe *layer, size_t L, const FoldConstsE *Fc, const fe *wi_lo,
-                                                      const fe *wi_hi, size_t wstride, FriLayout f, fe *next) {
-    const size_t rows = L / F;
-    for (size_t r = blockIdx.x * (size_t)blockDim.x + threadIdx.x; r < rows; r += (size_t)gridDim.x * blockDim.x) {
-        fe va[F], vb[F];
+        fe va[F], vb[KX == 2 ? F : 1];  // the component planes
 #pragma unroll
         for (int k = 0; k < F; k++) {
             const size_t at = fri_at(f, r + (size_t)k * rows);
             va[k] = layer[at];
-            vb[k] = layer[L + at];
+            if constexpr (KX == 2) vb[k] = layer[L + at];
         }
-        const fe2 beta = fe2_mulb(Fc->alpha, fe_mul(Fc->inv_offset, pow_split(wi_lo, wi_hi, r * wstride)));
+        // beta = alpha / x_r, 1/x_r = offset^-1 * w_L^-r = offset^-1 * w_N^(-r*wstride)
+        const T beta = X::mulb(Fc->alpha, fe_mul(Fc->inv_offset, pow_split(wi_lo, wi_hi, r * wstride)));
         idft_small<F>(va, Fc->zinv);
-        idft_small<F>(vb, Fc->zinv);
-        fe2 acc = fe2{va[F - 1], vb[F - 1]};
+        if constexpr (KX == 2) idft_small<F>(vb, Fc->zinv);
+        auto V = [&](int m) -> T {
+            if constexpr (KX == 2) return fe2{va[m], vb[m]};
+            else return va[m];
+        };
+        T acc = V(F - 1);
 #pragma unroll
-        for (int m = F - 2; m >= 0; m--) acc = fe2_add(fe2_mul(acc, beta), fe2{va[m], vb[m]});
-        acc = fe2_mulb(acc, Fc->inv_fold);
-        next[r] = acc.a;
-        next[rows + r] = acc.b;
+        for (int m = F - 2; m >= 0; m--) acc = X::add(X::mul(acc, beta), V(m));
+        X::st(next + r, rows, X::mulb(acc, Fc->inv_fold));
     }
 }
 
-void fri_fold_ext_launch(hipStream_t st, const fe *layer, size_t L, int fold, const void *fold_consts_dev,
-                         const NttTables &TN, size_t wstride, fe *next, int lb) {
+template <int KX>
+static void fri_fold_kx(hipStream_t st, const fe *layer, size_t L, int fold, const void *fold_consts_dev,
+                        const NttTables &TN, size_t wstride, fe *next, int lb) {
     unsigned blocks = cdiv(L / fold, 256);
     if (blocks > 65536) blocks = 65536;
-    const FoldConstsE *F = (const FoldConstsE *)fold_consts_dev;
+    const FoldConsts<KX> *F = (const FoldConsts<KX> *)fold_consts_dev;
     const FriLayout fl = fri_layout(L, lb);
-#define ZK_FOLD(FF) ZK_PROF(st, "fri_fold_ext", 32.0 * L + 32.0 * (L / fold), hipLaunchKernelGGL((k_fri_fold_ext<FF>), dim3(blocks), dim3(256), 0, st, layer, L, F, TN.inv_lo, TN.inv_hi, wstride, fl, next))
+    const char *name = KX == 1 ? "fri_fold" : "fri_fold_ext";
+#define ZK_FOLD(FF) ZK_PROF(st, name, KX * (16.0 * L + 16.0 * (L / fold)), hipLaunchKernelGGL((k_fri_fold<KX, FF>), dim3(blocks), dim3(256), 0, st, layer, L, F, TN.inv_lo, TN.inv_hi, wstride, fl, next))
     switch (fold) {
         case 2: ZK_FOLD(2); break;
         case 4: ZK_FOLD(4); break;
@@ -3153,14 +2840,13 @@ void fri_fold_ext_launch(hipStream_t st, const fe *layer, size_t L, int fold, co
     }
 #undef ZK_FOLD
 }
-
-// ================================================================ elementwise helpers
-__global__ void k_coset_major_to_natural(const fe *src, int log_n, int log_b, fe *dst) {
-    size_t N = (size_t)1 << (log_n + log_b), n = (size_t)1 << log_n, B = (size_t)1 << log_b;
-    for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < N; i += (size_t)gridDim.x * blockDim.x)
-        dst[i] = src[(i & (B - 1)) * n + (i >> log_b)];
+void fri_fold_launch(hipStream_t st, int KX, const fe *layer, size_t L, int fold, const void *fold_consts_dev,
+                     const NttTables &TN, size_t wstride, fe *next, int lb) {
+    if (KX == 1) fri_fold_kx<1>(st, layer, L, fold, fold_consts_dev, TN, wstride, next, lb);
+    else fri_fold_kx<2>(st, layer, L, fold, fold_consts_dev, TN, wstride, next, lb);
 }
 
+// ================================================================ elementwise helpers
 __global__ void k_gather_chunks(const uint64_t *addr, size_t k, fe *out) {
     const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (t < k) out[t] = *reinterpret_cast<const fe *>((uintptr_t)addr[t]);
@@ -3205,7 +2891,7 @@ void coset_major_to_natural(hipStream_t st, const fe *src, int log_n, int log_b,
     size_t N = (size_t)1 << (log_n + log_b);
     unsigned blocks = cdiv(N, 256);
     if (blocks > 65536) blocks = 65536;
-    hipLaunchKernelGGL(k_coset_major_to_natural, dim3(blocks), dim3(256), 0, st, src, log_n, log_b, dst);
+    hipLaunchKernelGGL(k_coset_to_natural, dim3(blocks), dim3(256), 0, st, src, log_n, log_b, dst);
 }
 
 }  // namespace zk

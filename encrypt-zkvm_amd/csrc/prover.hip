@@ -363,7 +363,7 @@ static int create_prover(int device, size_t max_n, uint32_t max_b, int world, zk
     ZK_CHECK_HIP(A.alloc(&p->clde, (size_t)8 * Nl));
     ZK_CHECK_HIP(A.alloc(&p->deep, Nl));
     if (!world) ZK_CHECK_HIP(A.alloc(&p->ulde, N));  // the single path's DEEP LDE
-    ZK_CHECK_HIP(A.alloc(&p->dscratch, 4 * (2048 + n / 2048 + 2) + 3 * n + 2 * (n / 256 + 1)));
+    ZK_CHECK_HIP(A.alloc(&p->dscratch, DeepScratch::size(n, 1)));
     // FRI layers: sum over layers of L/fold values and 2*L/fold digests; worst case fold = 2
     ZK_CHECK_HIP(A.alloc(&p->fri, N + 16));
     ZK_CHECK_HIP(A.alloc(&p->leaves, 32 * Nl));
@@ -386,8 +386,8 @@ static int create_prover(int device, size_t max_n, uint32_t max_b, int world, zk
     ZK_CHECK_HIP(hipHostMalloc((void **)&p->h_gather_out, ZK_GATHER_CAP * sizeof(fe), hipHostMallocDefault));
     ZK_CHECK_HIP(A.alloc(&p->flag, 4));
     ZK_CHECK_HIP(A.alloc((uint8_t **)&p->air_consts, sizeof(AirConsts)));
-    ZK_CHECK_HIP(A.alloc((uint8_t **)&p->deep_consts, sizeof(DeepConsts)));
-    ZK_CHECK_HIP(A.alloc((uint8_t **)&p->fold_consts, sizeof(FoldConsts)));
+    ZK_CHECK_HIP(A.alloc((uint8_t **)&p->deep_consts, sizeof(DeepConsts<1>)));
+    ZK_CHECK_HIP(A.alloc((uint8_t **)&p->fold_consts, sizeof(FoldConsts<1>)));
     ZK_CHECK_HIP(A.alloc(&p->fri_seed, 32));
     ZK_CHECK_HIP(A.alloc(&p->fri_alphas, 2 * ZK_MAX_FRI_LAYERS));
     // trace validation: the report and the raw periodic table (the Rescue constants, as the AIR lists them)
@@ -881,66 +881,83 @@ static void air_static_consts(const zk_pub_inputs *pub, size_t n, AirConsts &K) 
     set_bnd1(K);
 }
 
-void zk::draw_air_consts(Coin &coin, const zk_pub_inputs *pub, size_t n, AirConsts &K, zk_record &R) {
-    memset(&K, 0, sizeof K);
-    for (int k = 0; k < NUM_TCONS; k++) fe_to_bytes(K.coeff_t[k] = coin.draw(), R.coeff_t[k]);
-    for (int k = 0; k < NUM_ASSERTS; k++) fe_to_bytes(K.coeff_b[k] = coin.draw(), R.coeff_b[k]);
-    air_static_consts(pub, n, K);
-}
-
-void zk::draw_air_consts_ext(Coin &coin, const zk_pub_inputs *pub, size_t n, AirConsts &Ka, AirConsts &Kb,
-                             zk_record &R) {
-    memset(&Ka, 0, sizeof Ka);
+// K[j]: the constants with component j of every coefficient (KX planes; the record keeps the a components)
+void zk::draw_air_consts(Coin &coin, const zk_pub_inputs *pub, size_t n, int KX, AirConsts *K, zk_record &R) {
+    memset(K, 0, KX * sizeof K[0]);
     for (int k = 0; k < NUM_TCONS; k++) {
-        const fe2 v = coin.draw_ext(2);
-        Ka.coeff_t[k] = v.a;
-        Kb.coeff_t[k] = v.b;
+        const fe2 v = coin.draw_ext(KX);
+        for (int j = 0; j < KX; j++) K[j].coeff_t[k] = j ? v.b : v.a;
         fe_to_bytes(v.a, R.coeff_t[k]);
     }
     for (int k = 0; k < NUM_ASSERTS; k++) {
-        const fe2 v = coin.draw_ext(2);
-        Ka.coeff_b[k] = v.a;
-        Kb.coeff_b[k] = v.b;
+        const fe2 v = coin.draw_ext(KX);
+        for (int j = 0; j < KX; j++) K[j].coeff_b[k] = j ? v.b : v.a;
         fe_to_bytes(v.a, R.coeff_b[k]);
     }
-    air_static_consts(pub, n, Ka);
-    const AirConsts tmp = Kb;
-    Kb = Ka;
-    memcpy(Kb.coeff_t, tmp.coeff_t, sizeof Kb.coeff_t);
-    memcpy(Kb.coeff_b, tmp.coeff_b, sizeof Kb.coeff_b);
-    set_bnd1(Kb);
+    air_static_consts(pub, n, K[0]);
+    if (KX == 2) {  // the b plane: the same constants around its own coefficients
+        const AirConsts b = K[1];
+        K[1] = K[0];
+        memcpy(K[1].coeff_t, b.coeff_t, sizeof b.coeff_t);
+        memcpy(K[1].coeff_b, b.coeff_b, sizeof b.coeff_b);
+        set_bnd1(K[1]);
+    }
 }
 
-void zk::ood_reseed(Coin &coin, const fe *h, int C, zk_record &R) {
-    for (int c = 0; c < W; c++) {
-        fe_to_bytes(h[c], R.ood_trace_z[c]);
-        fe_to_bytes(h[W + c], R.ood_trace_zg[c]);
+// hv = ood_eval's output (KX planes of np = 2W + C KX values): T(z), T(zg) and the C KX base composition columns at z.
+// Builds the frame e = T(z) ++ T(zg) ++ H(z) (over E: H_c = P_2c + X P_2c+1), its flattened form h (the
+// serialization order, KX elements per value), records the a components, reseeds the coin [P7, P15].
+void zk::ood_reseed(Coin &coin, int KX, const std::vector<fe> &hv, int C, zk_record &R, std::vector<fe2> &e,
+                    std::vector<fe> &h) {
+    const int np = 2 * W + C * KX;
+    auto val = [&](int s) { return fe2{hv[s], KX == 2 ? hv[np + s] : fe_zero()}; };
+    e.assign(2 * W + C, fe2_zero());
+    for (int c = 0; c < 2 * W; c++) e[c] = val(c);
+    for (int c = 0; c < C; c++)
+        e[2 * W + c] = KX == 1 ? val(2 * W + c) : fe2_add(val(2 * W + 2 * c), fe2_mulX(val(2 * W + 2 * c + 1)));
+    h.assign(KX * e.size(), fe_zero());
+    for (size_t i = 0; i < e.size(); i++) {
+        h[KX * i] = e[i].a;
+        if (KX == 2) h[2 * i + 1] = e[i].b;
     }
-    for (int j = 0; j < C; j++) fe_to_bytes(h[2 * W + j], R.ood_constraints[j]);
+    for (int c = 0; c < W; c++) {
+        fe_to_bytes(e[c].a, R.ood_trace_z[c]);
+        fe_to_bytes(e[W + c].a, R.ood_trace_zg[c]);
+    }
+    for (int j = 0; j < C; j++) fe_to_bytes(e[2 * W + j].a, R.ood_constraints[j]);
     uint8_t d[32];
-    hash_elems(h, 2 * W, d);  // T(z) || T(zg)
+    hash_elems(h.data(), 2 * W * KX, d);  // T(z) || T(zg)
     coin.reseed(d);
-    hash_elems(h + 2 * W, C, d);
+    hash_elems(h.data() + 2 * W * KX, C * KX, d);
     coin.reseed(d);
 }
 
-DeepConsts zk::draw_deep_consts(Coin &coin, const fe *h, int C, fe z, fe zg, zk_record &R) {
-    DeepConsts D;
+template <int KX>
+DeepConsts<KX> zk::draw_deep_consts(Coin &coin, const std::vector<fe2> &e, int C, typename Chal<KX>::T z,
+                                    typename Chal<KX>::T zg, zk_record &R) {
+    typedef Chal<KX> X;
+    DeepConsts<KX> D;
     memset(&D, 0, sizeof D);
-    for (int c = 0; c < W; c++) fe_to_bytes(D.alpha_t[c] = coin.draw(), R.deep_t[c]);
-    for (int j = 0; j < C; j++) fe_to_bytes(D.alpha_c[j] = coin.draw(), R.deep_c[j]);
-    fe k1 = fe_zero(), k2 = fe_zero();
+    typename X::T k1 = X::zero(), k2 = X::zero();
     for (int c = 0; c < W; c++) {
-        k1 = fe_add(k1, fe_mul(D.alpha_t[c], h[c]));
-        k2 = fe_add(k2, fe_mul(D.alpha_t[c], h[W + c]));
+        D.alpha_t[c] = X::make(coin.draw_ext(KX));
+        fe_to_bytes(X::comp(D.alpha_t[c], 0), R.deep_t[c]);
+        k1 = X::add(k1, X::mul(D.alpha_t[c], X::make(e[c])));
+        k2 = X::add(k2, X::mul(D.alpha_t[c], X::make(e[W + c])));
     }
-    for (int j = 0; j < C; j++) k1 = fe_add(k1, fe_mul(D.alpha_c[j], h[2 * W + j]));
+    for (int j = 0; j < C; j++) {
+        D.alpha_c[j] = X::make(coin.draw_ext(KX));
+        fe_to_bytes(X::comp(D.alpha_c[j], 0), R.deep_c[j]);
+        k1 = X::add(k1, X::mul(D.alpha_c[j], X::make(e[2 * W + j])));
+    }
     D.k1 = k1;
     D.k2 = k2;
     D.z = z;
     D.zg = zg;
     return D;
 }
+template DeepConsts<1> zk::draw_deep_consts<1>(Coin &, const std::vector<fe2> &, int, fe, fe, zk_record &);
+template DeepConsts<2> zk::draw_deep_consts<2>(Coin &, const std::vector<fe2> &, int, fe2, fe2, zk_record &);
 
 int zk::fri_num_layers(size_t N, const zk_options *opt) {
     const size_t max_rem = (size_t)(opt->fri_rem_max_deg + 1) * opt->blowup;
@@ -949,114 +966,38 @@ int zk::fri_num_layers(size_t N, const zk_options *opt) {
     return nl;
 }
 
-FoldConsts zk::fold_consts(fe alpha, uint32_t fold) {
-    FoldConsts F;
+template <int KX>
+FoldConsts<KX> zk::fold_consts(fe2 alpha, uint32_t fold) {
+    FoldConsts<KX> F;
     memset(&F, 0, sizeof F);
     const fe zeta_inv = h_inv(h_root_of_unity(ilog2(fold)));
     F.zinv[0] = fe_one();
     for (uint32_t t = 1; t < 16; t++) F.zinv[t] = t < fold ? fe_mul(F.zinv[t - 1], zeta_inv) : fe_zero();
-    F.alpha = alpha;
+    F.alpha = Chal<KX>::make(alpha);
     F.inv_offset = h_inv(fe_make(3));
     F.inv_fold = h_inv(fe_make(fold));
     return F;
 }
+template FoldConsts<1> zk::fold_consts<1>(fe2, uint32_t);
+template FoldConsts<2> zk::fold_consts<2>(fe2, uint32_t);
 
-int zk::remainder_step(std::vector<fe> &rv, uint32_t B, Coin &coin, zk_record &R, unsigned &degree_flag) {
-    const size_t L = rv.size();
-    h_interp_coset3_cached(rv);
-    const size_t rl = L / B;
-    for (size_t k = rl; k < L; k++)
-        if (!fe_is_zero(rv[k])) degree_flag = 1;
+// rv: the last layer, KX planes of L values each, natural order over 3 * <w_L>
+int zk::remainder_step(int KX, const std::vector<fe> &rv, uint32_t B, Coin &coin, zk_record &R, unsigned &degree_flag,
+                       std::vector<fe> &rem_flat) {
+    const size_t L = rv.size() / KX, rl = L / B;
+    std::vector<fe> v[2];
+    for (int j = 0; j < KX; j++) {
+        v[j].assign(rv.begin() + j * L, rv.begin() + (j + 1) * L);
+        h_interp_coset3_cached(v[j]);
+        for (size_t k = rl; k < L; k++)
+            if (!fe_is_zero(v[j][k])) degree_flag = 1;
+    }
     if (rl > ZK_MAX_REMAINDER) ZK_FAIL(ZK_ERR_INVALID_ARG, "remainder too large");
-    R.remainder_len = (uint32_t)rl;
-    for (size_t k = 0; k < rl; k++) fe_to_bytes(rv[k], R.remainder[k]);
-    hash_elems(rv.data(), rl, R.remainder_commitment);
-    coin.reseed(R.remainder_commitment);
-    return ZK_OK;
-}
-
-// ---- FieldExtension::Quadratic host steps (shared by the single-GPU and sharded paths)
-// hv = ood_eval_ext output (2 planes of np = 2W + C*2 values): E values of T(z), T(zg) and of the 2C base
-// composition columns at z.  Builds the E frame e = T(z) ++ T(zg) ++ H(z) (H_c = P_c0 + X P_c1), its
-// flattened form h (the serialization order), records the a components, reseeds the coin [P7, P15].
-void zk::ood_reseed_ext(Coin &coin, const std::vector<fe> &hv, int C, zk_record &R, std::vector<fe2> &e,
-                        std::vector<fe> &h) {
-    const int np = 2 * W + 2 * C;
-    e.assign(2 * W + C, fe2_zero());
-    for (int c = 0; c < 2 * W; c++) e[c] = fe2{hv[c], hv[np + c]};
-    for (int c = 0; c < C; c++) {
-        const int s0 = 2 * W + 2 * c;
-        e[2 * W + c] = fe2_add(fe2{hv[s0], hv[np + s0]}, fe2_mulX(fe2{hv[s0 + 1], hv[np + s0 + 1]}));
-    }
-    h.assign(2 * e.size(), fe_zero());
-    for (size_t i = 0; i < e.size(); i++) {
-        h[2 * i] = e[i].a;
-        h[2 * i + 1] = e[i].b;
-    }
-    for (int c = 0; c < W; c++) {
-        fe_to_bytes(e[c].a, R.ood_trace_z[c]);
-        fe_to_bytes(e[W + c].a, R.ood_trace_zg[c]);
-    }
-    for (int j = 0; j < C; j++) fe_to_bytes(e[2 * W + j].a, R.ood_constraints[j]);
-    uint8_t d[32];
-    hash_elems(h.data(), 4 * W, d);
-    coin.reseed(d);
-    hash_elems(h.data() + 4 * W, 2 * C, d);
-    coin.reseed(d);
-}
-
-DeepConstsE zk::draw_deep_consts_ext(Coin &coin, const std::vector<fe2> &e, int C, fe2 z, fe2 zg, zk_record &R) {
-    DeepConstsE D;
-    memset(&D, 0, sizeof D);
-    fe2 k1 = fe2_zero(), k2 = fe2_zero();
-    for (int c = 0; c < W; c++) {
-        D.alpha_t[c] = coin.draw_ext(2);
-        fe_to_bytes(D.alpha_t[c].a, R.deep_t[c]);
-        k1 = fe2_add(k1, fe2_mul(D.alpha_t[c], e[c]));
-        k2 = fe2_add(k2, fe2_mul(D.alpha_t[c], e[W + c]));
-    }
-    for (int j = 0; j < C; j++) {
-        D.alpha_c[j] = coin.draw_ext(2);
-        fe_to_bytes(D.alpha_c[j].a, R.deep_c[j]);
-        k1 = fe2_add(k1, fe2_mul(D.alpha_c[j], e[2 * W + j]));
-    }
-    D.k1 = k1;
-    D.k2 = k2;
-    D.z = z;
-    D.zg = zg;
-    D.zb2 = fe_mul(z.b, z.b);
-    D.zgb2 = fe_mul(zg.b, zg.b);
-    return D;
-}
-
-FoldConstsE zk::fold_consts_ext(fe2 alpha, uint32_t fold) {
-    const FoldConsts F1 = fold_consts(fe_zero(), fold);
-    FoldConstsE F;
-    memset(&F, 0, sizeof F);
-    memcpy(F.zinv, F1.zinv, sizeof F.zinv);
-    F.alpha = alpha;
-    F.inv_offset = F1.inv_offset;
-    F.inv_fold = F1.inv_fold;
-    return F;
-}
-
-// rv: the last layer, planar (a plane then b plane, L values each, natural order over 3 * <w_L>)
-int zk::remainder_step_ext(const std::vector<fe> &rv, uint32_t B, Coin &coin, zk_record &R, unsigned &degree_flag,
-                           std::vector<fe> &rem_flat) {
-    const size_t L = rv.size() / 2;
-    std::vector<fe> va(rv.begin(), rv.begin() + L), vb(rv.begin() + L, rv.end());
-    h_interp_coset3_cached(va);
-    h_interp_coset3_cached(vb);
-    const size_t rl = L / B;
-    if (rl > ZK_MAX_REMAINDER) ZK_FAIL(ZK_ERR_INVALID_ARG, "remainder too large");
-    for (size_t k = rl; k < L; k++)
-        if (!fe_is_zero(va[k]) || !fe_is_zero(vb[k])) degree_flag = 1;
     R.remainder_len = (uint32_t)rl;
     rem_flat.clear();
     for (size_t k = 0; k < rl; k++) {
-        fe_to_bytes(va[k], R.remainder[k]);
-        rem_flat.push_back(va[k]);
-        rem_flat.push_back(vb[k]);
+        fe_to_bytes(v[0][k], R.remainder[k]);
+        for (int j = 0; j < KX; j++) rem_flat.push_back(v[j][k]);
     }
     hash_elems(rem_flat.data(), rem_flat.size(), R.remainder_commitment);
     coin.reseed(R.remainder_commitment);
@@ -1256,10 +1197,10 @@ int zk::ensure_ext(zk_prover *p) {
     ZK_CHECK_HIP(A.alloc(&p->x_partials, (size_t)2 * (2 * ZK_MAX_COLS + ZK_MAX_CCOLS) * ood_waves(n)));
     ZK_CHECK_HIP(A.alloc(&p->x_tab, (size_t)2 * (128 + 2 * ood_waves(n))));
     ZK_CHECK_HIP(A.alloc((uint8_t **)&p->x_air, 2 * sizeof(AirConsts)));
-    ZK_CHECK_HIP(A.alloc((uint8_t **)&p->x_deep_consts, sizeof(DeepConstsE)));
-    ZK_CHECK_HIP(A.alloc((uint8_t **)&p->x_fold_consts, sizeof(FoldConstsE)));
+    ZK_CHECK_HIP(A.alloc((uint8_t **)&p->x_deep_consts, sizeof(DeepConsts<2>)));
+    ZK_CHECK_HIP(A.alloc((uint8_t **)&p->x_fold_consts, sizeof(FoldConsts<2>)));
     if (!p->shard_world) ZK_CHECK_HIP(A.alloc(&p->x_ulde, 2 * N));
-    ZK_CHECK_HIP(A.alloc(&p->x_dscratch, 8 * (2048 + n / 2048 + 2) + 6 * n + 4 * (n / 256 + 1)));
+    ZK_CHECK_HIP(A.alloc(&p->x_dscratch, DeepScratch::size(n, 2)));
     return ZK_OK;
 }
 
@@ -1362,15 +1303,11 @@ int zk::fri_lead_layers(zk_prover *p, const Plan *pl, int KX, uint32_t fold, uin
     // the constant part of the fold constants is uploaded once; each layer's coin writes alpha into it
     void *fc = planes(p, KX).fold_consts;
     fe *alpha_dev = nullptr;
-    if (KX == 1) {
-        const FoldConsts F = fold_consts(fe_zero(), fold);
-        ZK_TRY(h2d_small(p, fc, &F, sizeof F));
-        alpha_dev = &((FoldConsts *)fc)->alpha;
-    } else {
-        const FoldConstsE F = fold_consts_ext(fe2_zero(), fold);
-        ZK_TRY(h2d_small(p, fc, &F, sizeof F));
-        alpha_dev = &((FoldConstsE *)fc)->alpha.a;
-    }
+    ZK_TRY(with_kx(KX, [&](auto kx) {
+        const auto F = fold_consts<decltype(kx)::value>(fe2_zero(), fold);
+        alpha_dev = (fe *)&((decltype(F) *)fc)->alpha;
+        return h2d_small(p, fc, &F, sizeof F);
+    }));
     ZK_TRY(h2d_small(p, p->fri_seed, coin.seed, 32));  // (the next reseed restarts the counter)
     for (int l = l0; l < nl; l++) {
         const size_t L = Y.len[l], rows = L / fold;
@@ -1378,11 +1315,9 @@ int zk::fri_lead_layers(zk_prover *p, const Plan *pl, int KX, uint32_t fold, uin
         Y.nodes[l] = dig + 32 * rows;
         dig += 64 * rows;
         const int lb = l == l0 ? lb0 : 0;
-        if (KX == 1) commit_fri_layer(p->st, Y.vals[l], L, (int)fold, Y.leaves[l], Y.nodes[l], lb);
-        else commit_fri_layer_ext(p->st, Y.vals[l], L, (int)fold, Y.leaves[l], Y.nodes[l], lb);
+        commit_fri_layer(p->st, KX, Y.vals[l], L, (int)fold, Y.leaves[l], Y.nodes[l], lb);
         fri_coin_launch(p->st, (uint32_t *)p->fri_seed, Y.nodes[l] + 32, KX, alpha_dev, p->fri_alphas + 2 * l);
-        if (KX == 1) fri_fold_launch(p->st, Y.vals[l], L, (int)fold, fc, pl->TN, N / L, next, lb);
-        else fri_fold_ext_launch(p->st, Y.vals[l], L, (int)fold, fc, pl->TN, N / L, next, lb);
+        fri_fold_launch(p->st, KX, Y.vals[l], L, (int)fold, fc, pl->TN, N / L, next, lb);
         Y.vals[l + 1] = next;
         Y.len[l + 1] = rows;
         next += KX * rows;
@@ -1397,7 +1332,7 @@ int zk::fri_lead_layers(zk_prover *p, const Plan *pl, int KX, uint32_t fold, uin
     // host replay of the same transcript (it continues into the remainder, grinding and queries)
     for (int l = l0; l < nl; l++) {
         coin.reseed(R.fri_roots[l]);
-        const fe2 alpha = KX == 1 ? fe2{coin.draw(), fe_zero()} : coin.draw_ext(2);
+        const fe2 alpha = coin.draw_ext(KX);
         fe_to_bytes(alpha.a, R.fri_alphas[l]);
         if (!fe_eq(alpha.a, dalpha[2 * l]) || (KX == 2 && !fe_eq(alpha.b, dalpha[2 * l + 1])))
             ZK_FAIL(ZK_ERR_DEVICE, "device FRI transcript diverged from the host transcript");
@@ -1406,8 +1341,7 @@ int zk::fri_lead_layers(zk_prover *p, const Plan *pl, int KX, uint32_t fold, uin
         ht->stop("fri_replay");
         ht->start();
     }
-    if (KX == 1) return remainder_step(rv, B, coin, R, degree_flag);
-    return remainder_step_ext(rv, B, coin, R, degree_flag, Y.rem_flat);
+    return remainder_step(KX, rv, B, coin, R, degree_flag, Y.rem_flat);
 }
 
 void Openings::unpack(const fe *got, size_t nu, int CK, const std::vector<std::vector<uint64_t>> &fri_pos,
@@ -1426,6 +1360,34 @@ void Openings::unpack(const fe *got, size_t nu, int CK, const std::vector<std::v
         digests[b].assign(dg, dg + bytes);
         dg += bytes;
     }
+}
+
+// S5 on one GPU: z from the coin, the OOD frame (its flattened form into h), the DEEP constants and the DEEP LDE into
+// the plane set's ulde (coset-major) and, deep_out != nullptr, in natural order into deep_out.
+template <int KX>
+static int ood_deep_stage(zk_prover *p, Plan *pl, Coin &coin, zk_record &R, HostTimer &HT, int C, const AirConsts *Kp,
+                          const zk_pub_inputs *pub, fe *deep_out, std::vector<fe> &h) {
+    typedef Chal<KX> X;
+    const Planes b = planes(p, KX);
+    const int log_n = pl->log_n;
+    const typename X::T z = X::make(coin.draw_ext(KX)), zg = X::mulb(z, h_root_of_unity(log_n));
+    fe_to_bytes(X::comp(z, 0), R.z);
+    ood_eval(p->st, p->polys, W, p->cpolys, C * KX, log_n, z, zg, b.ood_tab, b.partials, p->ood);
+    HT.stop("z");
+    std::vector<fe> hv((size_t)KX * (2 * W + C * KX));
+    ZK_TRY(d2h_small(p, hv.data(), p->ood, hv.size() * sizeof(fe)));
+    ZK_TRY(d2h_flush(p));
+    HT.start();
+    std::vector<fe2> e;
+    ood_reseed(coin, KX, hv, C, R, e, h);
+    stage_mark(p, "ood");
+    const DeepConsts<KX> D = draw_deep_consts<KX>(coin, e, C, z, zg, R);
+    ZK_TRY(h2d_small(p, b.deep_consts, &D, sizeof D));
+    deep_coeff_launch(p->st, pl->Tn, p->polys, p->cpolys, C, log_n, pl->log_b, b.deep_consts, z, zg, pl->ct, b.dscratch,
+                      b.ulde, p->tmp, deep_out);
+    HT.stop("deep_consts");
+    // while the GPU runs DEEP: the verifier's out-of-domain identity on the frame just read
+    return check_ood_identity(e, C, Kp, KX, X::wide(z), (size_t)1 << log_n, pub);
 }
 
 static int prove_once(zk_prover *p, const TraceSrc &src, size_t n, const zk_options *opt, const zk_pub_inputs *pub,
@@ -1460,7 +1422,6 @@ static int prove_once(zk_prover *p, const TraceSrc &src, size_t n, const zk_opti
     const int log_n = pl->log_n, log_b = pl->log_b;
     const int C = num_comp_cols(n);
     if (C > 8) ZK_FAIL(ZK_ERR_INVALID_ARG, "composition column count exceeds 8");
-    const fe g = h_root_of_unity(log_n);
     zk_record R = record_init(n, N, C);
     stage_begin(p);
     stage_mark(p, "start");
@@ -1489,22 +1450,13 @@ static int prove_once(zk_prover *p, const TraceSrc &src, size_t n, const zk_opti
     // CE cosets evaluated: 7 when the composition has at most 7 columns (the stage derives the 8th)
     const int nce = (!bnd_rows && C <= 7) ? 7 : 8;
     AirConsts Kp[2];
-    if (KX == 1) {
-        draw_air_consts(coin, pub, n, Kp[0], R);
-        ZK_TRY(h2d_small(p, p->air_consts, &Kp[0], sizeof Kp[0]));
-        const fe *binv = boundary_inverses(p, pl);
-        if (!binv) ZK_FAIL(ZK_ERR_OUT_OF_MEMORY, "boundary divisor table");
-        ZK_CHECK_HIP(eval_constraints(p->st, p->lde, log_n, log_b, pl->periodic, binv, (const AirConsts *)p->air_consts, comp,
-                                      bnd_rows, nce));
-        HT.stop("air_consts");
-    } else {
-        draw_air_consts_ext(coin, pub, n, Kp[0], Kp[1], R);
-        ZK_TRY(h2d_small(p, p->x_air, Kp, sizeof Kp));
-        const fe *binv = boundary_inverses(p, pl);
-        if (!binv) ZK_FAIL(ZK_ERR_OUT_OF_MEMORY, "boundary divisor table");
-        ZK_CHECK_HIP(eval_constraints_ext(p->st, p->lde, log_n, log_b, pl->periodic, binv, (const AirConsts *)p->x_air, comp,
-                                          bnd_rows, nce));
-    }
+    draw_air_consts(coin, pub, n, KX, Kp, R);
+    ZK_TRY(h2d_small(p, pb.air_consts, Kp, KX * sizeof Kp[0]));
+    const fe *binv = boundary_inverses(p, pl);
+    if (!binv) ZK_FAIL(ZK_ERR_OUT_OF_MEMORY, "boundary divisor table");
+    ZK_CHECK_HIP((KX == 1 ? eval_constraints : eval_constraints_ext)(p->st, p->lde, log_n, log_b, pl->periodic, binv,
+                                                                     (const AirConsts *)pb.air_consts, comp, bnd_rows, nce));
+    HT.stop("air_consts");
     stage_mark(p, "constraints");
 
     // S4: composition polynomial (interpolate over the CE coset, segment into C columns) + commit.
@@ -1522,43 +1474,10 @@ static int prove_once(zk_prover *p, const TraceSrc &src, size_t n, const zk_opti
     const int lb0 = nl > 0 ? log_b : 0;
     // S5: OOD frame [P7], DEEP coefficients [P8] and evaluations.  h holds the frame flattened
     // (k base elements per E value): [T(z)]_W ++ [T(zg)]_W ++ [H(z)]_C.
-    std::vector<fe> h((2 * W + C) * KX);
-    if (KX == 1) {
-        const fe z = coin.draw(), zg = fe_mul(z, g);
-        fe_to_bytes(z, R.z);
-        ood_eval(p->st, p->polys, W, p->cpolys, C, log_n, z, zg, p->ood_tab, p->partials, p->ood);
-        HT.stop("z");
-        ZK_TRY(d2h_small(p, h.data(), p->ood, (2 * W + C) * sizeof(fe)));
-        ZK_TRY(d2h_flush(p));
-        HT.start();
-        ood_reseed(coin, h.data(), C, R);
-        stage_mark(p, "ood");
-        const DeepConsts D = draw_deep_consts(coin, h.data(), C, z, zg, R);
-        ZK_TRY(h2d_small(p, p->deep_consts, &D, sizeof D));
-        deep_coeff_launch(p->st, pl->Tn, p->polys, p->cpolys, C, log_n, log_b, p->deep_consts, z, zg, pl->ct,
-                          p->dscratch, p->ulde, p->tmp, lb0 ? nullptr : deep);
-        HT.stop("deep_consts");
-        // while the GPU runs DEEP: the verifier's out-of-domain identity on the frame just read
-        std::vector<fe2> e(2 * W + C);
-        for (int i = 0; i < 2 * W + C; i++) e[i] = fe2_lift(h[i]);
-        ZK_TRY(check_ood_identity(e, C, Kp, 1, fe2_lift(z), n, pub));
-    } else {
-        const fe2 z = coin.draw_ext(2), zg = fe2_mulb(z, g);
-        fe_to_bytes(z.a, R.z);
-        const int np = 2 * W + CK;  // E values of the trace polys at z, zg and of the C*k base composition polys at z
-        ood_eval_ext(p->st, p->polys, W, p->cpolys, CK, log_n, z, zg, p->x_tab, p->x_partials, p->ood);
-        std::vector<fe> hv(2 * np);
-        ZK_TRY(d2h_small(p, hv.data(), p->ood, hv.size() * sizeof(fe)));
-        ZK_TRY(d2h_flush(p));
-        std::vector<fe2> e;
-        ood_reseed_ext(coin, hv, C, R, e, h);
-        stage_mark(p, "ood");
-        const DeepConstsE D = draw_deep_consts_ext(coin, e, C, z, zg, R);
-        ZK_TRY(h2d_small(p, p->x_deep_consts, &D, sizeof D));
-        deep_coeff_ext_launch(p->st, pl->Tn, p->polys, p->cpolys, C, log_n, log_b, p->x_deep_consts, z, zg,
-                              pl->ct, p->x_dscratch, p->x_ulde, p->tmp, lb0 ? nullptr : deep);
-        ZK_TRY(check_ood_identity(e, C, Kp, 2, z, n, pub));
-    }
+    std::vector<fe> h;
+    ZK_TRY(with_kx(KX, [&](auto kx) {
+        return ood_deep_stage<decltype(kx)::value>(p, pl, coin, R, HT, C, Kp, pub, lb0 ? nullptr : deep, h);
+    }));
     stage_mark(p, "deep");
 
     // S6: FRI [P9, P10]; E layers are planar (k planes of L values)
@@ -1570,7 +1489,7 @@ static int prove_once(zk_prover *p, const TraceSrc &src, size_t n, const zk_opti
         if (tot > p->max_n * p->max_b) ZK_FAIL(ZK_ERR_INVALID_ARG, "FRI layers exceed the prover's buffers");
     }
     FriLayers Y(nl);
-    const fe *deep0 = lb0 ? (KX == 2 ? p->x_ulde : p->ulde) : deep;
+    const fe *deep0 = lb0 ? pb.ulde : deep;
     Y.vals[0] = deep0;
     Y.len[0] = N;
     ZK_TRY(fri_lead_layers(p, pl, KX, fold, B, N, 0, lb0, pb.fri, p->fri_dig, Y, coin, R, degree_flag, &HT));
@@ -2349,7 +2268,7 @@ static int diag_back_half_upload(zk_prover *p, const uint8_t *tpolys, const uint
 
 // The OOD frame of 28 trace polynomials and ccols composition polynomials (n coefficients each, column-major; over E,
 // ext = 2, ccols counts the base columns) at the points z and zg, given independently (16 bytes each, 32 over E):
-// ood_eval / ood_eval_ext with the (rank, G) share of the coefficient range.  out: (56 + ccols) elements
+// ood_eval with the (rank, G) share of the coefficient range.  out: (56 + ccols) elements
 // [T(z)]_28 ++ [T(zg)]_28 ++ [H(z)]_ccols; over E the a components of all, then the b components.
 extern "C" int zk_diag_ood(int device, const uint8_t *tpolys, const uint8_t *cpolys, int ccols, size_t n, int ext,
                            const uint8_t *z, const uint8_t *zg, int rank, int G, uint8_t *out) {
@@ -2360,53 +2279,131 @@ extern "C" int zk_diag_ood(int device, const uint8_t *tpolys, const uint8_t *cpo
     ZK_TRY(zk_prover_create(device, n, 8, &p));
     std::unique_ptr<zk_prover, void (*)(zk_prover *)> guard(p, zk_prover_destroy);
     ZK_TRY(diag_back_half_upload(p, tpolys, cpolys, ccols, n, ext));
-    if (ext == 1) ood_eval(p->st, p->polys, W, p->cpolys, ccols, ilog2(n), zv.a, zgv.a, p->ood_tab, p->partials, p->ood, rank, G);
-    else ood_eval_ext(p->st, p->polys, W, p->cpolys, ccols, ilog2(n), zv, zgv, p->x_tab, p->x_partials, p->ood, rank, G);
+    const Planes b = planes(p, ext);
+    with_kx(ext, [&](auto kx) {
+        typedef Chal<decltype(kx)::value> X;
+        ood_eval(p->st, p->polys, W, p->cpolys, ccols, ilog2(n), X::make(zv), X::make(zgv), b.ood_tab, b.partials, p->ood, rank, G);
+        return 0;
+    });
     ZK_CHECK_HIP(hipStreamSynchronize(p->st));
     ZK_CHECK_HIP(hipMemcpy(out, p->ood, (size_t)ext * (2 * W + ccols) * 16, hipMemcpyDeviceToHost));
     return ZK_OK;
 }
 
-// The DEEP polynomial's coefficients through deep_poly / deep_poly_ext: alpha_t (28) weigh the trace polynomials,
+// The DEEP polynomial's coefficients through deep_poly: alpha_t (28) weigh the trace polynomials,
 // alpha_c the composition columns (ccols of them; over E ccols / 2 E columns H_j = P_2j + X P_2j+1, and every
 // coefficient and point is 32 bytes).  out: n coefficients; over E the a plane, then the b plane.  z = 0 or zg = 0 is
 // refused: the kernels scale by powers of their inverses.
-extern "C" int zk_diag_deep(int device, const uint8_t *tpolys, const uint8_t *cpolys, int ccols, size_t n, int ext,
-                            const uint8_t *z, const uint8_t *zg, const uint8_t *alpha_t, const uint8_t *alpha_c,
-                            uint8_t *out) {
+static int diag_deep(int device, const uint8_t *tpolys, const uint8_t *cpolys, int ccols, size_t n, int ext,
+                     const uint8_t *z, const uint8_t *zg, const uint8_t *alpha_t, const uint8_t *alpha_c, int parts,
+                     uint8_t *out) {
     fe2 zv, zgv;
     ZK_TRY(diag_back_half_args("zk_diag_deep", tpolys, cpolys, ccols, n, ext, z, zg, out, &zv, &zgv));
     if (!alpha_t || !alpha_c) ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_deep: null argument");
     if ((fe_is_zero(zv.a) && fe_is_zero(zv.b)) || (fe_is_zero(zgv.a) && fe_is_zero(zgv.b)))
         ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_deep: z and zg must be non-zero (their inverses are taken)");
-    const int C = ccols / ext;
-    DeepConsts D;
-    DeepConstsE DE;
-    memset(&D, 0, sizeof D);
-    memset(&DE, 0, sizeof DE);
-    for (int c = 0; c < W + C; c++) {
-        fe2 v;
-        if (!diag_read_fe((c < W ? alpha_t + 16 * ext * c : alpha_c + 16 * ext * (c - W)), ext, &v))
+    const int C = ccols / ext, log_n = ilog2(n);
+    fe2 at[W], ac[8];
+    for (int c = 0; c < W + C; c++)
+        if (!diag_read_fe((c < W ? alpha_t + 16 * ext * c : alpha_c + 16 * ext * (c - W)), ext, c < W ? &at[c] : &ac[c - W]))
             ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_deep: non-canonical coefficient");
-        (c < W ? D.alpha_t[c] : D.alpha_c[c - W]) = v.a;
-        (c < W ? DE.alpha_t[c] : DE.alpha_c[c - W]) = v;
-    }
-    D.z = zv.a, D.zg = zgv.a;
-    DE.z = zv, DE.zg = zgv, DE.zb2 = fe_mul(zv.b, zv.b), DE.zgb2 = fe_mul(zgv.b, zgv.b);
     zk_prover *p = nullptr;
     ZK_TRY(zk_prover_create(device, n, 8, &p));
     std::unique_ptr<zk_prover, void (*)(zk_prover *)> guard(p, zk_prover_destroy);
     ZK_TRY(diag_back_half_upload(p, tpolys, cpolys, ccols, n, ext));
-    const fe *Dk;
-    if (ext == 1) {
-        ZK_CHECK_HIP(hipMemcpy(p->deep_consts, &D, sizeof D, hipMemcpyHostToDevice));
-        Dk = deep_poly(p->st, p->polys, p->cpolys, C, ilog2(n), p->deep_consts, zv.a, zgv.a, p->dscratch);
-    } else {
-        ZK_CHECK_HIP(hipMemcpy(p->x_deep_consts, &DE, sizeof DE, hipMemcpyHostToDevice));
-        Dk = deep_poly_ext(p->st, p->polys, p->cpolys, C, ilog2(n), p->x_deep_consts, zv, zgv, p->x_dscratch);
-    }
+    const Planes b = planes(p, ext);
+    return with_kx(ext, [&](auto kx) -> int {
+        constexpr int KX = decltype(kx)::value;
+        typedef Chal<KX> X;
+        const typename X::T z = X::make(zv), zg = X::make(zgv);
+        DeepConsts<KX> D;
+        memset(&D, 0, sizeof D);
+        for (int c = 0; c < W; c++) D.alpha_t[c] = X::make(at[c]);
+        for (int c = 0; c < C; c++) D.alpha_c[c] = X::make(ac[c]);
+        D.z = z, D.zg = zg;
+        ZK_CHECK_HIP(hipMemcpy(b.deep_consts, &D, sizeof D, hipMemcpyHostToDevice));
+        const fe *Dk = nullptr;
+        if (parts == 1) {
+            Dk = deep_poly(p->st, p->polys, p->cpolys, C, log_n, b.deep_consts, z, zg, b.dscratch);
+        } else {
+            // The ranks of a sharded proof on one device, in rank order: every range's begin, the later ranges' totals
+            // summed here as the all-gather and k_sh_suffix_carry do, every range's end.  Each rank has a scratch of
+            // its own; here the ranges share one, so a range's block carries (begin leaves them at the head of the
+            // block-sum area, which the next range's begin overwrites) are kept in p->comp and put back before its end.
+            const DeepScratch S(b.dscratch, n, KX);
+            const size_t kn = n / parts, nc = 2 * KX, ncarry = nc * (kn / ZK_DEEP_BLOCK);
+            std::vector<fe> tot((size_t)parts * nc);
+            for (int g = 0; g < parts; g++) {
+                const fe *t = deep_range_begin(p->st, p->polys, p->cpolys, C, log_n, b.deep_consts, z, zg, b.dscratch, g * kn, kn);
+                ZK_CHECK_HIP(hipMemcpyAsync(p->comp + g * ncarry, S.bs, ncarry * sizeof(fe), hipMemcpyDeviceToDevice, p->st));
+                ZK_CHECK_HIP(hipMemcpyAsync(&tot[g * nc], t, nc * sizeof(fe), hipMemcpyDeviceToHost, p->st));
+            }
+            ZK_CHECK_HIP(hipStreamSynchronize(p->st));
+            std::vector<fe> later((size_t)parts * nc, fe_zero());
+            for (int g = parts - 2; g >= 0; g--)
+                for (size_t c = 0; c < nc; c++) later[g * nc + c] = fe_add(later[(g + 1) * nc + c], tot[(g + 1) * nc + c]);
+            ZK_CHECK_HIP(hipMemcpy(p->ood, later.data(), later.size() * sizeof(fe), hipMemcpyHostToDevice));
+            for (int g = 0; g < parts; g++) {
+                ZK_CHECK_HIP(hipMemcpyAsync(S.bs, p->comp + g * ncarry, ncarry * sizeof(fe), hipMemcpyDeviceToDevice, p->st));
+                Dk = deep_range_end(p->st, log_n, z, zg, b.dscratch, g * kn, kn, p->ood + g * nc);
+            }
+        }
+        ZK_CHECK_HIP(hipStreamSynchronize(p->st));
+        ZK_CHECK_HIP(hipMemcpy(out, Dk, (size_t)KX * n * 16, hipMemcpyDeviceToHost));
+        return ZK_OK;
+    });
+}
+extern "C" int zk_diag_deep(int device, const uint8_t *tpolys, const uint8_t *cpolys, int ccols, size_t n, int ext,
+                            const uint8_t *z, const uint8_t *zg, const uint8_t *alpha_t, const uint8_t *alpha_c,
+                            uint8_t *out) {
+    return diag_deep(device, tpolys, cpolys, ccols, n, ext, z, zg, alpha_t, alpha_c, 1, out);
+}
+// zk_diag_deep by coefficient ranges, as the ranks of a sharded proof compute it: `parts` ranges of n / parts
+// coefficients (a whole number of ZK_DEEP_RANGE_QUANTUM each), deep_range_begin / deep_range_end per range.  The same
+// output.
+extern "C" int zk_diag_deep_parts(int device, const uint8_t *tpolys, const uint8_t *cpolys, int ccols, size_t n, int ext,
+                                  const uint8_t *z, const uint8_t *zg, const uint8_t *alpha_t, const uint8_t *alpha_c,
+                                  int parts, uint8_t *out) {
+    if (parts < 2 || parts > 8 || (parts & (parts - 1)) || n < (size_t)parts * ZK_DEEP_RANGE_QUANTUM)
+        ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_deep_parts: 2, 4 or 8 ranges of at least 2048 coefficients");
+    return diag_deep(device, tpolys, cpolys, ccols, n, ext, z, zg, alpha_t, alpha_c, parts, out);
+}
+
+// One FRI layer through commit_fri_layer and fri_fold_launch: `layer` holds L values as the
+// kernels read them (over E planar: L a components, then L b components; lb > 0: coset-major over 2^lb cosets,
+// FriLayout), folded by `fold` at `alpha` (16 bytes, 32 over E) with x_r = 3 w_L^r taken from the tables of a plan of
+// N = L wstride points.  root_out: the layer's Merkle root (32 bytes); next_out: the L / fold folded values (planar).
+extern "C" int zk_diag_fri_layer(int device, const uint8_t *layer, size_t L, int ext, int fold, int lb, size_t wstride,
+                                 const uint8_t *alpha, uint8_t *root_out, uint8_t *next_out) {
+    fe2 av;
+    const size_t N = L * wstride;
+    const bool ok = layer && alpha && root_out && next_out && (ext == 1 || ext == 2) &&
+                    (fold == 2 || fold == 4 || fold == 8 || fold == 16) && L && !(L & (L - 1)) && wstride &&
+                    !(wstride & (wstride - 1)) && L >= 4 * (size_t)fold && N >= 128 && N <= ((size_t)1 << 22) && lb >= 0 &&
+                    ((size_t)1 << lb) <= L / fold;
+    if (!ok || !diag_read_fe(alpha, ext, &av))
+        ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_fri_layer: L and wstride powers of two, 128 <= L wstride <= 2^22, fold 2 .. 16, "
+                                    "at least 4 rows, 2^lb <= L / fold, alpha canonical");
+    zk_prover *p = nullptr;
+    ZK_TRY(zk_prover_create(device, N / 8, 8, &p));
+    std::unique_ptr<zk_prover, void (*)(zk_prover *)> guard(p, zk_prover_destroy);
+    Plan *pl = nullptr;
+    ZK_TRY(get_plan(p, N / 8, 8, &pl));
+    if (ext == 2) ZK_TRY(ensure_ext(p));
+    const Planes b = planes(p, ext);
+    const size_t rows = L / fold;
+    uint8_t *leaves = p->fri_dig, *nodes = leaves + 32 * rows;
+    ZK_CHECK_HIP(hipMemcpy(b.deep, layer, (size_t)ext * L * 16, hipMemcpyHostToDevice));
+    ZK_TRY(with_kx(ext, [&](auto kx) -> int {
+        const auto F = fold_consts<decltype(kx)::value>(av, (uint32_t)fold);
+        ZK_CHECK_HIP(hipMemcpy(b.fold_consts, &F, sizeof F, hipMemcpyHostToDevice));
+        return ZK_OK;
+    }));
+    commit_fri_layer(p->st, ext, b.deep, L, fold, leaves, nodes, lb);
+    fri_fold_launch(p->st, ext, b.deep, L, fold, b.fold_consts, pl->TN, wstride, b.fri, lb);
     ZK_CHECK_HIP(hipStreamSynchronize(p->st));
-    ZK_CHECK_HIP(hipMemcpy(out, Dk, (size_t)ext * n * 16, hipMemcpyDeviceToHost));
+    ZK_CHECK_HIP(hipMemcpy(root_out, nodes + 32, 32, hipMemcpyDeviceToHost));
+    ZK_CHECK_HIP(hipMemcpy(next_out, b.fri, (size_t)ext * rows * 16, hipMemcpyDeviceToHost));
     return ZK_OK;
 }
 

@@ -603,29 +603,35 @@ int check_prove_args(size_t n, size_t max_n, uint32_t max_b, const zk_options *o
 // num_constraint_composition_columns for the ProcessorAir degrees [P5]
 // S0: public coin seeded with Context::to_elements || PublicInputs::to_elements [P1]
 Coin seed_coin(size_t n, const zk_options *opt, const zk_pub_inputs *pub);
-// S3: composition coefficients (20 transition, 22 boundary) and the evaluator's constants [P3, P4]
-void draw_air_consts(Coin &coin, const zk_pub_inputs *pub, size_t n, AirConsts &K, zk_record &R);
-// FieldExtension::Quadratic: the coefficients are E values (a + bX); the composition is linear in them, so
-// the evaluator runs once with the a components (Ka) and once with the b components (Kb)
-void draw_air_consts_ext(Coin &coin, const zk_pub_inputs *pub, size_t n, AirConsts &Ka, AirConsts &Kb, zk_record &R);
-// S5: record the OOD frame h = T(z) || T(zg) || H(z) and reseed the coin with its two hashes [P7]
-void ood_reseed(Coin &coin, const fe *h, int C, zk_record &R);
+// The steps below are written once for both challenge fields: KX = 1 the base field, KX = 2 FieldExtension::Quadratic
+// [P15].  Coin::draw_ext(KX) draws a value of either (KX = 1: a lifted base element, the bytes of draw()); the record
+// keeps the a component of every value.
+// f(std::integral_constant<int, KX>) for a KX known at run time
+template <class F>
+auto with_kx(int KX, F f) {
+    return KX == 1 ? f(std::integral_constant<int, 1>{}) : f(std::integral_constant<int, 2>{});
+}
+// S3: composition coefficients (20 transition, 22 boundary) and the evaluator's constants [P3, P4]: K[j] holds
+// component j of every coefficient (the composition is linear in them, so the evaluator runs once per component)
+void draw_air_consts(Coin &coin, const zk_pub_inputs *pub, size_t n, int KX, AirConsts *K, zk_record &R);
+// S5: from ood_eval's output hv the OOD frame e = T(z) || T(zg) || H(z) and its flattened form h (the serialization
+// order); records it and reseeds the coin with its two hashes [P7]
+void ood_reseed(Coin &coin, int KX, const std::vector<fe> &hv, int C, zk_record &R, std::vector<fe2> &e,
+                std::vector<fe> &h);
 // S5: DEEP coefficients and the combined constants k1, k2 [P8]
-DeepConsts draw_deep_consts(Coin &coin, const fe *h, int C, fe z, fe zg, zk_record &R);
-// FieldExtension::Quadratic versions [P15] (prover.hip): E working set on first use, OOD frame from the
-// two-plane ood_eval_ext output, DEEP and fold constants, remainder from a planar last layer
+template <int KX>
+DeepConsts<KX> draw_deep_consts(Coin &coin, const std::vector<fe2> &e, int C, typename Chal<KX>::T z,
+                                typename Chal<KX>::T zg, zk_record &R);
+// the E working set (planar buffers, prover.hip) on first use
 int ensure_ext(zk_prover *p);
-void ood_reseed_ext(Coin &coin, const std::vector<fe> &hv, int C, zk_record &R, std::vector<fe2> &e,
-                    std::vector<fe> &h);
-DeepConstsE draw_deep_consts_ext(Coin &coin, const std::vector<fe2> &e, int C, fe2 z, fe2 zg, zk_record &R);
-FoldConstsE fold_consts_ext(fe2 alpha, uint32_t fold);
-int remainder_step_ext(const std::vector<fe> &rv, uint32_t B, Coin &coin, zk_record &R, unsigned &degree_flag,
-                       std::vector<fe> &rem_flat);
 // S6: number of FRI layers for an LDE domain of N points [P9]
 int fri_num_layers(size_t N, const zk_options *opt);
-FoldConsts fold_consts(fe alpha, uint32_t fold);
-// S6: interpolate the last layer (natural order, over 3 * <w_L>), keep L/B coefficients, commit [P9]
-int remainder_step(std::vector<fe> &last, uint32_t B, Coin &coin, zk_record &R, unsigned &degree_flag);
+template <int KX>
+FoldConsts<KX> fold_consts(fe2 alpha, uint32_t fold);
+// S6: interpolate the last layer (KX planes, natural order, over 3 * <w_L>), keep L/B coefficients, commit [P9];
+// rem_flat: the remainder as serialized (KX elements per coefficient)
+int remainder_step(int KX, const std::vector<fe> &last, uint32_t B, Coin &coin, zk_record &R, unsigned &degree_flag,
+                   std::vector<fe> &rem_flat);
 // S7: grinding nonce (on the GPU of `p` for grinding >= 8, else on the host) and the sorted unique
 // query positions [P10, P11]
 int grind_and_positions(zk_prover *p, Coin &coin, const zk_options *opt, size_t N, zk_record &R,
@@ -657,16 +663,21 @@ struct Openings {
 struct Planes {
     fe *comp, *ctmp, *clde, *deep, *fri;
     void *fold_consts, *air_consts;
+    fe *ood_tab, *partials, *dscratch, *ulde;  // (ulde: single-GPU provers only)
+    void *deep_consts;
 };
 inline Planes planes(const zk_prover *p, int KX) {
-    if (KX == 2) return {p->x_comp, p->x_ctmp, p->x_clde, p->x_deep, p->x_fri, p->x_fold_consts, p->x_air};
-    return {p->comp, p->ctmp, p->clde, p->deep, p->fri, p->fold_consts, p->air_consts};
+    if (KX == 2)
+        return {p->x_comp, p->x_ctmp, p->x_clde,     p->x_deep,     p->x_fri,  p->x_fold_consts,
+                p->x_air,  p->x_tab,  p->x_partials, p->x_dscratch, p->x_ulde, p->x_deep_consts};
+    return {p->comp,       p->ctmp,    p->clde,     p->deep,     p->fri,  p->fold_consts,
+            p->air_consts, p->ood_tab, p->partials, p->dscratch, p->ulde, p->deep_consts};
 }
 zk_record record_init(size_t n, size_t N, int C);  // a proof's record: the shape fields set, the rest zero
 // S6 from layer l0 on, on one GPU (a single-GPU proof: from 0; a sharded proof's lead rank: from the gathered layer):
 // vals[l0] / len[l0] hold layer l0, stored with the low lb0 index bits major (FriLayout).  Commit, device coin and fold
 // per layer, `next` and `dig` the cursors of the layer values and digests; one flush of the roots, the device alphas and
-// the last layer; the host replays the transcript and commits the remainder (rem_flat: KX = 2).  ht: ZK_HOST_TIMING.
+// the last layer; the host replays the transcript and commits the remainder (Y.rem_flat).  ht: ZK_HOST_TIMING.
 struct HostTimer;
 struct FriLayers {
     std::vector<const fe *> vals;

@@ -228,75 +228,57 @@ __global__ void k_sh_pack_coset(const fe *c, size_t plane_stride, int log_n, int
 }
 
 // first FRI fold over the local cosets: row r' = r + 8*q0 (values deep[j][q0 + k*m]) -> out[j*m + q0], as the
-// single-GPU fold (kernels.hip k_fri_fold: idft_small, then Horner at beta = alpha / x_r')
-template <int F>
+// single-GPU fold (kernels.hip k_fri_fold: idft_small per component plane, then Horner at beta = alpha / x_r').
+// E buffers are planar with plane stride Bl*n (DEEP) / Bl*m (fold).
+template <int KX, int F>
 __global__ void __launch_bounds__(256) k_sh_fri_fold0(const fe *deep, int log_n, int Bl, int g, int log_m,
-                                                      const FoldConsts *Fc, const fe *wi_lo, const fe *wi_hi,
+                                                      const FoldConsts<KX> *Fc, const fe *wi_lo, const fe *wi_hi,
                                                       size_t wstride, fe *out) {
-    const size_t n = (size_t)1 << log_n, m = (size_t)1 << log_m;
-    const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (t >= ((size_t)Bl << log_m)) return;
-    const size_t j = t >> log_m, q0 = t & (m - 1);
-    const size_t rp = (size_t)(g * Bl + (int)j) + 8 * q0;  // row index in the layer (1/x_r: w_N^-(rp wstride))
-    const size_t wi = rp * wstride;
-    fe v[F];
-#pragma unroll
-    for (int k = 0; k < F; k++) v[k] = deep[j * n + q0 + ((size_t)k << log_m)];
-    const fe beta = fe_mul(Fc->alpha, fe_mul(Fc->inv_offset, fe_mul(wi_lo[wi & 2047], wi_hi[wi >> 11])));
-    idft_small<F>(v, Fc->zinv);
-    fe acc = v[F - 1];
-#pragma unroll
-    for (int mm = F - 2; mm >= 0; mm--) acc = fe_add(fe_mul(acc, beta), v[mm]);
-    out[t] = fe_mul(acc, Fc->inv_fold);
-}
-
-// ---- FieldExtension::Quadratic versions: E buffers are planar with plane stride Bl*n (DEEP) / Bl*m (fold)
-template <int F>
-__global__ void __launch_bounds__(256) k_sh_fri_fold0_ext(const fe *deep, int log_n, int Bl, int g, int log_m,
-                                                          const FoldConstsE *Fc, const fe *wi_lo, const fe *wi_hi,
-                                                          size_t wstride, fe *out) {
+    typedef Chal<KX> X;
+    typedef typename X::T T;
     const size_t n = (size_t)1 << log_n, m = (size_t)1 << log_m, cs = (size_t)Bl * n, om = (size_t)Bl * m;
     const size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
     if (t >= om) return;
     const size_t j = t >> log_m, q0 = t & (m - 1);
-    const size_t rp = (size_t)(g * Bl + (int)j) + 8 * q0, wi = rp * wstride;
-    fe va[F], vb[F];
+    const size_t rp = (size_t)(g * Bl + (int)j) + 8 * q0;  // row index in the layer (1/x_r: w_N^-(rp wstride))
+    const size_t wi = rp * wstride;
+    fe va[F], vb[KX == 2 ? F : 1];  // the component planes
 #pragma unroll
     for (int k = 0; k < F; k++) {
         va[k] = deep[j * n + q0 + ((size_t)k << log_m)];
-        vb[k] = deep[cs + j * n + q0 + ((size_t)k << log_m)];
+        if constexpr (KX == 2) vb[k] = deep[cs + j * n + q0 + ((size_t)k << log_m)];
     }
-    const fe2 beta = fe2_mulb(Fc->alpha, fe_mul(Fc->inv_offset, fe_mul(wi_lo[wi & 2047], wi_hi[wi >> 11])));
+    const T beta = X::mulb(Fc->alpha, fe_mul(Fc->inv_offset, fe_mul(wi_lo[wi & 2047], wi_hi[wi >> 11])));
     idft_small<F>(va, Fc->zinv);
-    idft_small<F>(vb, Fc->zinv);
-    fe2 acc = fe2{va[F - 1], vb[F - 1]};
+    if constexpr (KX == 2) idft_small<F>(vb, Fc->zinv);
+    auto V = [&](int mm) -> T {
+        if constexpr (KX == 2) return fe2{va[mm], vb[mm]};
+        else return va[mm];
+    };
+    T acc = V(F - 1);
 #pragma unroll
-    for (int mm = F - 2; mm >= 0; mm--) acc = fe2_add(fe2_mul(acc, beta), fe2{va[mm], vb[mm]});
-    acc = fe2_mulb(acc, Fc->inv_fold);
-    out[t] = acc.a;
-    out[om + t] = acc.b;
+    for (int mm = F - 2; mm >= 0; mm--) acc = X::add(X::mul(acc, beta), V(mm));
+    X::st(out + t, om, X::mulb(acc, Fc->inv_fold));
 }
 
 // a fold over the local cosets (layer 0, or layer 1 with wstride = fold) for fold 2 / 4 / 8 / 16 (KX planes)
 static void sh_fri_fold0(hipStream_t st, int KX, int fold, const fe *deep, int log_n, int Bl, int g, int log_m,
                          const void *consts, const fe *wi_lo, const fe *wi_hi, size_t wstride, fe *out) {
     const dim3 grid(cdiv((size_t)Bl << log_m, 256));
-#define ZK_SH_FOLD(FF)                                                                                              \
-    do {                                                                                                            \
-        if (KX == 1)                                                                                                \
-            hipLaunchKernelGGL(k_sh_fri_fold0<FF>, grid, dim3(256), 0, st, deep, log_n, Bl, g, log_m,               \
-                               (const FoldConsts *)consts, wi_lo, wi_hi, wstride, out);                             \
-        else                                                                                                        \
-            hipLaunchKernelGGL(k_sh_fri_fold0_ext<FF>, grid, dim3(256), 0, st, deep, log_n, Bl, g, log_m,           \
-                               (const FoldConstsE *)consts, wi_lo, wi_hi, wstride, out);                            \
-    } while (0)
-    switch (fold) {
-        case 2: ZK_SH_FOLD(2); break;
-        case 4: ZK_SH_FOLD(4); break;
-        case 8: ZK_SH_FOLD(8); break;
-        default: ZK_SH_FOLD(16); break;
-    }
+    with_kx(KX, [&](auto kx) {
+        constexpr int K = decltype(kx)::value;
+#define ZK_SH_FOLD(FF)                                                                               \
+    hipLaunchKernelGGL((k_sh_fri_fold0<K, FF>), grid, dim3(256), 0, st, deep, log_n, Bl, g, log_m, \
+                       (const FoldConsts<K> *)consts, wi_lo, wi_hi, wstride, out)
+        switch (fold) {
+            case 2: ZK_SH_FOLD(2); break;
+            case 4: ZK_SH_FOLD(4); break;
+            case 8: ZK_SH_FOLD(8); break;
+            default: ZK_SH_FOLD(16); break;
+        }
 #undef ZK_SH_FOLD
+        return 0;
+    });
 }
 
 // the suffix carried into rank `rank`'s DEEP range: out[c] = sum over later ranks h of all[h * nc + c]
@@ -1005,12 +987,8 @@ struct ShardedProof {
     // are not evaluated per row: S4 adds their quotient in coefficient form, each rank over its n / G coefficient
     // slice (boundary_range_*; traces too short for whole ranges keep the per-row form).
     int air_tables() {
-        if (KX == 1) {
-            draw_air_consts(coin, pub, n, K, R);
-        } else {
-            draw_air_consts_ext(coin, pub, n, Kp[0], Kp[1], R);
-            K = Kp[0];
-        }
+        draw_air_consts(coin, pub, n, KX, Kp, R);
+        K = Kp[0];
         return each_rank(X, [this](int l, zk_prover *p, Plan *pl) -> int {
             // divisor tables of the local CE cosets (3 planes of Bl*n): they depend on n and the cosets only, so the
             // plan keeps them for the rank's next proofs (round 6: 0.26 ms per rank and proof at G = 8, 2^22)
@@ -1027,8 +1005,7 @@ struct ShardedProof {
                 pl->sh_divs_r0 = r0;
                 pl->sh_divs_cos = Bl;
             }
-            if (KX == 1) return h2d_small(p, p->air_consts, &K, sizeof K);
-            return h2d_small(p, p->x_air, Kp, sizeof Kp);
+            return h2d_small(p, pb(p).air_consts, Kp, KX * sizeof K);
         });
     }
     // S3 + S4's first step, coset by coset (round 6): evaluate local coset j, inverse-transform it (KX planes), pack
@@ -1070,7 +1047,7 @@ struct ShardedProof {
     // this rank's range sums of plane pln's assertion quotient (they read only the trace coefficients), into xb
     int boundary_begin(int pln) {
         return each_rank(X, [this, pln](int l, zk_prover *p, Plan *) -> int {
-            const void *sums = boundary_range_begin(p->st, p->polys, log_n, KX == 1 ? K : Kp[pln], K.g_last2, p->dscratch,
+            const void *sums = boundary_range_begin(p->st, p->polys, log_n, Kp[pln], K.g_last2, p->dscratch,
                                                     (size_t)X.rank[l] * kg, kg);
             xb.set(l, sums, p->sh_buf);
             return ZK_OK;
@@ -1176,7 +1153,7 @@ struct ShardedProof {
 
     // ---- S5: OOD frame -- every rank evaluates its 1/G of the coefficient range of the (replicated) polynomials, the
     // partial sums are all-gathered and added on the host -- then DEEP over the local cosets
-    // nv values per rank (ood_eval / ood_eval_ext output); the frame value v is sum over ranks of part[rank][v]
+    // nv values per rank (ood_eval output); the frame value v is sum over ranks of part[rank][v]
     template <typename Launch>
     int ood_parts(int nv, Launch launch, std::vector<fe> &sum) {
         ZK_TRY(each_rank(X, [this, launch](int l, zk_prover *p, Plan *) -> int {
@@ -1231,61 +1208,39 @@ struct ShardedProof {
         stage_mark(P0, "deep");
         return ZK_OK;
     }
-    int ood_deep_base() {
-        const fe z = coin.draw(), zg = fe_mul(z, g);
-        fe_to_bytes(z, R.z);
-        ZK_TRY(ood_parts(2 * W + C, [this, z, zg](zk_prover *p, int rank) {
-            ood_eval(p->st, p->polys, W, p->cpolys, C, log_n, z, zg, p->ood_tab, p->partials, p->ood, rank, G);
-        }, h));
-        ood_reseed(coin, h.data(), C, R);
-        stage_mark(P0, "ood");
-        const DeepConsts D = draw_deep_consts(coin, h.data(), C, z, zg, R);
-        auto upload = [D](zk_prover *p) { return h2d_small(p, p->deep_consts, &D, sizeof D); };
-        if (range_split) {
-            ZK_TRY(deep_split_ranges(1, [this, z, zg](zk_prover *p, size_t k0) {
-                return deep_range_begin(p->st, p->polys, p->cpolys, C, log_n, p->deep_consts, z, zg, p->dscratch, k0, kg);
-            }, [this, z, zg](zk_prover *p, size_t k0, const fe *ext) {
-                return deep_range_end(p->st, log_n, z, zg, p->dscratch, k0, kg, ext);
-            }, upload));
-        } else {
-            ZK_TRY(each_rank(X, [this, z, zg, upload](int l, zk_prover *p, Plan *) -> int {
-                ZK_TRY(upload(p));
-                Dk[l] = deep_poly(p->st, p->polys, p->cpolys, C, log_n, p->deep_consts, z, zg, p->dscratch);
-                return ZK_OK;
-            }));
-        }
-        return lde_deep();
-    }
-    int ood_deep_ext() {
-        const fe2 z = coin.draw_ext(2), zg = fe2_mulb(z, g);
-        fe_to_bytes(z.a, R.z);
-        const int np = 2 * W + CK;
+    template <int KX_>
+    int ood_deep_kx() {
+        typedef Chal<KX_> XF;
+        typedef typename XF::T T;
+        const T z = XF::make(coin.draw_ext(KX_)), zg = XF::mulb(z, g);
+        fe_to_bytes(XF::comp(z, 0), R.z);
         std::vector<fe> hv;
-        ZK_TRY(ood_parts(2 * np, [this, z, zg](zk_prover *p, int rank) {
-            ood_eval_ext(p->st, p->polys, W, p->cpolys, CK, log_n, z, zg, p->x_tab, p->x_partials, p->ood, rank, G);
+        ZK_TRY(ood_parts(KX_ * (2 * W + CK), [this, z, zg](zk_prover *p, int rank) {
+            ood_eval(p->st, p->polys, W, p->cpolys, CK, log_n, z, zg, pb(p).ood_tab, pb(p).partials, p->ood, rank, G);
         }, hv));
         std::vector<fe2> e;
-        ood_reseed_ext(coin, hv, C, R, e, h);
+        ood_reseed(coin, KX_, hv, C, R, e, h);
         stage_mark(P0, "ood");
-        const DeepConstsE D = draw_deep_consts_ext(coin, e, C, z, zg, R);
-        auto upload = [D](zk_prover *p) { return h2d_small(p, p->x_deep_consts, &D, sizeof D); };
+        const DeepConsts<KX_> D = draw_deep_consts<KX_>(coin, e, C, z, zg, R);
+        auto upload = [this, D](zk_prover *p) { return h2d_small(p, pb(p).deep_consts, &D, sizeof D); };
         if (range_split) {
-            ZK_TRY(deep_split_ranges(2, [this, z, zg](zk_prover *p, size_t k0) {
-                return deep_range_begin_ext(p->st, p->polys, p->cpolys, C, log_n, p->x_deep_consts, z, zg, p->x_dscratch,
-                                            k0, kg);
+            ZK_TRY(deep_split_ranges(KX_, [this, z, zg](zk_prover *p, size_t k0) {
+                return deep_range_begin(p->st, p->polys, p->cpolys, C, log_n, pb(p).deep_consts, z, zg, pb(p).dscratch, k0, kg);
             }, [this, z, zg](zk_prover *p, size_t k0, const fe *ext) {
-                return deep_range_end_ext(p->st, log_n, z, zg, p->x_dscratch, k0, kg, ext);
+                return deep_range_end(p->st, log_n, z, zg, pb(p).dscratch, k0, kg, ext);
             }, upload));
         } else {
             ZK_TRY(each_rank(X, [this, z, zg, upload](int l, zk_prover *p, Plan *) -> int {
                 ZK_TRY(upload(p));
-                Dk[l] = deep_poly_ext(p->st, p->polys, p->cpolys, C, log_n, p->x_deep_consts, z, zg, p->x_dscratch);
+                Dk[l] = deep_poly(p->st, p->polys, p->cpolys, C, log_n, pb(p).deep_consts, z, zg, pb(p).dscratch);
                 return ZK_OK;
             }));
         }
         return lde_deep();
     }
-    int ood_deep() { return KX == 1 ? ood_deep_base() : ood_deep_ext(); }
+    int ood_deep() {
+        return with_kx(KX, [this](auto kx) { return ood_deep_kx<decltype(kx)::value>(); });
+    }
 
     // ---- S6: FRI.  Layer 0 is sharded (its fold rows stay in one coset), and so is layer 1 when a layer follows it and
     // every rank holds enough of its rows; the next layer is all-gathered and the remaining layers run on local rank 0
@@ -1306,8 +1261,7 @@ struct ShardedProof {
         std::vector<fe> rv(KX * N);
         ZK_TRY(d2h_small(P0, rv.data(), pb(P0).fri, rv.size() * sizeof(fe)));
         ZK_TRY(d2h_flush(P0));
-        if (KX == 1) return remainder_step(rv, 8, coin, R, degree_flag);
-        return remainder_step_ext(rv, 8, coin, R, degree_flag, Y.rem_flat);
+        return remainder_step(KX, rv, 8, coin, R, degree_flag, Y.rem_flat);
     }
     // layer `layer`'s leaves (vals: this rank's cosets, log_len positions each) into tree T, the root into the coin
     int commit_sharded_layer(int layer, DistTree &T, bool ctmp, int log_len, int log_rows, const char *digests,
@@ -1326,20 +1280,11 @@ struct ShardedProof {
     }
     // alpha of `layer` from the host coin into every local rank's fold constants, then the fold over the local cosets
     int fold_sharded_layer(int layer, bool from_ctmp, int log_len, int log_rows, size_t wstride) {
-        FoldConsts F{};
-        FoldConstsE FE{};
-        if (KX == 1) {
-            const fe alpha = coin.draw();
-            fe_to_bytes(alpha, R.fri_alphas[layer]);
-            F = fold_consts(alpha, fold);
-        } else {
-            const fe2 alpha = coin.draw_ext(2);
-            fe_to_bytes(alpha.a, R.fri_alphas[layer]);
-            FE = fold_consts_ext(alpha, fold);
-        }
-        ZK_TRY(each_rank(X, [=](int, zk_prover *p, Plan *) -> int {
-            if (KX == 1) return h2d_small(p, p->fold_consts, &F, sizeof F);
-            return h2d_small(p, p->x_fold_consts, &FE, sizeof FE);
+        const fe2 alpha = coin.draw_ext(KX);
+        fe_to_bytes(alpha.a, R.fri_alphas[layer]);
+        ZK_TRY(with_kx(KX, [&](auto kx) {
+            const auto F = fold_consts<decltype(kx)::value>(alpha, fold);
+            return each_rank(X, [&](int, zk_prover *p, Plan *) -> int { return h2d_small(p, pb(p).fold_consts, &F, sizeof F); });
         }));
         return each_rank(X, [=](int l, zk_prover *p, Plan *pl) -> int {
             const Planes b = pb(p);  // layer 0 (DEEP) -> layer 1 in CTMP -> layer 2 in COMP, each [plane][j][q0]

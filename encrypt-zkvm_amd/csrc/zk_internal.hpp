@@ -1,12 +1,13 @@
 // zk_internal.hpp -- shared declarations of the gfx950 prove path (kernels.hip, prover.hip).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include <string>
 #include <vector>
 
-#include "ext2.hpp"
+#include "chal.hpp"
 #include "f128.hpp"
 
 namespace zk {
@@ -215,8 +216,6 @@ struct FriLayout {
     int lb, lcn;
 };
 FriLayout fri_layout(size_t L, int lb);
-// FRI layer leaves: row r of a layer of size L (rows = L/fold): [e[r + k*L/fold]]
-void commit_fri_layer(hipStream_t st, const fe *layer, size_t L, int fold, uint8_t *leaves, uint8_t *nodes, int lb = 0);
 // nodes[1..nl) of a binary Merkle tree over nl leaves (nodes[nl/2..nl) = merges of leaf pairs)
 void merkle_tree(hipStream_t st, const uint8_t *leaves, size_t nl, uint8_t *nodes);
 // out[k] = src[idx[k]] for 32-byte digests
@@ -309,7 +308,7 @@ void comp_cross_mapped(hipStream_t st, const CrossMap &m, const NttTables &T8n, 
 hipError_t eval_constraints(hipStream_t st, const fe *lde, int log_n, int log_b, const fe *periodic, const fe *divs,
                       const AirConsts *consts_dev, fe *comp, bool bnd = true, int nce = 8);
 // add the boundary terms' quotient polynomial (one coefficient plane K) into col0 (n coefficients);
-// c = g^(n-2); scratch: deep_poly's layout; sets *flag when an assertion fails
+// c = g^(n-2); scratch: DeepScratch (KX = 1); sets *flag when an assertion fails
 void boundary_poly_add(hipStream_t st, const fe *tpolys, int log_n, const AirConsts &K, fe c, fe *scratch, fe *col0,
                        unsigned *flag);
 // boundary_poly_add split over a sharded rank's coefficient range [k0, k0 + kn) (kn a multiple of
@@ -326,58 +325,89 @@ void comp_cross_coset(hipStream_t st, const fe *c, int log_n, const NttTables &T
                       fe scale, fe w8inv, fe inv3n, int ncols, fe *polys, unsigned *nonzero_flag);
 
 // ---------------------------------------------------------------- OOD / DEEP / FRI
-// out[p*2 + 0/1 ...]: evaluate `npolys` polys (n coeffs, stride n) at point x; partial sums per block
-// OOD frame in one pass: out = [T_c(z)]_W ++ [T_c(zg)]_W ++ [H_j(z)]_C.  tab: 128 + 2*ood_waves(n)
-// elements, partials: (2W + C) * ood_waves(n) elements of scratch.
+// Written once over the challenge field (chal.hpp): KX = 1 the base field, KX = 2 FieldExtension::Quadratic.  A
+// launcher that gets the point z takes its KX from z's type (fe or fe2); the FRI launchers, which get no point, take
+// KX as an argument.  What KX = 2 means for the buffers:
+//   * every E-valued buffer another stage reads is planar, component a at [0, M) and b at [M, 2M): the OOD partial sums
+//     (M = np nw) and frame (M = np), the DEEP coefficients (M = n) and their LDE (M = N), a FRI layer (M = L);
+//   * the composition columns stay base columns: E column j is P_2j + X P_2j+1, so the OOD `C` counts 2 C base columns
+//     while DEEP's `ccols` counts the C E columns it pairs them into;
+//   * constants in device memory (DeepConsts, FoldConsts) hold E values as (a, b) pairs.
+//
+// OOD frame in one pass: out = [T_c(z)]_W ++ [T_c(zg)]_W ++ [H_j(z)]_C, np = 2W + C values (KX planes of np).
+// tab: KX (128 + 2 ood_waves(n)) elements, partials: KX np ood_waves(n) elements of scratch.
+// (rank, G): only this rank's share of the coefficient range (waves [rank nw / G, (rank + 1) nw / G)), so that the G
+// partial sums of each value add up to it (the sharded prover all-gathers them); (0, 1) = the whole range
 int ood_waves(size_t n);
-void ood_eval(hipStream_t st, const fe *tpolys, int W, const fe *cpolys, int C, int log_n, fe z, fe zg, fe *tab,
+template <class T>
+void ood_eval(hipStream_t st, const fe *tpolys, int W, const fe *cpolys, int C, int log_n, T z, T zg, fe *tab,
               fe *partials, fe *out, int rank = 0, int G = 1);
 void sum_partials(hipStream_t st, const fe *partials, int npolys, int nblk, fe *out, int b0 = 0, int b1 = -1);
-// DEEP over the LDE domain, natural order (consts: DeepConsts in device memory)
+// DEEP constants in device memory (the combine kernel reads alpha_t and alpha_c in place)
+template <int KX>
 struct DeepConsts {
-    fe alpha_t[32];
-    fe alpha_c[16];
-    fe k1, k2, z, zg;
+    typename Chal<KX>::T alpha_t[32];
+    typename Chal<KX>::T alpha_c[16];
+    typename Chal<KX>::T k1, k2, z, zg;
 };
+static_assert(sizeof(DeepConsts<1>) == 52 * sizeof(fe) && sizeof(DeepConsts<2>) == 52 * sizeof(fe2), "DeepConsts layout");
 // LDE of one n-coefficient polynomial over `count` cosets r0 + stride*j: out[j*n ..], coset-major.  ntt_tmp: 8n.
 void lde_cosets(hipStream_t st, const NttTables &Tn, const CosetTables &CT, const fe *coeffs, size_t n, size_t r0,
                 size_t stride, int count, fe *out, fe *ntt_tmp);
-// The DEEP polynomial's coefficients (n; over E two planes of n) computed into scratch (returned)
+// The DEEP scratch for n coefficients over KX planes, in elements: 4 power tables of 2048 + H values (lo, hi halves of
+// z, zg, 1/z, 1/zg), g1 and g2 (n values each), the KX output planes of n, 2 KX sums per phase-1 block of
+// ZK_DEEP_BLOCK coefficients (after the scan: the block's carries), and a range's 2 KX totals (deep_range_*).  The
+// boundary quotient (boundary_poly_add, boundary_range_*) uses the KX = 1 layout.
+constexpr size_t ZK_DEEP_BLOCK = 256;
+struct DeepScratch {
+    size_t H;
+    fe *pw, *g1, *g2, *out, *bs, *total;
+    DeepScratch(fe *s, size_t n, int KX)
+        : H(n / 2048 + 2),  // hi[] covers every t < nb * 2048 + 8
+          pw(s),
+          g1(pw + 4 * KX * (2048 + H)),
+          g2(g1 + KX * n),
+          out(g2 + KX * n),
+          bs(out + KX * n),
+          total(bs + 2 * KX * ((n + ZK_DEEP_BLOCK - 1) / ZK_DEEP_BLOCK)) {}
+    static size_t size(size_t n, int KX) { return KX * (4 * (2048 + n / 2048 + 2) + 3 * n + 2 * (n / ZK_DEEP_BLOCK + 1)); }
+};
+// The DEEP polynomial's coefficients (KX planes of n) computed into scratch (returned); consts: DeepConsts<KX>
+template <class T>
 const fe *deep_poly(hipStream_t st, const fe *tpolys, const fe *cpolys, int ccols, int log_n,
-                    const void *deep_consts_dev, fe z, fe zg, fe *scratch);
-const fe *deep_poly_ext(hipStream_t st, const fe *tpolys, const fe *cpolys, int ccols, int log_n,
-                        const void *deep_consts_dev, fe2 z, fe2 zg, fe *scratch);
+                    const void *deep_consts_dev, T z, T zg, fe *scratch);
 // The same split by coefficient range over the ranks of a sharded proof: rank g computes the range [k0, k0 + kn)
 // (kn a multiple of ZK_DEEP_RANGE_QUANTUM) in two steps around one exchange.  deep_range_begin returns a device
-// pointer to the range's totals (2 base elements; over E 4); deep_range_end takes `ext`, the sum of the totals of
-// every later range (the suffix carried into this one), and returns the coefficient buffer (n; over E two planes of
-// n) with this range filled in.  The scratch is deep_poly's.
+// pointer to the range's totals (2 KX base elements); deep_range_end takes `ext`, the sum of the totals of every later
+// range (the suffix carried into this one), and returns the coefficient buffer with this range filled in.
 constexpr size_t ZK_DEEP_RANGE_QUANTUM = 2048;
+template <class T>
 const fe *deep_range_begin(hipStream_t st, const fe *tpolys, const fe *cpolys, int ccols, int log_n,
-                           const void *deep_consts_dev, fe z, fe zg, fe *scratch, size_t k0, size_t kn);
-const fe *deep_range_end(hipStream_t st, int log_n, fe z, fe zg, fe *scratch, size_t k0, size_t kn, const fe *ext);
-const fe *deep_range_begin_ext(hipStream_t st, const fe *tpolys, const fe *cpolys, int ccols, int log_n,
-                               const void *deep_consts_dev, fe2 z, fe2 zg, fe *scratch, size_t k0, size_t kn);
-const fe *deep_range_end_ext(hipStream_t st, int log_n, fe2 z, fe2 zg, fe *scratch, size_t k0, size_t kn,
-                             const fe *ext);
+                           const void *deep_consts_dev, T z, T zg, fe *scratch, size_t k0, size_t kn);
+template <class T>
+const fe *deep_range_end(hipStream_t st, int log_n, T z, T zg, fe *scratch, size_t k0, size_t kn, const fe *ext);
 // DEEP through coefficient form (kernels.hip): the DEEP polynomial (S - S(z))/(x - z) + (A - A(zg))/(x - zg)
-// by suffix sums over the combined coefficients, one LDE over the B cosets (CosetTables) into ulde
-// (coset-major), and (out != nullptr) a natural-order copy in out.  scratch: 4 (2048 + n/2048 + 2) + 3n + 2 ceil(n/256)
-// elements; ulde: B*n; ntt_tmp: 8n.
+// by suffix sums over the combined coefficients, one LDE per plane over the B cosets (CosetTables) into ulde
+// (coset-major, KX planes of N), and (out != nullptr) a natural-order copy in out.  scratch: DeepScratch; ntt_tmp: 8n.
+template <class T>
 void deep_coeff_launch(hipStream_t st, const NttTables &Tn, const fe *tpolys, const fe *cpolys, int ccols, int log_n,
-                       int log_b, const void *deep_consts_dev, fe z, fe zg, const CosetTables &CT, fe *scratch,
+                       int log_b, const void *deep_consts_dev, T z, T zg, const CosetTables &CT, fe *scratch,
                        fe *ulde, fe *ntt_tmp, fe *out);
-// the same over E (FieldExtension::Quadratic; DeepConstsE): scratch 8 (2048 + n/2048 + 2) + 6n + 4 ceil(n/256)
-// elements; ulde: 2*B*n; out planar (2N)
-void deep_coeff_ext_launch(hipStream_t st, const NttTables &Tn, const fe *tpolys, const fe *cpolys, int ccols,
-                           int log_n, int log_b, const void *deep_consts_dev, fe2 z, fe2 zg, const CosetTables &CT,
-                           fe *scratch, fe *ulde, fe *ntt_tmp, fe *out);
-// FRI fold: next[r] = p_r(alpha) over rows r < L/fold (consts: FoldConsts in device memory)
+// FRI fold constants in device memory; fri_coin_launch writes alpha (KX components) in place
+template <int KX>
 struct FoldConsts {
     fe zinv[16];  // zeta^-t, t < fold
-    fe alpha, inv_offset, inv_fold;
+    typename Chal<KX>::T alpha;
+    fe inv_offset, inv_fold;
 };
-void fri_fold_launch(hipStream_t st, const fe *layer, size_t L, int fold, const void *fold_consts_dev,
+static_assert(sizeof(FoldConsts<1>) == 19 * sizeof(fe) && offsetof(FoldConsts<1>, alpha) == 16 * sizeof(fe) &&
+                  offsetof(FoldConsts<2>, alpha) == 16 * sizeof(fe),
+              "FoldConsts layout");
+// FRI layer leaves: row r of a layer of L values (rows = L / fold) is [e[r + k rows]]_k, an E value hashed as (a, b)
+void commit_fri_layer(hipStream_t st, int KX, const fe *layer, size_t L, int fold, uint8_t *leaves, uint8_t *nodes,
+                      int lb = 0);
+// FRI fold: next[r] = p_r(alpha) over rows r < L / fold (consts: FoldConsts<KX> in device memory)
+void fri_fold_launch(hipStream_t st, int KX, const fe *layer, size_t L, int fold, const void *fold_consts_dev,
                      const NttTables &TN, size_t wstride, fe *next, int lb = 0);
 void coset_major_to_natural(hipStream_t st, const fe *src, int log_n, int log_b, fe *dst);
 // FRI commit-phase coin on the device: seed = merge(seed, root_dev), alpha (k = 1 or 2 components) drawn
@@ -386,36 +416,12 @@ void coset_major_to_natural(hipStream_t st, const fe *src, int log_n, int log_b,
 void fri_coin_launch(hipStream_t st, uint32_t *seed_dev, const uint8_t *root_dev, int k, fe *alpha_dev,
                      fe *alpha_log);
 
-// ---------------------------------------------------------------- FieldExtension::Quadratic (ext2.hpp)
-// Every E-valued buffer is planar: component a at [0, M), component b at [M, 2M).
-// OOD frame over E points: out[j*np + P], np = 2W + C, component j of poly P's value (T(z), T(zg), H(z));
-// tab: 2 * (128 + 2 * ood_waves(n)) fe, partials: 2 * np * ood_waves(n) fe.
-void ood_eval_ext(hipStream_t st, const fe *tpolys, int W, const fe *cpolys, int C, int log_n, fe2 z, fe2 zg,
-                  fe *tab, fe *partials, fe *out, int rank = 0, int G = 1);
 // composition over E: consts2_dev = {a components, b components}; planes comp[0, 8n), comp[8n, 16n)
 hipError_t eval_constraints_ext(hipStream_t st, const fe *lde, int log_n, int log_b, const fe *periodic, const fe *divs,
                           const AirConsts *consts2_dev, fe *comp, bool bnd = true, int nce = 8);
 // ... over the CE cosets of `map` (see eval_constraints_mapped), b plane at comp + plane
 hipError_t eval_constraints_ext_mapped(hipStream_t st, const fe *lde, int log_n, EvalMap map, const fe *periodic,
                                  const fe *divs, const AirConsts *consts2_dev, size_t plane, fe *comp, bool bnd = true);
-// out[i] = 1 / (N(x_i - z) N(x_i - zg)), N the norm E -> F (coset-major like batch_inv_pairs)
-void batch_inv_norm_pairs(hipStream_t st, const NttTables &Tn, const fe *xr, int log_b, int log_n, fe2 z, fe2 zg,
-                          fe *out);
-struct DeepConstsE {
-    fe2 alpha_t[32];
-    fe2 alpha_c[16];
-    fe2 k1, k2, z, zg;
-    fe zb2, zgb2;  // z.b^2, zg.b^2
-};
-struct FoldConstsE {
-    fe zinv[16];
-    fe2 alpha;
-    fe inv_offset, inv_fold;
-};
-// layer planar (2L), next planar (2 L/fold); leaves hash rows of fold E values (a, b per value)
-void commit_fri_layer_ext(hipStream_t st, const fe *layer, size_t L, int fold, uint8_t *leaves, uint8_t *nodes, int lb = 0);
-void fri_fold_ext_launch(hipStream_t st, const fe *layer, size_t L, int fold, const void *fold_consts_dev,
-                         const NttTables &TN, size_t wstride, fe *next, int lb = 0);
 // out[k] = src[idx[k]] for field elements
 void gather_fe(hipStream_t st, const fe *src, const uint64_t *idx, size_t k, fe *out);
 

@@ -286,6 +286,11 @@ def lib():
             L.zk_diag_deep.argtypes = [i32, vp, vp, i32, sz, i32, vp, vp, vp, vp, vp]
             # (device, seed32, start, count, bits, best_out)
             L.zk_diag_grind.argtypes = [i32, vp, C.c_uint64, u32, i32, C.POINTER(C.c_uint64)]
+        if hasattr(L, "zk_diag_fri_layer"):
+            # (device, tpolys, cpolys, ccols, n, ext, z, zg, alpha_t, alpha_c, parts, out)
+            L.zk_diag_deep_parts.argtypes = [i32, vp, vp, i32, sz, i32, vp, vp, vp, vp, i32, vp]
+            # (device, layer, L, ext, fold, lb, wstride, alpha, root_out, next_out)
+            L.zk_diag_fri_layer.argtypes = [i32, vp, sz, i32, i32, i32, sz, vp, vp, vp]
         _lib = L
     return _lib
 

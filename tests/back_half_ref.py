@@ -9,7 +9,9 @@ quadratic extension E = F[X] / (X^2 - X - 1), over pairs (a, b) = a + b X:
   * the grinding search: BLAKE3(seed || nonce_le64), the trailing zero bits of its first little-endian u64, the
     smallest hit of a window;
   * BatchMerkleProof::get_root: the root rebuilt from opened rows, their positions and the serialized batch proof
-    (u8 number of paths, per path u8 length and 32-byte digests: what verifier.cpp parses and wire.py cuts out).
+    (u8 number of paths, per path u8 length and 32-byte digests: what verifier.cpp parses and wire.py cuts out);
+  * one FRI layer: its rows, their Merkle root by pairwise merges, and the fold: per row the interpolant of the
+    `fold` values over x_r <zeta> evaluated at alpha by Lagrange's formula (over E by components).
 
 The hash is the CPU oracle's BLAKE3 (oracle.blake3, pinned against the specification by tests/test_blake3_pin.py);
 tests/test_back_half_ref_cpu.py checks each part of this file against the oracle and the golden proofs.
@@ -280,3 +282,59 @@ def row_digest(blake3, row):
     if isinstance(row, (bytes, bytearray)):
         return blake3(bytes(row))
     return blake3(b"".join(int(v).to_bytes(16, "little") for v in row))
+
+
+# ---------------------------------------------------------------- one FRI layer
+TWO_ADIC_ROOT = pow(3, (P - 1) >> 40, P)  # order 2^40; w_L = TWO_ADIC_ROOT^(2^40 / L)
+FRI_OFFSET = 3
+
+
+def fri_rows(layer, fold):
+    """row r of a layer of L values (natural order): [layer[r + k L / fold]] for k < fold, the values at x_r zeta^k"""
+    rows = len(layer) // fold
+    return [[layer[r + k * rows] for k in range(fold)] for r in range(rows)]
+
+
+def interp_eval(xs, vs, alpha, ext):
+    """the polynomial of degree < len(xs) through (xs[k], vs[k]) (base points; base or E values), evaluated at alpha,
+    by Lagrange's formula: the interpolation is F-linear, so over E it is taken by components"""
+    inv = [pow(prod_mod(xs[k] - xs[j] for j in range(len(xs)) if j != k), P - 2, P) for k in range(len(xs))]
+    if ext == 1:
+        return sum(v * w % P * prod_mod(alpha - xs[j] for j in range(len(xs)) if j != k)
+                   for k, (v, w) in enumerate(zip(vs, inv))) % P
+    acc = (0, 0)
+    for k, (v, w) in enumerate(zip(vs, inv)):
+        num = (1, 0)
+        for j in range(len(xs)):
+            if j != k:
+                num = e_mul(num, e_sub(alpha, (xs[j], 0)))
+        acc = e_add(acc, e_mul(num, (v[0] * w % P, v[1] * w % P)))
+    return acc
+
+
+def prod_mod(values):
+    r = 1
+    for v in values:
+        r = r * v % P
+    return r
+
+
+def fri_fold(layer, fold, alpha, ext):
+    """the next layer: entry r is the interpolant of row r over x_r <zeta> at alpha, x_r = 3 w_L^r, zeta = w_fold"""
+    L = len(layer)
+    w = pow(TWO_ADIC_ROOT, (1 << 40) // L, P)
+    zeta = pow(TWO_ADIC_ROOT, (1 << 40) // fold, P)
+    zs = powers(zeta, fold)
+    out, x = [], FRI_OFFSET
+    for row in fri_rows(layer, fold):
+        out.append(interp_eval([x * t % P for t in zs], row, alpha, ext))
+        x = x * w % P
+    return out
+
+
+def fri_layer_root(blake3, layer, fold, ext):
+    """the Merkle root over the rows' digests (a row's E values hashed as a, b per value), by pairwise merges"""
+    level = [row_digest(blake3, row if ext == 1 else [c for v in row for c in v]) for row in fri_rows(layer, fold)]
+    while len(level) > 1:
+        level = [blake3(level[i] + level[i + 1]) for i in range(0, len(level), 2)]
+    return level[0]

@@ -178,6 +178,54 @@ def test_batch_checker_on_a_small_tree(oracle):
         ref.batch_root(b3, [leaves[0], leaves[7]], [0, 7], proof[:-32], 3)
 
 
+@pytest.mark.parametrize("ext", [1, 2])
+@pytest.mark.parametrize("fold", [2, 4, 8, 16])
+def test_fri_fold_matches_oracle_interpolation(oracle, fold, ext):
+    """Every row of a layer: the oracle interpolates the row's `fold` values over the coset x_r <zeta> (per component
+    over E) and Horner's rule evaluates the coefficients at alpha."""
+    rnd = random.Random(100 * fold + ext)
+    L = 8 * fold
+    draw = (lambda: rnd.randrange(P)) if ext == 1 else (lambda: rand_e(rnd))
+    layer = [draw() for _ in range(L)]
+    w = oracle.root_of_unity(L.bit_length() - 1)
+    assert w == pow(ref.TWO_ADIC_ROOT, (1 << 40) // L, P)
+    for alpha in (draw(), 0 if ext == 1 else (0, 0), 1 if ext == 1 else (0, 1)):
+        got = ref.fri_fold(layer, fold, alpha, ext)
+        assert len(got) == L // fold
+        for r, row in enumerate(ref.fri_rows(layer, fold)):
+            x = 3 * pow(w, r, P) % P
+            if ext == 1:
+                assert got[r] == ref.horner(oracle.interp_coset(row, x), alpha), (r, alpha)
+            else:
+                ca, cb = oracle.interp_coset([v[0] for v in row], x), oracle.interp_coset([v[1] for v in row], x)
+                assert got[r] == ref.horner_ext(list(zip(ca, cb)), alpha), (r, alpha)
+    # a row's points are x_r zeta^k: the values of X^m there interpolate back to alpha^m
+    zeta = oracle.root_of_unity(fold.bit_length() - 1)
+    xs = [3 * pow(zeta, k, P) % P for k in range(fold)]
+    a = rnd.randrange(P)
+    assert ref.interp_eval(xs, [pow(x, fold - 1, P) for x in xs], a, 1) == pow(a, fold - 1, P)
+
+
+@pytest.mark.parametrize("name", ["pushadd12", "cipher8_b16_f4", "pushadd12_f2_r7", "lr_f16_r15"])
+def test_fri_fold_reproduces_an_oracle_proofs_first_layer(oracle, name):
+    """Folding the DEEP evaluations an oracle proof dumps at the recorded first alpha gives the first folded layer it
+    dumps, and the layer's root is the recorded one (base field: the dump carries only the a component over E)."""
+    import numpy as np
+
+    c = CASES[name]
+    trace = np.load(GOLD / f"{name}.trace.npy", allow_pickle=False)
+    ints = lambda hs: [int(h, 16) for h in hs]
+    pub = oracle.make_pub(ints(c["program_hash"]), ints(c["stack_outputs"]), c["lwe_size"], c["delta"])
+    _, rec, dumps = oracle.prove(trace, pub, oracle.default_options(**c["options"]), want=("deep", "fri_layer1"))
+    assert rec.num_fri_layers >= 1 and c["options"]["field_extension"] == 1
+    fold = c["options"]["fri_folding"]
+    val = lambda a: [int(lo) | int(hi) << 64 for lo, hi in a]
+    deep, layer1 = val(dumps["deep"]), val(dumps["fri_layer1"])
+    alpha = int.from_bytes(bytes(rec.fri_alphas)[:16], "little")
+    assert ref.fri_fold(deep, fold, alpha, 1) == layer1
+    assert ref.fri_layer_root(oracle.blake3, deep, fold, 1) == bytes(rec.fri_roots)[:32]
+
+
 @pytest.mark.parametrize("name", ["lr_grind10_q28", "cipher8_quad_f2_g9"])
 def test_grinding_reference_finds_the_golden_nonce(oracle, name):
     """The seed a golden proof ground on, replayed from the proof's own sections: the reference's search from 1

@@ -1,7 +1,9 @@
 """The back half of a proof, each stage called directly on the GPU at its edges: the out-of-domain frame
-(zk_diag_ood: ood_eval / ood_eval_ext), the DEEP quotient (zk_diag_deep: deep_poly / deep_poly_ext), the grinding
+(zk_diag_ood: ood_eval), the DEEP quotient (zk_diag_deep: deep_poly), the grinding
 search (zk_diag_grind: one grind_launch; and whole proofs whose search crosses the host / GPU threshold and the first
-2^22 batch) and the batch openings of the plug points (zk_lde_query, zk_comp_query, zk_lde_read_frame).
+2^22 batch) and the batch openings of the plug points (zk_lde_query, zk_comp_query, zk_lde_read_frame); the DEEP
+quotient by coefficient ranges as a sharded proof's ranks compute it (zk_diag_deep_parts) and one FRI layer, committed
+and folded (zk_diag_fri_layer).
 
 Whole proofs feed these stages what a valid trace and the coin give, at the trace lengths the VM makes (64 rows and
 up).  Here the inputs are chosen: trace lengths 16 and 32, points on the trace domain and of small order, polynomials
@@ -200,12 +202,16 @@ def test_ood_and_deep_refuse_bad_arguments():
 
 
 # ---------------------------------------------------------------- DEEP
-def run_deep(tp, cp, n, ext, z, zg, at, ac):
+def run_deep(tp, cp, n, ext, z, zg, at, ac, parts=1):
+    """zk_diag_deep, or with parts > 1 zk_diag_deep_parts: the same quotient by coefficient ranges"""
     assert native.device_count() > 0, "no GPU visible"
     out = C.create_string_buffer(16 * ext * n)
     flat = (lambda v: elems(v)) if ext == 1 else (lambda v: elems([c for pair in v for c in pair]))
-    native.check(native.lib().zk_diag_deep(0, cols_bytes(tp), cols_bytes(cp), len(cp), n, ext, point_bytes(z, ext),
-                                           point_bytes(zg, ext), flat(at), flat(ac), out), "zk_diag_deep")
+    args = (0, cols_bytes(tp), cols_bytes(cp), len(cp), n, ext, point_bytes(z, ext), point_bytes(zg, ext), flat(at), flat(ac))
+    if parts == 1:
+        native.check(native.lib().zk_diag_deep(*args, out), "zk_diag_deep")
+    else:
+        native.check(native.lib().zk_diag_deep_parts(*args, parts, out), "zk_diag_deep_parts")
     v = ref_ints(out.raw)
     return v if ext == 1 else list(zip(v[:n], v[n:]))
 
@@ -303,6 +309,171 @@ def test_deep_polynomial_classes(n, ext, part):
         check_deep([unit(n, k)] * 28, [[0] * n] * ccols, n, ext, z, zg, at, ac, f"n={n} ext={ext} trace only, k={k}")
         return
     check_deep([[0] * n] * 28, [unit(n, k)] * ccols, n, ext, z, zg, at, ac, f"n={n} ext={ext} composition only, k={k}")
+
+
+# ---------------------------------------------------------------- DEEP by coefficient ranges
+def same_polys(poly, count):
+    """`count` copies of one polynomial, encoded once"""
+    ps = Polys([poly] * count)
+    ps.encoded = elems(poly) * count
+    return ps
+
+
+RANGE_CLASSES = ["random", "all 0", "all p-1", "before first boundary", "first boundary", "before last boundary",
+                 "last boundary", "top", "random at boundary"]
+
+
+@pytest.mark.parametrize("kind", RANGE_CLASSES)
+@pytest.mark.parametrize("ext", [1, 2])
+@pytest.mark.parametrize("n,parts", [(4096, 2), (8192, 4), (16384, 8)])
+def test_deep_by_coefficient_ranges(n, parts, ext, kind):
+    """deep_range_begin for every range, the later ranges' totals summed, deep_range_end for every range (a sharded
+    proof's ranks on one device): the coefficients equal deep_poly's and the reference quotient.  A range is a whole
+    number of 2048-coefficient chunks, so 4096 / 2 is the smallest split.  The polynomial classes of
+    test_deep_polynomial_classes with the single coefficient at each side of a range boundary k0 = n / parts and
+    n - n / parts (its suffix sum is carried into every earlier range, or into none) and at n - 1."""
+    rnd = random.Random(4000 * ext + n + RANGE_CLASSES.index(kind))
+    ccols = 8 * ext
+    draw = draw_fn(rnd, ext)
+    at, ac = [draw() for _ in range(28)], [draw() for _ in range(ccols // ext)]
+    pts = ood_points(rnd, n, ext)
+    w, g = root_of_unity(11), root_of_unity(n.bit_length() - 1)
+    pts.append(("order2048", lift(w, ext), lift(w * g % P, ext)))
+    pname, z, zg = pts[RANGE_CLASSES.index(kind) % len(pts)]
+    kn = n // parts
+    at_k = {"before first boundary": kn - 1, "first boundary": kn, "before last boundary": n - kn - 1,
+            "last boundary": n - kn, "top": n - 1, "random at boundary": n - kn}
+    if kind == "random":
+        tp = Polys([rnd.randrange(P) for _ in range(n)] for _ in range(28))
+        cp = Polys([rnd.randrange(P) for _ in range(n)] for _ in range(ccols))
+    else:
+        poly = {"all 0": [0] * n, "all p-1": [P - 1] * n}.get(kind) or \
+            unit(n, at_k[kind], rnd.randrange(1, P) if kind.startswith("random") else 1)
+        tp, cp = same_polys(poly, 28), same_polys(poly, ccols)
+    what = f"n={n} parts={parts} ext={ext} polynomials {kind} at point {pname}"
+    whole = check_deep(tp, cp, n, ext, z, zg, at, ac, what + " (one range)")
+    split = run_deep(tp, cp, n, ext, z, zg, at, ac, parts)
+    bad = [k for k in range(n) if split[k] != whole[k]]
+    assert not bad, f"{what}: {len(bad)} coefficients differ from the one-range result, the first at k = {bad[:6]}"
+    if kind == "all 0":
+        assert split == [0 if ext == 1 else (0, 0)] * n
+
+
+def test_deep_by_ranges_refuses_bad_arguments():
+    L = native.lib()
+    n = 4096
+    tp, cp = bytes(16 * 28 * n), bytes(16 * 2 * n)
+    one, al, out = elems([1, 0]), elems([1, 0] * 28), C.create_string_buffer(32 * n)
+    for parts in (0, 1, 3, 4, 16):  # (4 ranges of 4096 coefficients would be 1024 each)
+        rc = L.zk_diag_deep_parts(0, tp, cp, 2, n, 2, one, one, al, al, parts, out)
+        assert rc == native.ZK_ERR_INVALID_ARG and L.zk_last_error(), parts
+    native.check(L.zk_diag_deep_parts(0, tp, cp, 2, n, 2, one, one, al, al, 2, out))
+    assert out.raw == bytes(32 * n)
+
+
+# ---------------------------------------------------------------- one FRI layer: commit, then fold
+def fri_store(layer, lb):
+    """natural order -> the order the kernels read (FriLayout): index i at (i mod 2^lb) L / 2^lb + i / 2^lb"""
+    L = len(layer)
+    out = [None] * L
+    for i, v in enumerate(layer):
+        out[(i & ((1 << lb) - 1)) * (L >> lb) + (i >> lb)] = v
+    return out
+
+
+def run_fri_layer(layer, ext, fold, lb, wstride, alpha):
+    """(root, next layer) of zk_diag_fri_layer; layer in natural order (ints; over E pairs)"""
+    assert native.device_count() > 0, "no GPU visible"
+    L = len(layer)
+    stored = fri_store(layer, lb)
+    data = elems(stored) if ext == 1 else elems([v[0] for v in stored]) + elems([v[1] for v in stored])
+    root, nxt = C.create_string_buffer(32), C.create_string_buffer(16 * ext * (L // fold))
+    native.check(native.lib().zk_diag_fri_layer(0, data, L, ext, fold, lb, wstride, point_bytes(alpha, ext), root, nxt),
+                 "zk_diag_fri_layer")
+    v = ref_ints(nxt.raw)
+    return root.raw, v if ext == 1 else list(zip(v[:L // fold], v[L // fold:]))
+
+
+def fri_layers(rnd, L, ext):
+    """(name, layer): random, all 0, all p - 1 and a single non-zero entry"""
+    draw = draw_fn(rnd, ext)
+    zero, top = lift(0, ext), (P - 1 if ext == 1 else (P - 1, P - 1))
+    single = [zero] * L
+    single[rnd.randrange(L)] = draw()
+    return [("random", [draw() for _ in range(L)]), ("all 0", [zero] * L), ("all p-1", [top] * L), ("single", single)]
+
+
+def fri_alphas(rnd, ext):
+    """random, 0 and 1; over E also a = 0 and b = 0"""
+    if ext == 1:
+        return [rnd.randrange(P), 0, 1]
+    return [(rnd.randrange(P), rnd.randrange(P)), (0, 0), (1, 0), (0, rnd.randrange(1, P)), (rnd.randrange(1, P), 0)]
+
+
+def check_fri_layer(oracle, layer, ext, fold, lb, wstride, alpha, what, want=None):
+    root, nxt = run_fri_layer(layer, ext, fold, lb, wstride, alpha)
+    want_root, want_next = want or (ref.fri_layer_root(oracle.blake3, layer, fold, ext), ref.fri_fold(layer, fold, alpha, ext))
+    assert root == want_root, f"{what}: the layer's root differs"
+    bad = [r for r in range(len(want_next)) if nxt[r] != want_next[r]]
+    assert not bad, f"{what}: {len(bad)} folded values differ, the first at r = {bad[:6]}"
+
+
+@pytest.mark.parametrize("lb", [0, 3])
+@pytest.mark.parametrize("ext", [1, 2])
+@pytest.mark.parametrize("fold", [2, 4, 8, 16])
+def test_fri_layer_smallest_tree(oracle, fold, ext, lb):
+    """L = 16 fold: 16 rows, the smallest tree with more than one level; natural order and the coset-major order of a
+    layer 0 with B = 8.  Every value class at a random alpha, every alpha class on the
+    random layer.  (x_r comes from the tables of a plan of at least 128 points, so wstride = max(1, 128 / L).)"""
+    rnd = random.Random(5000 * ext + 10 * fold + lb)
+    L = 16 * fold
+    wstride = max(1, 128 // L)
+    layers, alphas = fri_layers(rnd, L, ext), fri_alphas(rnd, ext)
+    for name, layer in layers:
+        check_fri_layer(oracle, layer, ext, fold, lb, wstride, alphas[0], f"fold={fold} ext={ext} lb={lb} values {name}")
+    root = ref.fri_layer_root(oracle.blake3, layers[0][1], fold, ext)
+    for alpha in alphas[1:]:
+        want = (root, ref.fri_fold(layers[0][1], fold, alpha, ext))
+        check_fri_layer(oracle, layers[0][1], ext, fold, lb, wstride, alpha, f"fold={fold} ext={ext} lb={lb} alpha {alpha}",
+                        want)
+    if ext == 2:  # a layer of lifted base values folds to the base fold, lifted
+        base = [v[0] for v in layers[0][1]]
+        a = alphas[4]
+        _, nxt = run_fri_layer([(v, 0) for v in base], 2, fold, lb, wstride, a)
+        assert nxt == [(v, 0) for v in ref.fri_fold(base, fold, a[0], 1)]
+
+
+@pytest.mark.parametrize("lb", [0, 3])
+@pytest.mark.parametrize("ext", [1, 2])
+def test_fri_layer_rows_past_the_split_tables_low_half(oracle, ext, lb):
+    """L = 8192, fold 2, wstride 1: the rows 2048 .. 4095 take 1 / x_r from the hi half of pow_split's tables."""
+    rnd = random.Random(6000 + 10 * ext + lb)
+    name, layer = fri_layers(rnd, 8192, ext)[0]
+    check_fri_layer(oracle, layer, ext, 2, lb, 1, fri_alphas(rnd, ext)[0], f"L=8192 ext={ext} lb={lb}")
+
+
+@pytest.mark.parametrize("ext", [1, 2])
+@pytest.mark.parametrize("fold", [2, 4, 8, 16])
+def test_fri_layer_later_layer(oracle, fold, ext):
+    """L = 1024 on a plan of N = 8192 points (wstride 8): a later layer, natural order."""
+    rnd = random.Random(7000 + 10 * fold + ext)
+    name, layer = fri_layers(rnd, 1024, ext)[0]
+    check_fri_layer(oracle, layer, ext, fold, 0, 8, fri_alphas(rnd, ext)[0], f"L=1024 wstride=8 fold={fold} ext={ext}")
+
+
+def test_fri_layer_refuses_bad_arguments():
+    F = native.lib().zk_diag_fri_layer
+    layer, one = bytes(32 * 256), elems([1, 0])
+    root, nxt = C.create_string_buffer(32), C.create_string_buffer(32 * 128)
+    good = dict(L=256, ext=1, fold=4, lb=0, wstride=1, alpha=one)
+    for kw in (dict(L=192), dict(L=64, wstride=1), dict(ext=3), dict(fold=3), dict(fold=32), dict(wstride=3), dict(wstride=0),
+               dict(lb=-1), dict(lb=7), dict(L=8, fold=4, wstride=16), dict(alpha=elems([P, 0])),
+               dict(ext=2, alpha=elems([1, P])), dict(alpha=None)):
+        a = dict(good)
+        a.update(kw)
+        rc = F(0, layer, a["L"], a["ext"], a["fold"], a["lb"], a["wstride"], a["alpha"], root, nxt)
+        assert rc == native.ZK_ERR_INVALID_ARG and native.lib().zk_last_error(), kw
+    assert F(0, None, 256, 1, 4, 0, 1, one, root, nxt) == native.ZK_ERR_INVALID_ARG
 
 
 # ---------------------------------------------------------------- grinding, one launch

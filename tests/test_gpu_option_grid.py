@@ -49,8 +49,8 @@ def test_small_and_extreme_shapes(oracle, case, name):
 @pytest.mark.parametrize("name", list(SMALL_PROGRAMS))
 @pytest.mark.parametrize("case", OVERFOLDED, ids=case_id)
 def test_overfolded_options_are_a_degree_error(oracle, case, name):
-    """The last layer is shorter than the blowup, so the remainder has no coefficient (remainder_step /
-    remainder_step_ext: rl = L / B = 0; every interpolated coefficient counts as beyond the degree bound, nothing is
+    """The last layer is shorter than the blowup, so the remainder has no coefficient (remainder_step:
+    rl = L / B = 0; every interpolated coefficient counts as beyond the degree bound, nothing is
     written to the record's remainder, the empty remainder is hashed and serialized as zero bytes).  The oracle gives
     its degree error with remainder_len 0; so must the GPU, and its next proof with default options is the oracle's."""
     trace, pub = small_trace(name)
