@@ -2254,21 +2254,30 @@ __global__ void k_ood_tables(typename Chal<KX>::T z, typename Chal<KX>::T zg, ui
     tab[t] = Chal<KX>::exp(x, e);
 }
 
-// C counts base columns (over E: 2 per composition column); np = 2W + C values per plane of partials
+// The polynomials of one launch (host-built from the trace columns' CoeffSrc and the composition columns): poly i's n
+// coefficients and the partials rows of its values at z and at zg.  The first count2 entries are evaluated at both
+// points (trace planes, e_(n-1)), the rest at z alone (the composition columns); blockIdx.y picks OOD_GROUP consecutive
+// entries of one kind, so a block's loop is the same for all its polynomials.  zero: the trace columns without a plane
+// (CoeffSrc::ZERO), whose rows c and W + c are set to zero.  np values per plane of partials.
+struct OodPolys {
+    static constexpr int MAXP = CoeffSrc::MAXC + 16 + 1;
+    int count, count2;
+    uint32_t zero;
+    const fe *poly[MAXP];
+    uint8_t rz[MAXP], rg[MAXP];
+};
 template <int KX, int E>
-__global__ void __launch_bounds__(256) k_ood_eval(const fe *tpolys, int W, const fe *cpolys, int C, size_t n,
-                                                  const typename Chal<KX>::T *tab, int nw, int w0, int w1,
-                                                  fe *partials) {
+__global__ void __launch_bounds__(256) k_ood_eval(OodPolys L, int W, int np, size_t n, const typename Chal<KX>::T *tab,
+                                                  int nw, int w0, int w1, fe *partials) {
     typedef Chal<KX> X;
     typedef typename X::T T;
     const int gw = w0 + (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);  // waves [w0, w1) of nw
     const int lane = threadIdx.x & 63;
-    const size_t plane = (size_t)(2 * W + C) * nw;
-    const int tgroups = (W + OOD_GROUP - 1) / OOD_GROUP;
-    const int g = blockIdx.y;
-    const bool comp = g >= tgroups;
-    const int p0 = comp ? 0 : g * OOD_GROUP;
-    const int p1 = comp ? C : min(W, p0 + OOD_GROUP);
+    const size_t plane = (size_t)np * nw;
+    const int tg = (L.count2 + OOD_GROUP - 1) / OOD_GROUP, g = blockIdx.y;
+    const bool two = g < tg;
+    const int p0 = two ? g * OOD_GROUP : L.count2 + (g - tg) * OOD_GROUP;
+    const int p1 = min(two ? L.count2 : L.count, p0 + OOD_GROUP);
     const size_t base = (size_t)gw * 64 * E + lane;
     // a lane's E coefficients sit 64 apart: sum_e v_e (x^64)^e as a lazy dot product against the powers
     // (x^64)^e in LDS (one unreduced product per coefficient instead of a reduced Horner step)
@@ -2280,21 +2289,24 @@ __global__ void __launch_bounds__(256) k_ood_eval(const fe *tpolys, int W, const
     }
     __syncthreads();
     if (gw >= w1) return;
+    if (blockIdx.y == 0 && L.zero && lane == 0)
+        for (int c = 0; c < W; c++)
+            if ((L.zero >> c) & 1u) {
+                X::st(partials + (size_t)c * nw + gw, plane, X::zero());
+                X::st(partials + (size_t)(W + c) * nw + gw, plane, X::zero());
+            }
     const T wz = X::mul(tab[lane], tab[128 + gw]);
-    const T wzg = comp ? X::zero() : X::mul(tab[64 + lane], tab[128 + nw + gw]);
+    const T wzg = two ? X::mul(tab[64 + lane], tab[128 + nw + gw]) : X::zero();
     for (int p = p0; p < p1; p++) {
-        const fe *c = (comp ? cpolys : tpolys) + (size_t)p * n;
+        const fe *c = L.poly[p] + base;  // (one address per lane, the E loads at constant offsets from it)
         fe v[E];
 #pragma unroll
-        for (int e = 0; e < E; e++) {
-            const size_t k = base + 64 * (size_t)e;
-            v[e] = k < n ? c[k] : fe_zero();
-        }
+        for (int e = 0; e < E; e++) v[e] = base + 64 * (size_t)e < n ? c[64 * e] : fe_zero();
         const T hz = wave_sum(X::mul(dot_base<E>(v, Y[0]), wz));
-        if (lane == 0) X::st(partials + (size_t)(comp ? 2 * W + p : p) * nw + gw, plane, hz);
-        if (!comp) {
+        if (lane == 0) X::st(partials + (size_t)L.rz[p] * nw + gw, plane, hz);
+        if (two) {
             const T hg = wave_sum(X::mul(dot_base<E>(v, Y[1]), wzg));
-            if (lane == 0) X::st(partials + (size_t)(W + p) * nw + gw, plane, hg);
+            if (lane == 0) X::st(partials + (size_t)L.rg[p] * nw + gw, plane, hg);
         }
     }
 }
@@ -2302,7 +2314,7 @@ __global__ void __launch_bounds__(256) k_ood_eval(const fe *tpolys, int W, const
 int ood_waves(size_t n) { return (int)std::max<size_t>(1, n / 1024); }
 
 template <class T>
-void ood_eval(hipStream_t st, const fe *tpolys, int W, const fe *cpolys, int C, int log_n, T z, T zg, fe *tab,
+void ood_eval(hipStream_t st, const CoeffSrc &S, int W, const fe *cpolys, int C, int log_n, T z, T zg, fe *tab,
               fe *partials, fe *out, int rank, int G) {
     constexpr int KX = ChalOf<T>::KX;
     const size_t n = (size_t)1 << log_n;
@@ -2311,10 +2323,25 @@ void ood_eval(hipStream_t st, const fe *tpolys, int W, const fe *cpolys, int C, 
     const int w0 = (int)((int64_t)nw * rank / G), w1 = (int)((int64_t)nw * (rank + 1) / G);
     T *t = reinterpret_cast<T *>(tab);
     hipLaunchKernelGGL(k_ood_tables<KX>, dim3(cdiv(128 + 2 * nw, 256)), dim3(256), 0, st, z, zg, (uint64_t)64 * E, nw, t);
-    const dim3 grid(std::max(1u, cdiv(w1 - w0, 4)), (W + OOD_GROUP - 1) / OOD_GROUP + 1);
+    // every column's plane but the ZERO ones', e_(n-1) (rows np - 2, np - 1), the composition columns
+    const int np = ood_out_values(S, W, C);
+    OodPolys L{};
+    auto add = [&L](const fe *poly, int rz, int rg) {
+        L.poly[L.count] = poly, L.rz[L.count] = (uint8_t)rz, L.rg[L.count] = (uint8_t)rg;
+        L.count++;
+    };
+    for (int c = 0; c < W; c++) {
+        if (S.mode[c] == CoeffSrc::ZERO) L.zero |= 1u << c;
+        else add(S.plane[c], c, W + c);
+    }
+    if (S.lagr) add(S.lagr, np - 2, np - 1);
+    L.count2 = L.count;
+    for (int j = 0; j < C; j++) add(cpolys + (size_t)j * n, 2 * W + j, 0);
+    const dim3 grid(std::max(1u, cdiv(w1 - w0, 4)),
+                    (L.count2 + OOD_GROUP - 1) / OOD_GROUP + (L.count - L.count2 + OOD_GROUP - 1) / OOD_GROUP);
     const char *name = KX == 1 ? "ood_eval" : "ood_eval_ext";
-#define ZK_OOD(EE) ZK_PROF(st, name, bytes, hipLaunchKernelGGL((k_ood_eval<KX, EE>), grid, dim3(256), 0, st, tpolys, W, cpolys, C, n, t, nw, w0, w1, partials))
-    const double bytes = 16.0 * (W + C) * (double)n * (w1 - w0) / nw;
+#define ZK_OOD(EE) ZK_PROF(st, name, bytes, hipLaunchKernelGGL((k_ood_eval<KX, EE>), grid, dim3(256), 0, st, L, W, np, n, t, nw, w0, w1, partials))
+    const double bytes = 16.0 * L.count * (double)n * (w1 - w0) / nw;
     switch (E) {
         case 16: ZK_OOD(16); break;
         case 8: ZK_OOD(8); break;
@@ -2323,10 +2350,26 @@ void ood_eval(hipStream_t st, const fe *tpolys, int W, const fe *cpolys, int C, 
         default: ZK_OOD(1); break;
     }
 #undef ZK_OOD
-    sum_partials(st, partials, KX * (2 * W + C), nw, out, w0, w1);
+    sum_partials(st, partials, KX * ood_out_values(S, W, C), nw, out, w0, w1);
 }
-template void ood_eval<fe>(hipStream_t, const fe *, int, const fe *, int, int, fe, fe, fe *, fe *, fe *, int, int);
-template void ood_eval<fe2>(hipStream_t, const fe *, int, const fe *, int, int, fe2, fe2, fe *, fe *, fe *, int, int);
+template void ood_eval<fe>(hipStream_t, const CoeffSrc &, int, const fe *, int, int, fe, fe, fe *, fe *, fe *, int, int);
+template void ood_eval<fe2>(hipStream_t, const CoeffSrc &, int, const fe *, int, int, fe2, fe2, fe *, fe *, fe *, int, int);
+
+void ood_fold_sources(int KX, int W, int C, const CoeffSrc &S, const fe *w, const fe *raw, fe *hv) {
+    const int np = 2 * W + C, nr = ood_out_values(S, W, C);
+    for (int j = 0; j < KX; j++) {
+        const fe *r = raw + (size_t)j * nr;
+        fe *h = hv + (size_t)j * np;
+        for (int i = 0; i < np; i++) h[i] = r[i];
+        if (!S.lagr) continue;
+        const fe ez = r[np], ezg = r[np + 1];  // component j of e(z), e(zg)
+        for (int c = 0; c < W; c++) {
+            if (!S.derived(c)) continue;
+            h[c] = fe_add(h[c], fe_mul(w[c], ez));
+            h[W + c] = fe_add(h[W + c], fe_mul(w[c], ezg));
+        }
+    }
+}
 
 __global__ void k_sum_partials(const fe *partials, int nblk, int b0, int b1, fe *out) {
     __shared__ fe red[256];
@@ -2389,8 +2432,10 @@ __device__ __forceinline__ fe block_sum256(fe v, fe *red) {
 
 // phase 1: g1, g2 and per-256 totals (one coefficient per thread)
 // [kbase, kend): the coefficient range of this launch (a sharded rank's share; 0, n otherwise); n is the column stride
+// TS: the trace columns' sources (CoeffSrc): the planes of the PLAIN and BASE columns, and with TS.lagr the one term
+// alpha_t[ZK_DEEP_LAGR] e_(n-1)[k] that carries every BASE and ZERO column's w_c e_(n-1) (one lazy sum: the same value)
 template <int KX>
-__global__ void __launch_bounds__(DIV_T) k_deep_div_g(const fe *tpolys, const fe *cpolys, int ccols, size_t n,
+__global__ void __launch_bounds__(DIV_T) k_deep_div_g(CoeffSrc TS, const fe *cpolys, int ccols, size_t n,
                                                      const DeepConsts<KX> *D, const typename Chal<KX>::T *pw, size_t H,
                                                      typename Chal<KX>::T *g1, typename Chal<KX>::T *g2, fe *bs,
                                                      size_t kbase, size_t kend) {
@@ -2403,7 +2448,9 @@ __global__ void __launch_bounds__(DIV_T) k_deep_div_g(const fe *tpolys, const fe
     if (k < kend) {
         typename X::Acc aA = X::acc_zero();
 #pragma unroll 4
-        for (int c = 0; c < 28; c++) X::madd(aA, D->alpha_t[c], ld_fe(tpolys + (size_t)c * n + k));
+        for (int c = 0; c < 28; c++)
+            if (TS.mode[c] != CoeffSrc::ZERO) X::madd(aA, D->alpha_t[c], ld_fe(TS.plane[c] + k));
+        if (TS.lagr) X::madd(aA, D->alpha_t[ZK_DEEP_LAGR], ld_fe(TS.lagr + k));
         typename X::Acc aH = X::acc_zero();
         if constexpr (KX == 1) {
             for (int j = 0; j < ccols; j++) X::madd(aH, D->alpha_c[j], ld_fe(cpolys + (size_t)j * n + k));
@@ -2580,13 +2627,15 @@ static void deep_tables(hipStream_t st, size_t n, T z, T zg, fe *scratch) {
     hipLaunchKernelGGL(k_deep_pow_tables<KX>, dim3(cdiv(4 * (2048 + S.H), 256)), dim3(256), 0, st, pb, S.H, (T *)S.pw);
 }
 template <class T>
-static void deep_phase1(hipStream_t st, const fe *tpolys, const fe *cpolys, int ccols, size_t n,
+static void deep_phase1(hipStream_t st, const CoeffSrc &TS, const fe *cpolys, int ccols, size_t n,
                         const void *deep_consts_dev, fe *scratch, size_t k0, size_t kn, fe *total) {
     constexpr int KX = ChalOf<T>::KX;
     const DeepScratch S(scratch, n, KX);
     const size_t nb1 = (kn + DIV_T - 1) / DIV_T;
-    ZK_PROF(st, "deep_combine", (16.0 * (28 + KX * ccols) + 32.0 * KX) * kn,
-            hipLaunchKernelGGL(k_deep_div_g<KX>, dim3((unsigned)nb1), dim3(DIV_T), 0, st, tpolys, cpolys, ccols, n,
+    int tplanes = TS.lagr ? 1 : 0;  // the trace planes read
+    for (int c = 0; c < 28; c++) tplanes += TS.mode[c] != CoeffSrc::ZERO;
+    ZK_PROF(st, "deep_combine", (16.0 * (tplanes + KX * ccols) + 32.0 * KX) * kn,
+            hipLaunchKernelGGL(k_deep_div_g<KX>, dim3((unsigned)nb1), dim3(DIV_T), 0, st, TS, cpolys, ccols, n,
                                (const DeepConsts<KX> *)deep_consts_dev, (const T *)S.pw, S.H, (T *)S.g1, (T *)S.g2, S.bs, k0,
                                k0 + kn));
     hipLaunchKernelGGL(k_deep_div_scan<2 * KX>, dim3(1), dim3(1024), 0, st, S.bs, (int)nb1, total);
@@ -2602,21 +2651,21 @@ static void deep_phase3(hipStream_t st, size_t n, T z, T zg, fe *scratch, size_t
                                ext));
 }
 template <class T>
-const fe *deep_poly(hipStream_t st, const fe *tpolys, const fe *cpolys, int ccols, int log_n,
+const fe *deep_poly(hipStream_t st, const CoeffSrc &TS, const fe *cpolys, int ccols, int log_n,
                     const void *deep_consts_dev, T z, T zg, fe *scratch) {
     const size_t n = (size_t)1 << log_n;
     deep_tables(st, n, z, zg, scratch);
-    deep_phase1<T>(st, tpolys, cpolys, ccols, n, deep_consts_dev, scratch, 0, n, nullptr);
+    deep_phase1<T>(st, TS, cpolys, ccols, n, deep_consts_dev, scratch, 0, n, nullptr);
     deep_phase3(st, n, z, zg, scratch, 0, n, nullptr);
     return DeepScratch(scratch, n, ChalOf<T>::KX).out;
 }
 template <class T>
-const fe *deep_range_begin(hipStream_t st, const fe *tpolys, const fe *cpolys, int ccols, int log_n,
+const fe *deep_range_begin(hipStream_t st, const CoeffSrc &TS, const fe *cpolys, int ccols, int log_n,
                            const void *deep_consts_dev, T z, T zg, fe *scratch, size_t k0, size_t kn) {
     const size_t n = (size_t)1 << log_n;
     deep_tables(st, n, z, zg, scratch);
     fe *total = DeepScratch(scratch, n, ChalOf<T>::KX).total;
-    deep_phase1<T>(st, tpolys, cpolys, ccols, n, deep_consts_dev, scratch, k0, kn, total);
+    deep_phase1<T>(st, TS, cpolys, ccols, n, deep_consts_dev, scratch, k0, kn, total);
     return total;
 }
 template <class T>
@@ -2633,32 +2682,30 @@ const fe *deep_range_end(hipStream_t st, int log_n, T z, T zg, fe *scratch, size
 // composition column 0 after the interpolation.  The evaluator then skips the 22 products per CE row
 // (k_eval_constraints<KE, false>); the composition coefficients are the same field values.  Nonzero
 // remainders (an assertion that fails) set the degree flag.
+// The launch's terms (host-built from the trace columns' CoeffSrc): plane i's weight in f0 (c0: the step 0 assertions,
+// air/src/lib.rs:170-195 order, columns 0, 7, 8, 11, 12..19) and in f1 (c1: the step n-2 assertions, columns 7, 8,
+// 12..19; zero for columns 0 and 11).  A BASE or ZERO column's w_c e_(n-1) rides on one more term, e_(n-1)'s plane with
+// the weights sum_k cb_k w_ck of each group; a ZERO column has no plane of its own.
 struct BndPoly {
-    fe cb[22];  // one coefficient plane (air/src/lib.rs:170-195 order: step 0 cols 0,7,8,11,12..19; step n-2 cols 7,8,12..19)
-    fe bnd1;    // sum_k cb[12+k] v_k
+    static constexpr int MAXT = 13;
+    int nt;
+    fe bnd1;  // sum_k cb[12+k] v_k
+    const fe *plane[MAXT];
+    fe c0[MAXT], c1[MAXT];
 };
-// [kbase, kend): the coefficient range of this launch (a sharded rank's share; 0, n otherwise); n is the column stride
-__global__ void __launch_bounds__(DIV_T) k_bnd_div_g(const fe *tpolys, size_t n, BndPoly bp, const fe *pw, size_t H,
-                                                    fe *g1, fe *g2, fe *bs, size_t kbase, size_t kend) {
+// [kbase, kend): the coefficient range of this launch (a sharded rank's share; 0, n otherwise)
+__global__ void __launch_bounds__(DIV_T) k_bnd_div_g(BndPoly bp, const fe *pw, size_t H, fe *g1, fe *g2, fe *bs,
+                                                    size_t kbase, size_t kend) {
     __shared__ fe red[DIV_T / 64];
     const size_t per = 2048 + H;
     const size_t k = kbase + blockIdx.x * (size_t)DIV_T + threadIdx.x;
     fe v1 = fe_zero(), v2 = fe_zero();
     if (k < kend) {
-        auto T = [&](int c) { return ld_fe(tpolys + (size_t)c * n + k); };
         acc288 a0 = acc288_zero(), a1 = acc288_zero();
-        acc288_madd(a0, bp.cb[0], T(0));
-        acc288_madd(a0, bp.cb[3], T(11));
-        const fe t7 = T(7), t8 = T(8);
-        acc288_madd(a0, bp.cb[1], t7);
-        acc288_madd(a0, bp.cb[2], t8);
-        acc288_madd(a1, bp.cb[12], t7);
-        acc288_madd(a1, bp.cb[13], t8);
-#pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const fe c = T(12 + j);
-            acc288_madd(a0, bp.cb[4 + j], c);
-            acc288_madd(a1, bp.cb[14 + j], c);
+        for (int i = 0; i < bp.nt; i++) {
+            const fe t = ld_fe(bp.plane[i] + k);
+            acc288_madd(a0, bp.c0[i], t);
+            acc288_madd(a1, bp.c1[i], t);
         }
         v1 = acc288_reduce(a0);
         fe f1 = acc288_reduce(a1);
@@ -2675,8 +2722,8 @@ __global__ void __launch_bounds__(DIV_T) k_bnd_div_g(const fe *tpolys, size_t n,
     }
 }
 
-static void bnd_tables_phase1(hipStream_t st, const fe *tpolys, size_t n, const AirConsts &K, fe c, fe *scratch,
-                              size_t k0, size_t kn, fe *total) {
+static void bnd_tables_phase1(hipStream_t st, const CoeffSrc &TS, const fe *w, size_t n, const AirConsts &K, fe c,
+                              fe *scratch, size_t k0, size_t kn, fe *total) {
     const DeepScratch S(scratch, n, 1);
     const size_t nb1 = (kn + DIV_T - 1) / DIV_T;
     DeepPowBases<1> pb;
@@ -2685,12 +2732,30 @@ static void bnd_tables_phase1(hipStream_t st, const fe *tpolys, size_t n, const 
     pb.b[2] = fe_one();
     pb.b[3] = fe_inv(c);
     hipLaunchKernelGGL(k_deep_pow_tables<1>, dim3(cdiv(4 * (2048 + S.H), 256)), dim3(256), 0, st, pb, S.H, S.pw);
-    BndPoly bp;
-    memcpy(bp.cb, K.coeff_b, sizeof bp.cb);
+    BndPoly bp{};
     bp.bnd1 = K.bnd1;
-    ZK_PROF(st, "boundary_poly", (16.0 * 12 + 32.0) * kn,
-            hipLaunchKernelGGL(k_bnd_div_g, dim3((unsigned)nb1), dim3(DIV_T), 0, st, tpolys, n, bp, S.pw, S.H, S.g1, S.g2,
-                               S.bs, k0, k0 + kn));
+    // the assertions' columns: coefficient i < 12 asserts column col0[i] at step 0; 12 + j asserts col1[j] at step n-2
+    static const int col0[12] = {0, 7, 8, 11, 12, 13, 14, 15, 16, 17, 18, 19};
+    fe le0 = fe_zero(), le1 = fe_zero();
+    for (int i = 0; i < 12; i++) {
+        const int cc = col0[i];
+        const fe b0 = K.coeff_b[i], b1 = i == 0 || i == 3 ? fe_zero() : K.coeff_b[i < 3 ? 11 + i : 10 + i];
+        if (TS.mode[cc] != CoeffSrc::ZERO) {
+            bp.plane[bp.nt] = TS.plane[cc], bp.c0[bp.nt] = b0, bp.c1[bp.nt] = b1;
+            bp.nt++;
+        }
+        if (TS.lagr && TS.derived(cc)) {
+            le0 = fe_add(le0, fe_mul(b0, w[cc]));
+            le1 = fe_add(le1, fe_mul(b1, w[cc]));
+        }
+    }
+    if (TS.lagr) {
+        bp.plane[bp.nt] = TS.lagr, bp.c0[bp.nt] = le0, bp.c1[bp.nt] = le1;
+        bp.nt++;
+    }
+    ZK_PROF(st, "boundary_poly", (16.0 * bp.nt + 32.0) * kn,
+            hipLaunchKernelGGL(k_bnd_div_g, dim3((unsigned)nb1), dim3(DIV_T), 0, st, bp, S.pw, S.H, S.g1, S.g2, S.bs, k0,
+                               k0 + kn));
     hipLaunchKernelGGL(k_deep_div_scan<2>, dim3(1), dim3(1024), 0, st, S.bs, (int)nb1, total);
 }
 static void bnd_phase3(hipStream_t st, size_t n, fe c, fe *scratch, size_t k0, size_t kn, const fe *ext, fe *col0,
@@ -2702,20 +2767,20 @@ static void bnd_phase3(hipStream_t st, size_t n, fe c, fe *scratch, size_t k0, s
                                k0 + kn, fe_one(), c, S.pw, S.H, col0, 0, flag, k0, ext));
 }
 
-void boundary_poly_add(hipStream_t st, const fe *tpolys, int log_n, const AirConsts &K, fe c, fe *scratch, fe *col0,
-                       unsigned *flag) {
+void boundary_poly_add(hipStream_t st, const CoeffSrc &TS, const fe *w, int log_n, const AirConsts &K, fe c, fe *scratch,
+                       fe *col0, unsigned *flag) {
     const size_t n = (size_t)1 << log_n;
-    bnd_tables_phase1(st, tpolys, n, K, c, scratch, 0, n, nullptr);
+    bnd_tables_phase1(st, TS, w, n, K, c, scratch, 0, n, nullptr);
     bnd_phase3(st, n, c, scratch, 0, n, nullptr, col0, flag);
 }
 
 // The same over a sharded rank's coefficient range [k0, k0 + kn): begin returns the range's two sums (device); the
 // ranks exchange them and end gets ext = the sums of the later ranks' ranges.  col0 is indexed by global k.
-const fe *boundary_range_begin(hipStream_t st, const fe *tpolys, int log_n, const AirConsts &K, fe c, fe *scratch,
-                               size_t k0, size_t kn) {
+const fe *boundary_range_begin(hipStream_t st, const CoeffSrc &TS, const fe *w, int log_n, const AirConsts &K, fe c,
+                               fe *scratch, size_t k0, size_t kn) {
     const size_t n = (size_t)1 << log_n;
     fe *total = DeepScratch(scratch, n, 1).total;
-    bnd_tables_phase1(st, tpolys, n, K, c, scratch, k0, kn, total);
+    bnd_tables_phase1(st, TS, w, n, K, c, scratch, k0, kn, total);
     return total;
 }
 void boundary_range_end(hipStream_t st, int log_n, fe c, fe *scratch, size_t k0, size_t kn, const fe *ext, fe *col0,
@@ -2724,12 +2789,12 @@ void boundary_range_end(hipStream_t st, int log_n, fe c, fe *scratch, size_t k0,
 }
 
 template <class T>
-void deep_coeff_launch(hipStream_t st, const NttTables &Tn, const fe *tpolys, const fe *cpolys, int ccols, int log_n,
+void deep_coeff_launch(hipStream_t st, const NttTables &Tn, const CoeffSrc &TS, const fe *cpolys, int ccols, int log_n,
                        int log_b, const void *deep_consts_dev, T z, T zg, const CosetTables &CT, fe *scratch,
                        fe *ulde, fe *ntt_tmp, fe *out) {
     constexpr int KX = ChalOf<T>::KX;
     const size_t n = (size_t)1 << log_n, B = (size_t)1 << log_b, N = n << log_b;
-    const fe *Dk = deep_poly(st, tpolys, cpolys, ccols, log_n, deep_consts_dev, z, zg, scratch);
+    const fe *Dk = deep_poly(st, TS, cpolys, ccols, log_n, deep_consts_dev, z, zg, scratch);
     for (int plane = 0; plane < KX; plane++) lde_cosets(st, Tn, CT, Dk + plane * n, n, 0, 1, (int)B, ulde + plane * N, ntt_tmp);
     if (!out) return;  // FRI layer 0 is read coset-major from ulde
     unsigned pb2 = cdiv(N, 256);
@@ -2739,11 +2804,11 @@ void deep_coeff_launch(hipStream_t st, const NttTables &Tn, const fe *tpolys, co
                 hipLaunchKernelGGL(k_coset_to_natural, dim3(pb2), dim3(256), 0, st, ulde + plane * N, log_n, log_b, out + plane * N));
 }
 #define ZK_DEEP_INSTANCES(T)                                                                                           \
-    template const fe *deep_poly<T>(hipStream_t, const fe *, const fe *, int, int, const void *, T, T, fe *);          \
-    template const fe *deep_range_begin<T>(hipStream_t, const fe *, const fe *, int, int, const void *, T, T, fe *,    \
-                                           size_t, size_t);                                                            \
+    template const fe *deep_poly<T>(hipStream_t, const CoeffSrc &, const fe *, int, int, const void *, T, T, fe *);    \
+    template const fe *deep_range_begin<T>(hipStream_t, const CoeffSrc &, const fe *, int, int, const void *, T, T,    \
+                                           fe *, size_t, size_t);                                                      \
     template const fe *deep_range_end<T>(hipStream_t, int, T, T, fe *, size_t, size_t, const fe *);                    \
-    template void deep_coeff_launch<T>(hipStream_t, const NttTables &, const fe *, const fe *, int, int, int,          \
+    template void deep_coeff_launch<T>(hipStream_t, const NttTables &, const CoeffSrc &, const fe *, int, int, int,    \
                                        const void *, T, T, const CosetTables &, fe *, fe *, fe *, fe *);
 ZK_DEEP_INSTANCES(fe)
 ZK_DEEP_INSTANCES(fe2)

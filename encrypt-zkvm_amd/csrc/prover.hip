@@ -593,6 +593,12 @@ int zk_prover_upload_fixed(zk_prover *p, uint32_t *fixed_cols) {
     return ZK_OK;
 }
 
+int zk_prover_coeff_sources(zk_prover *p, uint32_t *cols) {
+    if (!p || !cols) ZK_FAIL(ZK_ERR_INVALID_ARG, "null argument");
+    *cols = p->tc.coeff_src;
+    return ZK_OK;
+}
+
 int zk_prover_exchange_stats_ex(zk_prover *p, const char **names, float *ms, float *exposed_ms, double *bytes,
                                 int *calls, int cap, int *count) {
     if (!p) ZK_FAIL(ZK_ERR_INVALID_ARG, "null prover");
@@ -1214,8 +1220,10 @@ int zk::ensure_ext(zk_prover *p) {
 // nce = 7 (C <= 7): only CE cosets 0..6 were evaluated; the cross-coset step derives coset 7 from the degree
 // bound (CrossMap::derive7).  Same polynomial for a trace that satisfies the AIR; for one that does not, the
 // out-of-domain identity check (check_ood_identity) reports it instead of the top-block flag.
+// TS, w (with bnd): where the boundary quotient reads the trace coefficients (CoeffSrc and its scalars; null: p->polys).
 static int composition_stage(zk_prover *p, Plan *pl, int KX, int C, fe *comp, fe *ctmp, fe *clde, uint8_t root[32],
-                             const AirConsts *bnd = nullptr, int nce = 8) {
+                             const AirConsts *bnd = nullptr, int nce = 8, const CoeffSrc *TS = nullptr,
+                             const fe *w = nullptr) {
     const size_t n = (size_t)1 << pl->log_n, CE = 8 * n;
     const int CK = C * KX;
     if (nce != 8 && (nce != 7 || C > 7)) ZK_FAIL(ZK_ERR_INVALID_ARG, "composition: unsupported CE coset count");
@@ -1238,10 +1246,12 @@ static int composition_stage(zk_prover *p, Plan *pl, int KX, int C, fe *comp, fe
         comp_cross_mapped(p->st, m, pl->Tce, pl->inv3, h_inv(fe_make(CE)), h_inv(w8), h_inv(h_pow(fe_make(3), n)), C,
                           p->cpolys + (size_t)j * n, p->flag);
     }
-    if (bnd)
+    if (bnd) {
+        const CoeffSrc plain = coeff_plain(p->polys, n);
         for (int j = 0; j < KX; j++)
-            boundary_poly_add(p->st, p->polys, pl->log_n, bnd[j], bnd[0].g_last2, p->dscratch, p->cpolys + (size_t)j * n,
-                              p->flag);
+            boundary_poly_add(p->st, TS ? *TS : plain, w, pl->log_n, bnd[j], bnd[0].g_last2, p->dscratch,
+                              p->cpolys + (size_t)j * n, p->flag);
+    }
     return lde_commit(p, pl, p->cpolys, CK, clde, p->cleaves, p->cnodes, root);
 }
 
@@ -1372,18 +1382,22 @@ static int ood_deep_stage(zk_prover *p, Plan *pl, Coin &coin, zk_record &R, Host
     const int log_n = pl->log_n;
     const typename X::T z = X::make(coin.draw_ext(KX)), zg = X::mulb(z, h_root_of_unity(log_n));
     fe_to_bytes(X::comp(z, 0), R.z);
-    ood_eval(p->st, p->polys, W, p->cpolys, C * KX, log_n, z, zg, b.ood_tab, b.partials, p->ood);
+    // the trace coefficients where this proof's commitment left them (p->csrc: p->polys, or the derived columns' sources)
+    const CoeffSrc &TS = p->csrc;
+    ood_eval(p->st, TS, W, p->cpolys, C * KX, log_n, z, zg, b.ood_tab, b.partials, p->ood);
     HT.stop("z");
-    std::vector<fe> hv((size_t)KX * (2 * W + C * KX));
-    ZK_TRY(d2h_small(p, hv.data(), p->ood, hv.size() * sizeof(fe)));
+    std::vector<fe> raw((size_t)KX * ood_out_values(TS, W, C * KX)), hv((size_t)KX * (2 * W + C * KX));
+    ZK_TRY(d2h_small(p, raw.data(), p->ood, raw.size() * sizeof(fe)));
     ZK_TRY(d2h_flush(p));
     HT.start();
+    ood_fold_sources(KX, W, C * KX, TS, p->csrc_w, raw.data(), hv.data());
     std::vector<fe2> e;
     ood_reseed(coin, KX, hv, C, R, e, h);
     stage_mark(p, "ood");
-    const DeepConsts<KX> D = draw_deep_consts<KX>(coin, e, C, z, zg, R);
+    DeepConsts<KX> D = draw_deep_consts<KX>(coin, e, C, z, zg, R);
+    deep_source_weight(D, TS, p->csrc_w);
     ZK_TRY(h2d_small(p, b.deep_consts, &D, sizeof D));
-    deep_coeff_launch(p->st, pl->Tn, p->polys, p->cpolys, C, log_n, pl->log_b, b.deep_consts, z, zg, pl->ct, b.dscratch,
+    deep_coeff_launch(p->st, pl->Tn, TS, p->cpolys, C, log_n, pl->log_b, b.deep_consts, z, zg, pl->ct, b.dscratch,
                       b.ulde, p->tmp, deep_out);
     HT.stop("deep_consts");
     // while the GPU runs DEEP: the verifier's out-of-domain identity on the frame just read
@@ -1460,7 +1474,8 @@ static int prove_once(zk_prover *p, const TraceSrc &src, size_t n, const zk_opti
     stage_mark(p, "constraints");
 
     // S4: composition polynomial (interpolate over the CE coset, segment into C columns) + commit.
-    ZK_TRY(composition_stage(p, pl, KX, C, comp, ctmp, clde, R.constraint_root, bnd_rows ? nullptr : Kp, nce));
+    ZK_TRY(composition_stage(p, pl, KX, C, comp, ctmp, clde, R.constraint_root, bnd_rows ? nullptr : Kp, nce, &p->csrc,
+                             p->csrc_w));
     unsigned degree_flag = 0;
     ZK_TRY(d2h_small(p, &degree_flag, p->flag, 4));
     ZK_TRY(d2h_flush(p));
@@ -1775,7 +1790,7 @@ int zk::fixed_prefix(zk_prover *p, size_t n, uint32_t B, const FixedCols &fx) {
     const size_t Bn = n << pl->log_b;
     if (fixed_fuse_on()) {
         // their LDE inside the row hash of their blocks; the streaming pass extends the zero registers only
-        fixed_axpy(p->st, fx, p->fix_ws, n, (size_t)1 << pl->log_b, p->polys, p->lde, 4 * nb);
+        fixed_axpy(p->st, fx, p->fix_ws, n, (size_t)1 << pl->log_b, p->polys, p->lde, 4 * nb, !coeff_src_on());
         FixedHashCols A{};
         for (int c = 0; c < 4 * nb; c++) {
             A.mode[c] = FixedHashCols::FORM;
@@ -1784,7 +1799,7 @@ int zk::fixed_prefix(zk_prover *p, size_t n, uint32_t B, const FixedCols &fx) {
         }
         fixed_hash(p->st, A, fx.lagr_lde, p->fix_ws, p->lde, W, pl->log_n, pl->log_b, nb, p->leaves);
     } else {
-        fixed_axpy(p->st, fx, p->fix_ws, n, (size_t)1 << pl->log_b, p->polys, p->lde);
+        fixed_axpy(p->st, fx, p->fix_ws, n, (size_t)1 << pl->log_b, p->polys, p->lde, 0, !coeff_src_on());
         hash_rows_blocks(p->st, p->lde, W, pl->log_n, pl->log_b, 0, nb, p->leaves);
     }
     p->fix_prefix_blocks = nb;
@@ -2047,18 +2062,26 @@ extern "C" void zk_diag_blake3_host(const uint8_t *in, size_t len, uint8_t out[3
 
 // Host: the upload plan of a host-trace commitment (upload_plan.hpp).  in[13] = have, sparse, nw8, nw32, clk_off,
 // fixed_off, snap, snap_mask, hint_ok, no_virtual, lat_sched, detect, switches (bit 0 ZK_SPARSE, 1 ZK_NARROW, 2 ZK_CLOCK,
-// 3 ZK_FIXED, 4 ZK_FIXED_FUSE, 5 ZK_VIRTUAL); n the trace length.  masks[8] = hint, nw8, nw32, clk, fixm, virt, snap_now,
-// lat; counts[7] = nd, nh, nhv, nn, np, ngroups, fuse_nb; cols[4 W] = dense, hin, hnv, nar (W each); width[W];
-// off[W + 1] (off[W] = pack_bytes); pb[W + 1]; gsz[W].  Returns the plan's status.
-extern "C" int zk_diag_upload_plan(const uint32_t *in, size_t n, uint32_t *masks, int32_t *counts, int32_t *cols,
-                                   int32_t *width, uint64_t *off, int32_t *pb, int32_t *gsz) {
+// 3 ZK_FIXED, 4 ZK_FIXED_FUSE, 5 ZK_VIRTUAL, 6 ZK_COEFF_SRC); n the trace length.
+static UploadPlanIn diag_upload_plan_in(const uint32_t *in, size_t n) {
     UploadPlanIn q;
     q.have = in[0], q.sparse = in[1], q.nw8 = in[2], q.nw32 = in[3], q.clk_off = in[4], q.fixed_off = in[5];
     q.snap = in[6], q.snap_mask = in[7], q.hint_ok = in[8], q.no_virtual = in[9], q.lat_sched = in[10], q.detect = in[11];
     q.sparse_on = in[12] & 1u, q.narrow_on = in[12] & 2u, q.clock_on = in[12] & 4u, q.fixed_on = in[12] & 8u;
-    q.fixed_fuse_on = in[12] & 16u, q.virtual_on = in[12] & 32u;
+    q.fixed_fuse_on = in[12] & 16u, q.virtual_on = in[12] & 32u, q.coeff_src_on = in[12] & 64u;
     q.n = n;
-    const UploadPlan u = upload_plan(q);
+    return q;
+}
+// the plan's coeff_src (the derived columns' coefficients read at their source, not written): 1 or 0
+extern "C" int zk_diag_upload_plan_coeff_src(const uint32_t *in, size_t n) {
+    return upload_plan(diag_upload_plan_in(in, n)).coeff_src ? 1 : 0;
+}
+// masks[8] = hint, nw8, nw32, clk, fixm, virt, snap_now, lat; counts[7] = nd, nh, nhv, nn, np, ngroups, fuse_nb;
+// cols[4 W] = dense, hin, hnv, nar (W each); width[W]; off[W + 1] (off[W] = pack_bytes); pb[W + 1]; gsz[W].  Returns the
+// plan's status.
+extern "C" int zk_diag_upload_plan(const uint32_t *in, size_t n, uint32_t *masks, int32_t *counts, int32_t *cols,
+                                   int32_t *width, uint64_t *off, int32_t *pb, int32_t *gsz) {
+    const UploadPlan u = upload_plan(diag_upload_plan_in(in, n));
     const uint32_t m[8] = {u.hint, u.nw8, u.nw32, u.clk, u.fixm, u.virt, u.snap_now, u.lat};
     const int32_t k[7] = {u.nd, u.nh, u.nhv, u.nn, u.np, u.ngroups, u.fuse_nb};
     memcpy(masks, m, sizeof m);
@@ -2282,7 +2305,8 @@ extern "C" int zk_diag_ood(int device, const uint8_t *tpolys, const uint8_t *cpo
     const Planes b = planes(p, ext);
     with_kx(ext, [&](auto kx) {
         typedef Chal<decltype(kx)::value> X;
-        ood_eval(p->st, p->polys, W, p->cpolys, ccols, ilog2(n), X::make(zv), X::make(zgv), b.ood_tab, b.partials, p->ood, rank, G);
+        ood_eval(p->st, coeff_plain(p->polys, n), W, p->cpolys, ccols, ilog2(n), X::make(zv), X::make(zgv), b.ood_tab,
+                 b.partials, p->ood, rank, G);
         return 0;
     });
     ZK_CHECK_HIP(hipStreamSynchronize(p->st));
@@ -2323,8 +2347,9 @@ static int diag_deep(int device, const uint8_t *tpolys, const uint8_t *cpolys, i
         D.z = z, D.zg = zg;
         ZK_CHECK_HIP(hipMemcpy(b.deep_consts, &D, sizeof D, hipMemcpyHostToDevice));
         const fe *Dk = nullptr;
+        const CoeffSrc TS = coeff_plain(p->polys, n);
         if (parts == 1) {
-            Dk = deep_poly(p->st, p->polys, p->cpolys, C, log_n, b.deep_consts, z, zg, b.dscratch);
+            Dk = deep_poly(p->st, TS, p->cpolys, C, log_n, b.deep_consts, z, zg, b.dscratch);
         } else {
             // The ranks of a sharded proof on one device, in rank order: every range's begin, the later ranges' totals
             // summed here as the all-gather and k_sh_suffix_carry do, every range's end.  Each rank has a scratch of
@@ -2334,7 +2359,7 @@ static int diag_deep(int device, const uint8_t *tpolys, const uint8_t *cpolys, i
             const size_t kn = n / parts, nc = 2 * KX, ncarry = nc * (kn / ZK_DEEP_BLOCK);
             std::vector<fe> tot((size_t)parts * nc);
             for (int g = 0; g < parts; g++) {
-                const fe *t = deep_range_begin(p->st, p->polys, p->cpolys, C, log_n, b.deep_consts, z, zg, b.dscratch, g * kn, kn);
+                const fe *t = deep_range_begin(p->st, TS, p->cpolys, C, log_n, b.deep_consts, z, zg, b.dscratch, g * kn, kn);
                 ZK_CHECK_HIP(hipMemcpyAsync(p->comp + g * ncarry, S.bs, ncarry * sizeof(fe), hipMemcpyDeviceToDevice, p->st));
                 ZK_CHECK_HIP(hipMemcpyAsync(&tot[g * nc], t, nc * sizeof(fe), hipMemcpyDeviceToHost, p->st));
             }
@@ -2367,6 +2392,91 @@ extern "C" int zk_diag_deep_parts(int device, const uint8_t *tpolys, const uint8
     if (parts < 2 || parts > 8 || (parts & (parts - 1)) || n < (size_t)parts * ZK_DEEP_RANGE_QUANTUM)
         ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_deep_parts: 2, 4 or 8 ranges of at least 2048 coefficients");
     return diag_deep(device, tpolys, cpolys, ccols, n, ext, z, zg, alpha_t, alpha_c, parts, out);
+}
+
+// The three consumers of the trace coefficients through a CoeffSrc (tests/test_coeff_sources.py): tplanes = 29 planes of
+// n coefficients, plane c < 28 column c's (mode PLAIN: the column; BASE: its base; ZERO: not read) and plane 28 standing
+// for e_(n-1) (any polynomial: the consumers are linear in it); modes[28]; w[28] the columns' scalars (canonical).
+// ood_eval + ood_fold_sources -> ood_out as zk_diag_ood's; deep_poly (with deep_source_weight) -> deep_out as
+// zk_diag_deep's; boundary_poly_add per coefficient plane (coeff_b: ext x 22, bnd1: ext values, c = the second divisor
+// point, non-zero) into zeroed columns -> col0_out (ext planes of n) and the degree flag -> *flag_out.  With every mode
+// PLAIN this is the table coeff_plain gives, so a caller compares sources against the materialised base + w e planes.
+extern "C" int zk_diag_coeff_sources(int device, const uint8_t *tplanes, const uint8_t *modes, const uint8_t *w,
+                                     const uint8_t *cpolys, int ccols, size_t n, int ext, const uint8_t *z,
+                                     const uint8_t *zg, const uint8_t *alpha_t, const uint8_t *alpha_c,
+                                     const uint8_t *coeff_b, const uint8_t *bnd1, const uint8_t *c, uint8_t *ood_out,
+                                     uint8_t *deep_out, uint8_t *col0_out, uint32_t *flag_out) {
+    fe2 zv, zgv;
+    ZK_TRY(diag_back_half_args("zk_diag_coeff_sources", tplanes, cpolys, ccols, n, ext, z, zg, ood_out, &zv, &zgv));
+    if (!modes || !w || !alpha_t || !alpha_c || !coeff_b || !bnd1 || !c || !deep_out || !col0_out || !flag_out)
+        ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_coeff_sources: null argument");
+    if ((fe_is_zero(zv.a) && fe_is_zero(zv.b)) || (fe_is_zero(zgv.a) && fe_is_zero(zgv.b)))
+        ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_coeff_sources: z and zg must be non-zero (their inverses are taken)");
+    const int C = ccols / ext, log_n = ilog2(n);
+    fe2 at[W], ac[8];
+    for (int k = 0; k < W + C; k++)
+        if (!diag_read_fe((k < W ? alpha_t + 16 * ext * k : alpha_c + 16 * ext * (k - W)), ext, k < W ? &at[k] : &ac[k - W]))
+            ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_coeff_sources: non-canonical coefficient");
+    fe wv[W];
+    AirConsts K[2];
+    memset(K, 0, sizeof K);
+    const fe cv = fe_from_bytes(c);
+    bool ok = fe_canonical(cv) && !fe_is_zero(cv);
+    for (int k = 0; k < W; k++) {
+        wv[k] = fe_from_bytes(w + 16 * k);
+        ok = ok && fe_canonical(wv[k]) && modes[k] <= CoeffSrc::ZERO;
+    }
+    for (int j = 0; j < ext; j++) {
+        for (int k = 0; k < NUM_ASSERTS; k++) {
+            K[j].coeff_b[k] = fe_from_bytes(coeff_b + 16 * (NUM_ASSERTS * j + k));
+            ok = ok && fe_canonical(K[j].coeff_b[k]);
+        }
+        K[j].bnd1 = fe_from_bytes(bnd1 + 16 * j);
+        ok = ok && fe_canonical(K[j].bnd1);
+    }
+    if (!ok) ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_coeff_sources: canonical values, modes 0 .. 2, c non-zero");
+    zk_prover *p = nullptr;
+    ZK_TRY(zk_prover_create(device, n, 8, &p));
+    std::unique_ptr<zk_prover, void (*)(zk_prover *)> guard(p, zk_prover_destroy);
+    if (ext == 2) ZK_TRY(ensure_ext(p));
+    ZK_CHECK_HIP(hipMemcpy(p->polys, tplanes, (size_t)(W + 1) * n * 16, hipMemcpyHostToDevice));  // (polys holds 32 planes)
+    ZK_CHECK_HIP(hipMemcpy(p->cpolys, cpolys, (size_t)ccols * n * 16, hipMemcpyHostToDevice));
+    CoeffSrc TS = coeff_plain(p->polys, n);
+    for (int k = 0; k < W; k++) {
+        TS.mode[k] = modes[k];
+        if (modes[k] == CoeffSrc::ZERO) TS.plane[k] = nullptr;
+        if (modes[k] != CoeffSrc::PLAIN) TS.lagr = p->polys + (size_t)W * n;
+    }
+    const Planes b = planes(p, ext);
+    return with_kx(ext, [&](auto kx) -> int {
+        constexpr int KX = decltype(kx)::value;
+        typedef Chal<KX> X;
+        const typename X::T zz = X::make(zv), zzg = X::make(zgv);
+        ood_eval(p->st, TS, W, p->cpolys, ccols, log_n, zz, zzg, b.ood_tab, b.partials, p->ood);
+        std::vector<fe> raw((size_t)KX * ood_out_values(TS, W, ccols)), hv((size_t)KX * (2 * W + ccols));
+        ZK_CHECK_HIP(hipStreamSynchronize(p->st));
+        ZK_CHECK_HIP(hipMemcpy(raw.data(), p->ood, raw.size() * sizeof(fe), hipMemcpyDeviceToHost));
+        ood_fold_sources(KX, W, ccols, TS, wv, raw.data(), hv.data());
+        memcpy(ood_out, hv.data(), hv.size() * sizeof(fe));
+        DeepConsts<KX> D;
+        memset(&D, 0, sizeof D);
+        for (int k = 0; k < W; k++) D.alpha_t[k] = X::make(at[k]);
+        for (int k = 0; k < C; k++) D.alpha_c[k] = X::make(ac[k]);
+        D.z = zz, D.zg = zzg;
+        deep_source_weight(D, TS, wv);
+        ZK_CHECK_HIP(hipMemcpy(b.deep_consts, &D, sizeof D, hipMemcpyHostToDevice));
+        const fe *Dk = deep_poly(p->st, TS, p->cpolys, C, log_n, b.deep_consts, zz, zzg, b.dscratch);
+        ZK_CHECK_HIP(hipStreamSynchronize(p->st));
+        ZK_CHECK_HIP(hipMemcpy(deep_out, Dk, (size_t)KX * n * 16, hipMemcpyDeviceToHost));
+        ZK_CHECK_HIP(hipMemsetAsync(p->flag, 0, 4, p->st));
+        ZK_CHECK_HIP(hipMemsetAsync(p->ctmp, 0, (size_t)KX * n * 16, p->st));
+        for (int j = 0; j < KX; j++)
+            boundary_poly_add(p->st, TS, wv, log_n, K[j], cv, p->dscratch, p->ctmp + (size_t)j * n, p->flag);
+        ZK_CHECK_HIP(hipStreamSynchronize(p->st));
+        ZK_CHECK_HIP(hipMemcpy(col0_out, p->ctmp, (size_t)KX * n * 16, hipMemcpyDeviceToHost));
+        ZK_CHECK_HIP(hipMemcpy(flag_out, p->flag, 4, hipMemcpyDeviceToHost));
+        return ZK_OK;
+    });
 }
 
 // One FRI layer through commit_fri_layer and fri_fold_launch: `layer` holds L values as the

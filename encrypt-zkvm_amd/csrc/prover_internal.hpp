@@ -279,7 +279,13 @@ struct zk_prover {
         uint32_t virt = 0;
         fe virt_last[28] = {};
         const fe *virt_lagr = nullptr;
+        uint32_t coeff_src = 0;  // the columns whose coefficients were read at their source (csrc), never written
     } tc;
+    // Where stages S3 .. S5 of the current proof read the trace coefficients (zk_internal.hpp CoeffSrc) and the scalars
+    // w_c of its BASE and ZERO columns: set by every trace commitment (trace_lde_commit), every column PLAIN over polys
+    // unless a host-trace proof took its clock, fixed and hinted sparse columns at their source (UploadPlan::coeff_src)
+    zk::CoeffSrc csrc = {};
+    fe csrc_w[zk::W] = {};
     // Sharded host-trace hints (shard.hip S2): the sparse columns and the clock a previous sharded proof of this length
     // and world found (from all-gathered flags, so every rank holds the same), checked by the ranks' host threads
     uint32_t sh_sparse = 0, sh_nw8 = 0, sh_nw32 = 0;  // (and the narrow ones: the owner rank uploads them packed)
@@ -439,20 +445,27 @@ int prove_fixed(zk_prover *p, size_t n, const zk_options *opt, const zk_pub_inpu
                 uint8_t *proof_out, size_t *proof_len);
 // polys / lde of the preprocessed columns (all but 12 .. 12 + md - 1): f_c + last[c] e_(n-1) (vm_gpu.hip); B: the LDE
 // cosets held (fx's flde / lagr_lde and lde alike).  lde_c0: the LDE launch forms the columns from lde_c0 on only (the
-// ones below it are formed by fixed_hash, inside their rows' hashing); the coefficients are always all of them
+// ones below it are formed by fixed_hash, inside their rows' hashing); the coefficients are all of them, or with
+// coeffs = false none (read at their source: fixed_coeff_src)
 void fixed_axpy(hipStream_t st, const FixedCols &fx, const fe_ws *ws_dev, size_t n, size_t B, fe *polys, fe *lde,
-                int lde_c0 = 0);
+                int lde_c0 = 0, bool coeffs = true);
+// ZK_COEFF_SRC=0: the derived columns' coefficients are written into polys, not read at their source (CoeffSrc)
+bool coeff_src_on();
+// the table of zk_vm_prove's preprocessed columns into p->csrc / p->csrc_w: column c < 12 is fx.fpolys' plane c plus
+// last[c] e_(n-1), a register past the program's depth last[c] e_(n-1) alone, the dynamic ones p->polys'
+void fixed_coeff_src(zk_prover *p, const FixedCols &fx, size_t n);
 // The same pass for the host-trace fixed class (zk_prover::FixedSnap): `count` trace columns col[k], each with a compact
 // plane slot[k] of the snapshot.  Use: polys / lde column col[k] = snapshot plane slot[k] + ws_dev[col[k]] e_(n-1)'s.
 // snapshot: the other way, plane slot[k] of polys / lde (the snapshot's buffers) = column col[k] of src_polys / src_lde
 // + ws_dev[col[k]] e_(n-1)'s, ws_dev holding the NEGATED last row (exact: f_c = column - last[c] e_(n-1)).
+// coeffs = false: the LDE launch alone (the coefficients are read at their source: CoeffSrc)
 struct FixedColList {
     int count = 0;
     uint8_t col[W], slot[W];
 };
 void fixed_cols_axpy(hipStream_t st, const FixedColList &L, bool snapshot, const fe *src_polys, const fe *src_lde,
                      const fe *lagr, const fe *lagr_lde, const fe_ws *ws_dev, size_t n, size_t B, fe *polys, fe *lde,
-                     int lde_c0 = 0);
+                     int lde_c0 = 0, bool coeffs = true);
 bool fixed_on();
 // ZK_FIXED_FUSE=0: the fixed / preprocessed columns' LDE by its own streaming pass and hash_rows_blocks, not fixed_hash
 bool fixed_fuse_on();

@@ -1047,8 +1047,9 @@ struct ShardedProof {
     // this rank's range sums of plane pln's assertion quotient (they read only the trace coefficients), into xb
     int boundary_begin(int pln) {
         return each_rank(X, [this, pln](int l, zk_prover *p, Plan *) -> int {
-            const void *sums = boundary_range_begin(p->st, p->polys, log_n, Kp[pln], K.g_last2, p->dscratch,
-                                                    (size_t)X.rank[l] * kg, kg);
+            // (a sharded rank writes every column's coefficients: the all-PLAIN table)
+            const void *sums = boundary_range_begin(p->st, coeff_plain(p->polys, n), nullptr, log_n, Kp[pln], K.g_last2,
+                                                    p->dscratch, (size_t)X.rank[l] * kg, kg);
             xb.set(l, sums, p->sh_buf);
             return ZK_OK;
         });
@@ -1216,7 +1217,8 @@ struct ShardedProof {
         fe_to_bytes(XF::comp(z, 0), R.z);
         std::vector<fe> hv;
         ZK_TRY(ood_parts(KX_ * (2 * W + CK), [this, z, zg](zk_prover *p, int rank) {
-            ood_eval(p->st, p->polys, W, p->cpolys, CK, log_n, z, zg, pb(p).ood_tab, pb(p).partials, p->ood, rank, G);
+            ood_eval(p->st, coeff_plain(p->polys, n), W, p->cpolys, CK, log_n, z, zg, pb(p).ood_tab, pb(p).partials, p->ood,
+                     rank, G);
         }, hv));
         std::vector<fe2> e;
         ood_reseed(coin, KX_, hv, C, R, e, h);
@@ -1225,14 +1227,16 @@ struct ShardedProof {
         auto upload = [this, D](zk_prover *p) { return h2d_small(p, pb(p).deep_consts, &D, sizeof D); };
         if (range_split) {
             ZK_TRY(deep_split_ranges(KX_, [this, z, zg](zk_prover *p, size_t k0) {
-                return deep_range_begin(p->st, p->polys, p->cpolys, C, log_n, pb(p).deep_consts, z, zg, pb(p).dscratch, k0, kg);
+                return deep_range_begin(p->st, coeff_plain(p->polys, n), p->cpolys, C, log_n, pb(p).deep_consts, z, zg,
+                                        pb(p).dscratch, k0, kg);
             }, [this, z, zg](zk_prover *p, size_t k0, const fe *ext) {
                 return deep_range_end(p->st, log_n, z, zg, pb(p).dscratch, k0, kg, ext);
             }, upload));
         } else {
             ZK_TRY(each_rank(X, [this, z, zg, upload](int l, zk_prover *p, Plan *) -> int {
                 ZK_TRY(upload(p));
-                Dk[l] = deep_poly(p->st, p->polys, p->cpolys, C, log_n, pb(p).deep_consts, z, zg, pb(p).dscratch);
+                Dk[l] = deep_poly(p->st, coeff_plain(p->polys, n), p->cpolys, C, log_n, pb(p).deep_consts, z, zg,
+                                  pb(p).dscratch);
                 return ZK_OK;
             }));
         }

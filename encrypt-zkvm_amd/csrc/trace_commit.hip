@@ -29,6 +29,8 @@ bool zk::fixed_on() { static const bool on = env_switch("ZK_FIXED"); return on; 
 bool zk::fixed_fuse_on() { static const bool on = env_switch("ZK_FIXED_FUSE"); return on; }
 // Virtual columns (upload_plan.hpp ZK_VIRT_MIN_COL): ZK_VIRTUAL=0 writes their LDE
 static bool virtual_on() { static const bool on = env_switch("ZK_VIRTUAL"); return on; }
+// Coefficient sources (UploadPlan::coeff_src): ZK_COEFF_SRC=0 writes the derived columns' coefficients into polys
+bool zk::coeff_src_on() { static const bool on = env_switch("ZK_COEFF_SRC"); return on; }
 
 // ---------------------------------------------------------------- hint sets and snapshots
 // forget snapshot i (its device buffers stay allocated for the next snapshot of that size)
@@ -257,9 +259,22 @@ static int upload_trace_group(zk_prover *p, const TraceSrc &src, size_t n, int c
     return ZK_OK;
 }
 
-// zk_vm_prove: interpolate and extend the dynamic stack columns only; the preprocessed ones by one pass
+void zk::fixed_coeff_src(zk_prover *p, const FixedCols &fx, size_t n) {
+    for (int c = 0; c < W; c++) {
+        if (c >= 12 && c < 12 + fx.md) continue;
+        p->csrc.plane[c] = c < 12 ? fx.fpolys + (size_t)c * n : nullptr;
+        p->csrc.mode[c] = c < 12 ? CoeffSrc::BASE : CoeffSrc::ZERO;
+        p->csrc_w[c] = fx.last[c];
+        p->tc.coeff_src |= 1u << c;
+    }
+    p->csrc.lagr = fx.lagr;
+}
+
+// zk_vm_prove: interpolate and extend the dynamic stack columns only; the preprocessed ones by one pass (their
+// coefficients are read at their source, not written: fixed_coeff_src)
 static int commit_device_fixed(zk_prover *p, Plan *pl, const TraceSrc &src, size_t n, uint8_t root[32]) {
     const FixedCols &fx = *src.fixed;
+    if (coeff_src_on()) fixed_coeff_src(p, fx, n);
     const fe inv_n = h_inv(fe_make(n));
     const size_t B = (size_t)1 << pl->log_b, c0 = 12;
     if (fx.md > 0) {
@@ -275,7 +290,7 @@ static int commit_device_fixed(zk_prover *p, Plan *pl, const TraceSrc &src, size
         fe_ws ws[W];
         for (int c = 0; c < W; c++) ws[c] = make_fe_ws(fx.last[c]);
         ZK_TRY(h2d_small(p, p->fix_ws, ws, sizeof ws));
-        fixed_axpy(p->st, fx, p->fix_ws, n, B, p->polys, p->lde);
+        fixed_axpy(p->st, fx, p->fix_ws, n, B, p->polys, p->lde, 0, !coeff_src_on());
         hash_rows_cosets(p->st, p->lde, W, pl->log_n, pl->log_b, 0, pl->log_b, p->leaves);
     }
     merkle_tree(p->st, p->leaves, n * B, p->nodes);
@@ -359,6 +374,7 @@ struct HostTraceCommit {
         in.hint_ok = src.hint_ok, in.no_virtual = src.no_virtual, in.lat_sched = p->lat_sched, in.detect = sp != nullptr;
         in.sparse_on = sparse_on(), in.narrow_on = narrow_on(), in.clock_on = clock_on();
         in.fixed_on = fixed_on(), in.fixed_fuse_on = fixed_fuse_on(), in.virtual_on = virtual_on(), in.n = n;
+        in.coeff_src_on = coeff_src_on();
         u = upload_plan(in);
         if (!u.fix_ok) FS = nullptr;
         else if (!FS && H->snap >= 0) fixed_drop(p, H->snap);  // snap for another blowup or lwe_size: snap again
@@ -378,6 +394,14 @@ struct HostTraceCommit {
     }
 
     fe last_of(int c) const { return fe_from_bytes(src.cols[c] + (n - 1) * sizeof(fe)); }  // the column's last row
+    // column c's coefficients are plane (or nothing) + w e_(n-1), read there by S3 .. S5 and not written (u.coeff_src)
+    void source(int c, uint8_t mode, const fe *plane, fe w) {
+        p->csrc.plane[c] = plane;
+        p->csrc.mode[c] = mode;
+        p->csrc.lagr = pl->lagr;
+        p->csrc_w[c] = w;
+        p->tc.coeff_src |= 1u << c;
+    }
     // interpolation and / or coset LDE of columns [c0, c0 + nc).  fused: the interpolation's pass 1 writes the columns'
     // flags; all: every column is sparse, the fills alone (SparseCols)
     enum { INTERP = 1, LDE = 2 };
@@ -443,7 +467,10 @@ struct HostTraceCommit {
         fe lastv[W] = {};
         for (int i = 0; i < u.nh; i++) lastv[u.hin[i]] = last_of(u.hin[i]);
         ZK_TRY(h2d_small(p, p->sp_last, lastv, sizeof lastv));
-        ZK_TRY(for_runs(u.hin, u.nh, [this](int c0, int nc) { return transform(c0, nc, false, true, INTERP); }));
+        if (u.coeff_src)
+            for (int i = 0; i < u.nh; i++) source(u.hin[i], CoeffSrc::ZERO, nullptr, lastv[u.hin[i]]);
+        else
+            ZK_TRY(for_runs(u.hin, u.nh, [this](int c0, int nc) { return transform(c0, nc, false, true, INTERP); }));
         ZK_TRY(for_runs(u.hnv, u.nhv, [this](int c0, int nc) { return transform(c0, nc, false, true, LDE); }));
         p->tc.virt = u.virt;
         memcpy(p->tc.virt_last, lastv, sizeof lastv);
@@ -459,8 +486,10 @@ struct HostTraceCommit {
         row_tasks(clocked, 0, 0, n - 1, R, [this](int, size_t r0, size_t r1) {
             if (!clock_rows(src.cols[0], r0, r1)) clock_bad.store(1u);
         });
-        clk_d = make_fe_ws(fe_sub(last_of(0), fe_make(n - 1)));
-        axpy_fill(p->st, pl->id_poly, pl->lagr, clk_d, n, p->polys);
+        const fe d = fe_sub(last_of(0), fe_make(n - 1));
+        clk_d = make_fe_ws(d);
+        if (u.coeff_src) source(0, CoeffSrc::BASE, pl->id_poly, d);
+        else axpy_fill(p->st, pl->id_poly, pl->lagr, clk_d, n, p->polys);
         if (!u.fuse_nb) axpy_fill(p->st, pl->id_lde, pl->lagr_lde, clk_d, B * n, p->lde);
         ready[0] = true;
         return ZK_OK;
@@ -475,15 +504,17 @@ struct HostTraceCommit {
         FixedColList L;
         for (int c = 0; c < W; c++) {
             if (!((u.fixm >> c) & 1u)) continue;
-            ws[c] = make_fe_ws(last_of(c));
+            const fe last = last_of(c);
+            ws[c] = make_fe_ws(last);
             L.col[L.count] = (uint8_t)c;
             L.slot[L.count] = FS->slot[c];
             L.count++;
+            if (u.coeff_src) source(c, CoeffSrc::BASE, FS->fpolys + (size_t)FS->slot[c] * n, last);
         }
         if (u.fuse_nb) ws[0] = clk_d;  // (column 0 is never in the fixed class: its W set slot carries the clock's d)
         ZK_TRY(h2d_small(p, p->fix_ws, ws, sizeof ws));
         fixed_cols_axpy(p->st, L, false, FS->fpolys, FS->flde, pl->lagr, pl->lagr_lde, p->fix_ws, n, B, p->polys, p->lde,
-                        4 * u.fuse_nb);
+                        4 * u.fuse_nb, !u.coeff_src);
         for (int k = 0; k < L.count; k++) ready[L.col[k]] = true;
         if (u.fuse_nb) {
             FixedHashCols A{};
@@ -708,6 +739,10 @@ int zk::trace_lde_commit(zk_prover *p, Plan *pl, const TraceSrc &src, size_t n, 
     zk_prover::TraceOutcome &tc = p->tc;
     tc.up_bytes = 0;
     tc.up_sparse = tc.up_nw8 = tc.up_nw32 = tc.virt = 0;  // (virt: the host path may take some columns as virtual)
+    // every column's coefficients in polys, unless the host path reads some at their source (HostTraceCommit::source)
+    tc.coeff_src = 0;
+    p->csrc = coeff_plain(p->polys, n);
+    memset(p->csrc_w, 0, sizeof p->csrc_w);
     SparseCols spc{};
     const SparseCols *sp = nullptr;
     if (!src.fixed) ZK_TRY(sparse_begin(p, pl, &spc, &sp));

@@ -26,8 +26,9 @@ struct UploadPlanIn {
     uint32_t snap_mask = 0;  // ... of these columns
     bool hint_ok = true, no_virtual = false;  // TraceSrc
     bool lat_sched = false, detect = true;  // detect: the detection runs; without it no hint is used or learned
-    // the switches (ZK_SPARSE, ZK_NARROW, ZK_CLOCK, ZK_FIXED, ZK_FIXED_FUSE, ZK_VIRTUAL)
+    // the switches (ZK_SPARSE, ZK_NARROW, ZK_CLOCK, ZK_FIXED, ZK_FIXED_FUSE, ZK_VIRTUAL, ZK_COEFF_SRC)
     bool sparse_on = true, narrow_on = true, clock_on = true, fixed_on = true, fixed_fuse_on = true, virtual_on = true;
+    bool coeff_src_on = true;
     size_t n = 0;
 };
 
@@ -49,6 +50,9 @@ struct UploadPlan {
     int pb[W + 1] = {}, np = 0;    // narrow part k: nar[pb[k]] .. nar[pb[k + 1] - 1]
     int gsz[W] = {}, ngroups = 0;  // the dense groups' sizes, in dense[] order
     int fuse_nb = 0;               // leading BLAKE3 blocks whose columns' LDE is formed inside their row hash
+    // The coefficients of the derived clock, the fixed columns and the hinted sparse columns are not written: the stages
+    // that read trace coefficients (boundary quotient, OOD frame, DEEP) take them at their source (CoeffSrc)
+    bool coeff_src = false;
 };
 
 inline UploadPlan upload_plan(const UploadPlanIn &in) {
@@ -115,6 +119,10 @@ inline UploadPlan upload_plan(const UploadPlanIn &in) {
         const uint32_t pre = (P.clk ? 1u : 0u) | P.fixm | (P.hint & ~P.virt);
         while (P.fuse_nb < W / 4 && ((pre >> (4 * P.fuse_nb)) & 0xFu) == 0xFu) P.fuse_nb++;
     }
+    // Coefficient sources: the proofs that form columns from a snapshot (steady state).  The proof that takes the
+    // snapshot reads its own fully written polys, and a caller that reads the trace polynomials (stage dumps:
+    // no_virtual) gets every plane written.
+    P.coeff_src = in.coeff_src_on && !in.no_virtual && P.fixm != 0;
     return P;
 }
 

@@ -436,8 +436,8 @@ int fixed_columns(zk_prover *p, zk_program *prog, const zk::vm::Inputs &in, uint
 }  // namespace
 
 void zk::fixed_axpy(hipStream_t st, const FixedCols &fx, const fe_ws *ws_dev, size_t n, size_t B, fe *polys, fe *lde,
-                    int lde_c0) {
-    AxpyCols A, E;  // coefficients: every preprocessed column; LDE: the ones from lde_c0 on
+                    int lde_c0, bool coeffs) {
+    AxpyCols A, E;  // coefficients: every preprocessed column (coeffs); LDE: the ones from lde_c0 on
     A.ncol = E.ncol = 0;
     size_t ef = 0;
     for (int c = 0; c < W; c++) {
@@ -454,9 +454,10 @@ void zk::fixed_axpy(hipStream_t st, const FixedCols &fx, const fe_ws *ws_dev, si
         ef += c < 12;
     }
     const size_t nf = 12, nz = (size_t)A.ncol - nf;
-    ZK_PROF(st, "fixed_axpy", (double)n * 16 * (1 + 2 * nf + nz),
-            hipLaunchKernelGGL(k_fixed_axpy, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, fx.fpolys, fx.lagr, n, A,
-                               ws_dev, polys));
+    if (coeffs)
+        ZK_PROF(st, "fixed_axpy", (double)n * 16 * (1 + 2 * nf + nz),
+                hipLaunchKernelGGL(k_fixed_axpy, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, fx.fpolys, fx.lagr, n,
+                                   A, ws_dev, polys));
     if (!E.ncol) return;
     ZK_PROF(st, "fixed_axpy", (double)B * n * 16 * (1 + ef + E.ncol),
             hipLaunchKernelGGL(k_fixed_axpy, dim3((unsigned)((B * n + 255) / 256)), dim3(256), 0, st, fx.flde,
@@ -465,9 +466,9 @@ void zk::fixed_axpy(hipStream_t st, const FixedCols &fx, const fe_ws *ws_dev, si
 
 void zk::fixed_cols_axpy(hipStream_t st, const FixedColList &L, bool snapshot, const fe *src_polys, const fe *src_lde,
                          const fe *lagr, const fe *lagr_lde, const fe_ws *ws_dev, size_t n, size_t B, fe *polys, fe *lde,
-                         int lde_c0) {
+                         int lde_c0, bool coeffs) {
     if (L.count <= 0) return;
-    AxpyCols A, E;  // coefficients: every listed column; LDE: the ones from lde_c0 on
+    AxpyCols A, E;  // coefficients: every listed column (coeffs); LDE: the ones from lde_c0 on
     A.ncol = L.count;
     E.ncol = 0;
     for (int k = 0; k < L.count; k++) {
@@ -482,9 +483,10 @@ void zk::fixed_cols_axpy(hipStream_t st, const FixedColList &L, bool snapshot, c
         E.ncol++;
     }
     const char *name = snapshot ? "fixed_snapshot" : "fixed_axpy";
-    ZK_PROF(st, name, (double)n * 16.0 * (1 + 2 * A.ncol),
-            hipLaunchKernelGGL(k_fixed_axpy, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src_polys, lagr, n, A,
-                               ws_dev, polys));
+    if (coeffs)
+        ZK_PROF(st, name, (double)n * 16.0 * (1 + 2 * A.ncol),
+                hipLaunchKernelGGL(k_fixed_axpy, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src_polys, lagr, n, A,
+                                   ws_dev, polys));
     if (!E.ncol) return;
     ZK_PROF(st, name, (double)B * n * 16.0 * (1 + 2 * E.ncol),
             hipLaunchKernelGGL(k_fixed_axpy, dim3((unsigned)((B * n + 255) / 256)), dim3(256), 0, st, src_lde, lagr_lde,

@@ -210,6 +210,29 @@ struct FixedHashCols {
 };
 void fixed_hash(hipStream_t st, const FixedHashCols &A, const fe *lagr_lde, const fe_ws *ws_dev, fe *lde, int ncols,
                 int log_n, int log_b, int nb, uint8_t *leaves);
+// Where the consumers that are linear in the trace polynomials (ood_eval, deep_poly, boundary_poly_add) read trace
+// column c's n coefficients.  A column formed as base_c + w_c e_(n-1) (the derived clock, the fixed class, the hinted
+// sparse columns of a host trace: trace_commit.hip) is read at its source, the sum never written:
+//   PLAIN  plane[c][k]
+//   BASE   plane[c][k] + w_c lagr[k]
+//   ZERO   w_c lagr[k]  (no plane)
+// lagr: e_(n-1)'s coefficients, read once per consumer with the w_c folded into one scalar per linear combination; null
+// when every column is PLAIN.  The scalars w_c are the caller's (host values, passed beside the table).
+struct CoeffSrc {
+    enum : uint8_t { PLAIN = 0, BASE = 1, ZERO = 2 };
+    static constexpr int MAXC = 28;
+    const fe *plane[MAXC];
+    uint8_t mode[MAXC];
+    const fe *lagr;
+    bool derived(int c) const { return mode[c] != PLAIN; }
+};
+// every column PLAIN over ncols (<= 28) column-major planes of n coefficients: the consumers behave as without a table
+inline CoeffSrc coeff_plain(const fe *tpolys, size_t n, int ncols = CoeffSrc::MAXC) {
+    CoeffSrc S{};
+    for (int c = 0; c < ncols; c++) S.plane[c] = tpolys + (size_t)c * n;
+    return S;
+}
+
 // Storage of a FRI layer of L values: natural order (lb = 0), or coset-major over 2^lb cosets of 2^lcn
 // points (natural index i at (i mod 2^lb) 2^lcn + i / 2^lb): layer 0 as the DEEP coset LDE leaves it
 struct FriLayout {
@@ -308,14 +331,15 @@ void comp_cross_mapped(hipStream_t st, const CrossMap &m, const NttTables &T8n, 
 hipError_t eval_constraints(hipStream_t st, const fe *lde, int log_n, int log_b, const fe *periodic, const fe *divs,
                       const AirConsts *consts_dev, fe *comp, bool bnd = true, int nce = 8);
 // add the boundary terms' quotient polynomial (one coefficient plane K) into col0 (n coefficients);
-// c = g^(n-2); scratch: DeepScratch (KX = 1); sets *flag when an assertion fails
-void boundary_poly_add(hipStream_t st, const fe *tpolys, int log_n, const AirConsts &K, fe c, fe *scratch, fe *col0,
-                       unsigned *flag);
+// c = g^(n-2); scratch: DeepScratch (KX = 1); sets *flag when an assertion fails.  S: the trace coefficients' sources;
+// w: the 28 scalars w_c of its BASE and ZERO columns (host; may be null when every column is PLAIN)
+void boundary_poly_add(hipStream_t st, const CoeffSrc &S, const fe *w, int log_n, const AirConsts &K, fe c, fe *scratch,
+                       fe *col0, unsigned *flag);
 // boundary_poly_add split over a sharded rank's coefficient range [k0, k0 + kn) (kn a multiple of
 // ZK_DEEP_RANGE_QUANTUM): begin -> the range's 2 sums on the device; end adds the quotient's range into col0
 // (global index) given ext = the sums of every later range.  The remainder flag is raised by the rank with k0 = 0.
-const fe *boundary_range_begin(hipStream_t st, const fe *tpolys, int log_n, const AirConsts &K, fe c, fe *scratch,
-                               size_t k0, size_t kn);
+const fe *boundary_range_begin(hipStream_t st, const CoeffSrc &S, const fe *w, int log_n, const AirConsts &K, fe c,
+                               fe *scratch, size_t k0, size_t kn);
 void boundary_range_end(hipStream_t st, int log_n, fe c, fe *scratch, size_t k0, size_t kn, const fe *ext, fe *col0,
                         unsigned *flag);
 // cross-coset step of the size-8n interpolation: per k1 < n, from the 8 per-coset inverse NTTs
@@ -338,12 +362,24 @@ void comp_cross_coset(hipStream_t st, const fe *c, int log_n, const NttTables &T
 // tab: KX (128 + 2 ood_waves(n)) elements, partials: KX np ood_waves(n) elements of scratch.
 // (rank, G): only this rank's share of the coefficient range (waves [rank nw / G, (rank + 1) nw / G)), so that the G
 // partial sums of each value add up to it (the sharded prover all-gathers them); (0, 1) = the whole range
+// S: the trace coefficients' sources (W <= 28 columns).  With BASE or ZERO columns (S.lagr set) e_(n-1) is evaluated as
+// one more polynomial: out then holds KX planes of np + 2 values, e(z) and e(zg) last, a BASE column's slots its base's
+// values and a ZERO column's slots zero; ood_fold_sources makes the frame of them on the host.
 int ood_waves(size_t n);
 template <class T>
-void ood_eval(hipStream_t st, const fe *tpolys, int W, const fe *cpolys, int C, int log_n, T z, T zg, fe *tab,
+void ood_eval(hipStream_t st, const CoeffSrc &S, int W, const fe *cpolys, int C, int log_n, T z, T zg, fe *tab,
               fe *partials, fe *out, int rank = 0, int G = 1);
+// values per plane of ood_eval's output
+inline int ood_out_values(const CoeffSrc &S, int W, int C) { return 2 * W + C + (S.lagr ? 2 : 0); }
+// Host: ood_eval's output `raw` (KX planes of ood_out_values) -> hv, KX planes of np = 2 W + C values: T_c(z) =
+// base_c(z) + w_c e(z) and T_c(zg) likewise for the BASE and ZERO columns, in exact field arithmetic (w_c is a base
+// element, so it multiplies each component of an E value)
+void ood_fold_sources(int KX, int W, int C, const CoeffSrc &S, const fe *w, const fe *raw, fe *hv);
 void sum_partials(hipStream_t st, const fe *partials, int npolys, int nblk, fe *out, int b0 = 0, int b1 = -1);
-// DEEP constants in device memory (the combine kernel reads alpha_t and alpha_c in place)
+// DEEP constants in device memory (the combine kernel reads alpha_t and alpha_c in place).  alpha_t[ZK_DEEP_LAGR] weighs
+// e_(n-1)'s coefficients when the trace is read through a CoeffSrc with BASE or ZERO columns: sum_c alpha_t[c] w_c over
+// them (deep_source_weight), zero otherwise
+constexpr int ZK_DEEP_LAGR = 28;
 template <int KX>
 struct DeepConsts {
     typename Chal<KX>::T alpha_t[32];
@@ -351,6 +387,16 @@ struct DeepConsts {
     typename Chal<KX>::T k1, k2, z, zg;
 };
 static_assert(sizeof(DeepConsts<1>) == 52 * sizeof(fe) && sizeof(DeepConsts<2>) == 52 * sizeof(fe2), "DeepConsts layout");
+// Host: D.alpha_t[ZK_DEEP_LAGR] for the sources S with the scalars w (28, host)
+template <int KX>
+inline void deep_source_weight(DeepConsts<KX> &D, const CoeffSrc &S, const fe *w) {
+    typedef Chal<KX> X;
+    typename X::T s = X::zero();
+    if (S.lagr)
+        for (int c = 0; c < CoeffSrc::MAXC; c++)
+            if (S.derived(c)) s = X::add(s, X::mulb(D.alpha_t[c], w[c]));
+    D.alpha_t[ZK_DEEP_LAGR] = s;
+}
 // LDE of one n-coefficient polynomial over `count` cosets r0 + stride*j: out[j*n ..], coset-major.  ntt_tmp: 8n.
 void lde_cosets(hipStream_t st, const NttTables &Tn, const CosetTables &CT, const fe *coeffs, size_t n, size_t r0,
                 size_t stride, int count, fe *out, fe *ntt_tmp);
@@ -374,7 +420,7 @@ struct DeepScratch {
 };
 // The DEEP polynomial's coefficients (KX planes of n) computed into scratch (returned); consts: DeepConsts<KX>
 template <class T>
-const fe *deep_poly(hipStream_t st, const fe *tpolys, const fe *cpolys, int ccols, int log_n,
+const fe *deep_poly(hipStream_t st, const CoeffSrc &S, const fe *cpolys, int ccols, int log_n,
                     const void *deep_consts_dev, T z, T zg, fe *scratch);
 // The same split by coefficient range over the ranks of a sharded proof: rank g computes the range [k0, k0 + kn)
 // (kn a multiple of ZK_DEEP_RANGE_QUANTUM) in two steps around one exchange.  deep_range_begin returns a device
@@ -382,7 +428,7 @@ const fe *deep_poly(hipStream_t st, const fe *tpolys, const fe *cpolys, int ccol
 // range (the suffix carried into this one), and returns the coefficient buffer with this range filled in.
 constexpr size_t ZK_DEEP_RANGE_QUANTUM = 2048;
 template <class T>
-const fe *deep_range_begin(hipStream_t st, const fe *tpolys, const fe *cpolys, int ccols, int log_n,
+const fe *deep_range_begin(hipStream_t st, const CoeffSrc &S, const fe *cpolys, int ccols, int log_n,
                            const void *deep_consts_dev, T z, T zg, fe *scratch, size_t k0, size_t kn);
 template <class T>
 const fe *deep_range_end(hipStream_t st, int log_n, T z, T zg, fe *scratch, size_t k0, size_t kn, const fe *ext);
@@ -390,7 +436,7 @@ const fe *deep_range_end(hipStream_t st, int log_n, T z, T zg, fe *scratch, size
 // by suffix sums over the combined coefficients, one LDE per plane over the B cosets (CosetTables) into ulde
 // (coset-major, KX planes of N), and (out != nullptr) a natural-order copy in out.  scratch: DeepScratch; ntt_tmp: 8n.
 template <class T>
-void deep_coeff_launch(hipStream_t st, const NttTables &Tn, const fe *tpolys, const fe *cpolys, int ccols, int log_n,
+void deep_coeff_launch(hipStream_t st, const NttTables &Tn, const CoeffSrc &S, const fe *cpolys, int ccols, int log_n,
                        int log_b, const void *deep_consts_dev, T z, T zg, const CosetTables &CT, fe *scratch,
                        fe *ulde, fe *ntt_tmp, fe *out);
 // FRI fold constants in device memory; fri_coin_launch writes alpha (KX components) in place

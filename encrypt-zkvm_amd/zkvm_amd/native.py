@@ -34,7 +34,7 @@ EXPORTED = (
     "zk_prover_acquire", "zk_prover_release", "zk_prover_pool_trim", "zk_prover_trace_buffer",
     "zk_prove", "zk_prove_columns", "zk_prove_columns_ex", "zk_host_alloc", "zk_host_free", "zk_host_register",
     "zk_host_unregister", "zk_prove_device", "zk_lde_new", "zk_lde_read_frame", "zk_lde_query", "zk_lde_free",
-    "zk_eval_constraints", "zk_commit_composition", "zk_comp_query", "zk_comp_free", "zk_prover_stage_times", "zk_prover_profile", "zk_prover_kernel_stats", "zk_prover_kernel_ops", "zk_prover_exchange_stats", "zk_prover_exchange_stats_ex", "zk_prover_shard_schedule", "zk_prover_upload_stats", "zk_prover_upload_derived", "zk_prover_upload_fixed", "zk_prover_set_upload_schedule", "zk_prover_proof_info", "zk_vm_trace",
+    "zk_eval_constraints", "zk_commit_composition", "zk_comp_query", "zk_comp_free", "zk_prover_stage_times", "zk_prover_profile", "zk_prover_kernel_stats", "zk_prover_kernel_ops", "zk_prover_exchange_stats", "zk_prover_exchange_stats_ex", "zk_prover_shard_schedule", "zk_prover_upload_stats", "zk_prover_upload_derived", "zk_prover_upload_fixed", "zk_prover_coeff_sources", "zk_prover_set_upload_schedule", "zk_prover_proof_info", "zk_vm_trace",
     "zk_verify", "zk_comm_create_loopback", "zk_comm_unique_id", "zk_comm_create_rccl", "zk_comm_create_host", "zk_comm_destroy", "zk_comm_set_measure", "zk_comm_set_trace_split", "zk_prove_sharded",
     "zk_program_compile", "zk_program_trace", "zk_program_free", "zk_vm_last_error", "zk_vm_trace_device",
     "zk_vm_prove",
@@ -232,6 +232,14 @@ def lib():
         L.zk_prover_upload_stats.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(u32), C.POINTER(u32), C.POINTER(u32)]
         L.zk_prover_upload_derived.argtypes = [vp, C.POINTER(u32)]
         L.zk_prover_upload_fixed.argtypes = [vp, C.POINTER(u32)]
+        if hasattr(L, "zk_prover_coeff_sources"):  # (an A/B library of an earlier commit has none)
+            L.zk_prover_coeff_sources.argtypes = [vp, C.POINTER(u32)]
+            # (in[13] as zk_diag_upload_plan, bit 6 of in[12]: ZK_COEFF_SRC; n) -> UploadPlan::coeff_src
+            L.zk_diag_upload_plan_coeff_src.argtypes = [vp, sz]
+            # (device, planes[29 n], modes[28], w[28], cpolys, ccols, n, ext, z, zg, alpha_t, alpha_c, coeff_b, bnd1, c,
+            #  ood_out, deep_out, col0_out, flag_out)
+            L.zk_diag_coeff_sources.argtypes = [i32, vp, vp, vp, vp, i32, sz, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                vp, vp]
         L.zk_prover_exchange_stats.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), C.POINTER(C.c_double),
                                                C.POINTER(i32), i32, C.POINTER(i32)]
         L.zk_verify.argtypes = [vp, sz, C.POINTER(PubInputs), u32, C.c_char_p, sz]

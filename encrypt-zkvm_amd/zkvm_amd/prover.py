@@ -219,6 +219,13 @@ class GpuProver:
         return {"bytes": b.value, "sparse": cols(sp.value), "narrow8": cols(n8.value), "narrow32": cols(n32.value),
                 "derived": cols(dv.value), "fixed": cols(fx.value)}
 
+    def coeff_sources(self) -> list:
+        """zk_prover_coeff_sources: the columns of the last proof whose interpolation coefficients were read at their
+        source (snapshot plane, identity column, e_(n-1)) by the boundary quotient, OOD and DEEP stages, never written."""
+        m = C.c_uint32(0)
+        check(lib().zk_prover_coeff_sources(self.handle, C.byref(m)))
+        return [c for c in range(28) if (m.value >> c) & 1]
+
     UPLOAD_SCHEDULES = {"auto": 0, "throughput": 1, "latency": 2}
 
     def proof_info(self) -> dict:

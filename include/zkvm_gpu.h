@@ -346,6 +346,12 @@ int zk_prover_upload_derived(zk_prover *p, uint32_t *derived_cols);
  * class.  A fixed column that is also narrow stays listed in narrow8_cols / narrow32_cols of zk_prover_upload_stats;
  * its bytes are not counted: `bytes` is what crossed the link.  ZK_FIXED=0 in the environment turns the class off. */
 int zk_prover_upload_fixed(zk_prover *p, uint32_t *fixed_cols);
+/* the columns of the last proof (bit c) whose interpolation coefficients were never written: once a host-column proof
+ * forms columns from a snapshot, the derived clock, the fixed columns and the hinted sparse columns are each
+ * base_c + w_c e_(n-1) (e_(n-1): the Lagrange interpolant of the last row), and the stages that are linear in the trace
+ * polynomials -- the boundary quotient, the out-of-domain frame, the DEEP combination -- read base_c and e_(n-1) where
+ * they already lie and fold the scalars w_c in.  Same proof bytes.  ZK_COEFF_SRC=0 in the environment writes them. */
+int zk_prover_coeff_sources(zk_prover *p, uint32_t *cols);
 /* How a host-resident trace goes up (zk_prove / zk_prove_columns).  ZK_SCHED_AUTO (the default): the latency schedule
  * for a proof that starts with no other proof in flight on its device, else the throughput schedule.
  * ZK_SCHED_THROUGHPUT: the narrow (packed) columns in two parts through the copy engine between 64-MB column groups.
