@@ -1070,7 +1070,7 @@ __global__ void __launch_bounds__(256) k_hash_rows_blocks(const fe *base, int lo
 #pragma unroll
         for (int e = 0; e < 4; e++) {
             const int c = 4 * blk + e;
-            const fe v = ((vmask >> c) & 1u) ? fe_mul(lg, virt.last[c]) : p[(size_t)e * B * n];
+            const fe v = ((vmask >> c) & 1u) ? fe_mul_uniform(lg, load_fe_ws(virt.last_ws, c)) : p[(size_t)e * B * n];
             m[4 * e + 0] = (uint32_t)v.lo;
             m[4 * e + 1] = (uint32_t)(v.lo >> 32);
             m[4 * e + 2] = (uint32_t)v.hi;
@@ -1511,13 +1511,11 @@ __device__ __forceinline__ fe cube(fe x) { return fe_mul(fe_mul(x, x), x); }
 
 // Rescue MDS (crypto/src/rescue.rs:197-214) as signed small integers: row r = (-a, +b, -c, +d)
 __device__ __forceinline__ fe mds_row(int r, const fe x[4]) {
-    constexpr uint32_t M[16] = {729, 1080, 390, 40, 29160, 42471, 14520, 1210,
-                                882090, 1277640, 429429, 33880, 24698520, 35708310, 11935560, 925771};
     acc160 pos = acc160_zero(), neg = acc160_zero();
-    acc160_madd(neg, x[0], M[4 * r + 0]);
-    acc160_madd(pos, x[1], M[4 * r + 1]);
-    acc160_madd(neg, x[2], M[4 * r + 2]);
-    acc160_madd(pos, x[3], M[4 * r + 3]);
+    acc160_madd(neg, x[0], mds_abs(4 * r + 0));
+    acc160_madd(pos, x[1], mds_abs(4 * r + 1));
+    acc160_madd(neg, x[2], mds_abs(4 * r + 2));
+    acc160_madd(pos, x[3], mds_abs(4 * r + 3));
     return fe_sub(acc160_reduce(pos), acc160_reduce(neg));
 }
 
@@ -1571,6 +1569,7 @@ static constexpr fe ZK_INV3_72 = fe{0x8092deb1ab776293ull, 0xf0185d00eca40a3bull
 struct EvalShared {
     fe ct[20], cb[22], ct2[20], cb2[22];
     fe ct3[4], nct[4], ct3b[4], nctb[4];  // constraints 12..15: ct 3^-72 and -ct (planes a, b)
+    fe u[4], ub[4];                       // their linear half's weights of the cubes (air_fold_mds; planes a, b)
     fe delta, bnd1, bnd1b;
 };
 
@@ -1578,10 +1577,10 @@ struct EvalShared {
 #define ZK_EVAL_LAZY 1  // lazy 288-bit sum over the selector section's terms (base field)
 #endif
 #ifndef ZK_EVAL_WAVES
-#define ZK_EVAL_WAVES 4  // waves per SIMD the register budget targets (measured: 4 > 3 > 1; the LDS stash also caps a CU at 4 blocks)
+#define ZK_EVAL_WAVES 4  // waves per SIMD the register budget targets (measured: 4 > 3 > 1)
 #endif
 #ifndef ZK_EVAL_WAVES_EXT
-#define ZK_EVAL_WAVES_EXT 4  // the two-plane (quadratic extension) variant (4: 110 VGPRs, no spills since the limb sums)
+#define ZK_EVAL_WAVES_EXT 4  // the two-plane (quadratic extension) variant (4: 124 VGPRs, no spills since the limb sums)
 #endif
 // KE coefficient planes: KE = 2 for FieldExtension::Quadratic, where the composition coefficients are
 // E values; the composition is linear in them, so each constraint value is folded into two
@@ -1593,11 +1592,12 @@ __global__ void __launch_bounds__(256, KE == 1 ? ZK_EVAL_WAVES : ZK_EVAL_WAVES_E
                                                           const fe *divs, const AirConsts *K, const AirConsts *K2,
                                                           size_t plane, fe *comp) {
     __shared__ EvalShared S;
-    // lane-private stash of the columns two sections read (the 5 opcode bits, sponge 7 and 8, next-row s0): an LDS
-    // slot instead of a second global load, which missed L2 (PMC: 4.30 GB per launch without, 3.42 with, against
-    // 3.52 GB algorithmic; profiles/r04_pmc_traffic_eval_stash.txt).  8 x 256 x 16 B = 32 KiB per block, so four
-    // 256-thread blocks (16 waves, the register budget's 4 per SIMD) still fit a CU's 160 KiB
-    __shared__ fe stash[8][256];
+    // lane-private stash of what a later section reads again (the opcode value and the push term the selector section
+    // forms from the 5 opcode bits, sponge 7 and 8): an LDS slot instead of a second global load, which missed L2 (PMC:
+    // 4.30 GB per launch without, 3.42 with, against 3.52 GB algorithmic; profiles/r04_pmc_traffic_eval_stash.txt).
+    // 4 x 256 x 16 B = 16 KiB per block: four 256-thread blocks (16 waves, the register budget's 4 per SIMD) fit a
+    // CU's 160 KiB with room to spare (up to 8 slots would)
+    __shared__ fe stash[4][256];
     const int tid = threadIdx.x;
     {
         // one LDS slot per thread, every range bounded on both sides
@@ -1614,6 +1614,8 @@ __global__ void __launch_bounds__(256, KE == 1 ? ZK_EVAL_WAVES : ZK_EVAL_WAVES_E
             S.ct3b[t - 84] = fe_mul(K2->coeff_t[12 + t - 84], ZK_INV3_72);
             S.nctb[t - 84] = fe_neg(K2->coeff_t[12 + t - 84]);
         }
+        else if (t >= 88 && t < 92) S.u[t - 88] = air_fold_mds(K->coeff_t + 12, t - 88);
+        else if (KE == 2 && t >= 92 && t < 96) S.ub[t - 92] = air_fold_mds(K2->coeff_t + 12, t - 92);
         else if (KE == 2 && t >= 128 && t < 148) S.ct2[t - 128] = K2->coeff_t[t - 128];
         else if (KE == 2 && t >= 148 && t < 170) S.cb2[t - 148] = K2->coeff_b[t - 148];
         __syncthreads();
@@ -1635,8 +1637,6 @@ __global__ void __launch_bounds__(256, KE == 1 ? ZK_EVAL_WAVES : ZK_EVAL_WAVES_E
 #define CUR(c) cb[(size_t)(c)*cs + q]
 #define NXT(c) cb[(size_t)(c)*cs + qn]
     const fe one = fe_one();
-    const fe s0n = NXT(12);
-    stash[5][tid] = s0n;
     fe t = fe_zero();  // sum of coeff_t[k] * C_k (kept reduced: a lazy 288-bit sum here costs 130 spills)
     fe t2 = fe_zero();  // the b-plane sum (KE = 2)
 #define ZK_ACC(k, val)                                                    \
@@ -1648,88 +1648,9 @@ __global__ void __launch_bounds__(256, KE == 1 ? ZK_EVAL_WAVES : ZK_EVAL_WAVES_E
             asm volatile("" : "+v"(t2.lo), "+v"(t2.hi));                  \
         }                                                                 \
     } while (0)
-    // 12..19 Rescue round / copy (constrains.rs:182-216) first: it needs only the opcode value and
-    // is_push from the flags, so the ten selectors below are never live across it.
-    {
-        const fe b0 = CUR(5), b1 = CUR(4), b2 = CUR(3), b3 = CUR(2), b4 = CUR(1);
-        stash[0][tid] = b0;
-        stash[1][tid] = b1;
-        stash[2][tid] = b2;
-        stash[3][tid] = b3;
-        stash[4][tid] = b4;
-        // opcode = 16 b0 + 8 b1 + 4 b2 + 2 b3 + b4  (Horner by doubling: bits are field elements)
-        fe opc = b0;
-        opc = fe_add(fe_add(opc, opc), b1);
-        opc = fe_add(fe_add(opc, opc), b2);
-        opc = fe_add(fe_add(opc, opc), b3);
-        opc = fe_add(fe_add(opc, opc), b4);
-        // is_push = b0 (1-b1)(1-b2)(1-b3)(1-b4)  (flags.rs)
-        const fe push_term = fe_mul(s0n, fe_mul(fe_mul(fe_mul(fe_mul(b0, fe_sub(one, b1)), fe_sub(one, b2)),
-                                                            fe_sub(one, b3)), fe_sub(one, b4)));
-        ZK_SEQ(cb, push_term.lo);
-        const fe *per = periodic + (i & 127) * 9;
-        fe x[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-            const fe c = CUR(7 + k);
-            if (k < 2) stash[6 + k][tid] = c;
-            x[k] = cube(c);
-        }
-        fe m0[4];
-#pragma unroll
-        for (int r2 = 0; r2 < 4; r2++) m0[r2] = fe_add(mds_row(r2, x), per[1 + r2]);
-        m0[0] = fe_add(m0[0], opc);
-        m0[1] = fe_add(m0[1], push_term);
-        ZK_SEQ(cb, m0[3].lo);
-        const fe h0 = CUR(6);
-        const fe fh = fe_mul(per[0], h0);
-        const fe nfh = fe_sub(h0, fh);  // (1 - hash_flag) * h0
-        fe y[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) y[k] = fe_sub(NXT(7 + k), per[5 + k]);
-        // 12..15 share the factor fh and 16..19 the factor nfh: sum the coefficient-weighted values first,
-        // multiply by the flag once (ct_k (v_k f) summed = f (sum ct_k v_k): 6 multiplies fewer per row)
-        fe sR = fe_zero(), sR2 = fe_zero();
-        {
-            // ct_r ((INV_MDS y)_r^3 - m0_r) = ct3_r (adj_r y)^3 + (-ct_r) m0_r, summed lazily
-            acc288 aR = acc288_zero(), aR2 = acc288_zero();
-#pragma unroll
-            for (int r2 = 0; r2 < 4; r2++) {
-                const fe v3 = cube(adj_row(r2, y));
-                acc288_madd(aR, S.ct3[r2], v3);
-                acc288_madd(aR, S.nct[r2], m0[r2]);
-                if (KE == 2) {
-                    acc288_madd(aR2, S.ct3b[r2], v3);
-                    acc288_madd(aR2, S.nctb[r2], m0[r2]);
-                }
-            }
-            sR = acc288_reduce(aR);
-            if (KE == 2) sR2 = acc288_reduce(aR2);
-        }
-        t = fe_add(t, fe_mul(sR, fh));
-        if (KE == 2) t2 = fe_add(t2, fe_mul(sR2, fh));
-        ZK_SEQ(cb, t.lo);
-        {
-            const fe c7 = stash[6][tid], c8 = stash[7][tid];
-            const fe d16 = fe_sub(NXT(7), c7), d17 = fe_sub(NXT(8), c8), n9 = NXT(9), n10 = NXT(10);
-            acc288 aC = acc288_zero();
-            acc288_madd(aC, S.ct[16], d16);
-            acc288_madd(aC, S.ct[17], d17);
-            acc288_madd(aC, S.ct[18], n9);
-            acc288_madd(aC, S.ct[19], n10);
-            t = fe_add(t, fe_mul(acc288_reduce(aC), nfh));
-            if (KE == 2) {
-                acc288 aD = acc288_zero();
-                acc288_madd(aD, S.ct2[16], d16);
-                acc288_madd(aD, S.ct2[17], d17);
-                acc288_madd(aD, S.ct2[18], n9);
-                acc288_madd(aD, S.ct2[19], n10);
-                t2 = fe_add(t2, fe_mul(acc288_reduce(aD), nfh));
-            }
-        }
-    }
-    ZK_SEQ(cb, t.lo);
-    // 0..11: degree-5 selectors (flags.rs:45-79) with shared prefixes, each consumed right away.
+    // 0..11 first: degree-5 selectors (flags.rs:45-79) with shared prefixes, each consumed right away.  The Rescue
+    // section after it needs only the opcode value and s0' is_push from the flags, and is_push is one more factor on
+    // this section's push / read prefix: both wait in the stash, so no selector is live across the Rescue round.
     // Sibling selectors share one multiply: P*(1 - b) = P - P*b.  Two pairs of constraints are folded
     // before their coefficient (3/6 and 8/9 differ only in the last bit b4):
     //   ct3*(X(1-b4))*d3 + ct6*(X b4)*d6 = X*(ct3 d3 + b4 (ct6 d6 - ct3 d3))
@@ -1745,10 +1666,19 @@ __global__ void __launch_bounds__(256, KE == 1 ? ZK_EVAL_WAVES : ZK_EVAL_WAVES_E
         else ZK_ACC(k, val);                             \
     } while (0)
 #define ZK_SEQS() ZK_SEQ(cb, LZ ? aS.w[0] : (uint32_t)t.lo)
-        const fe b0 = stash[0][tid], b1 = stash[1][tid], b2 = stash[2][tid], b3 = stash[3][tid], b4 = stash[4][tid];
+        const fe b0 = CUR(5), b1 = CUR(4), b2 = CUR(3), b3 = CUR(2), b4 = CUR(1);
+        {
+            // opcode = 16 b0 + 8 b1 + 4 b2 + 2 b3 + b4  (Horner by doubling: bits are field elements)
+            fe opc = b0;
+            opc = fe_add(fe_add(opc, opc), b1);
+            opc = fe_add(fe_add(opc, opc), b2);
+            opc = fe_add(fe_add(opc, opc), b3);
+            opc = fe_add(fe_add(opc, opc), b4);
+            stash[0][tid] = opc;
+        }
         const fe nb0 = fe_sub(one, b0), nb2 = fe_sub(one, b2), nb3 = fe_sub(one, b3), nb4 = fe_sub(one, b4);
         const fe s0 = CUR(12), s1 = CUR(13);
-        const fe s0n = stash[5][tid];  // (shadows the first section's: no live range across)
+        const fe s0n = NXT(12);
         // 0 clock, 2 shift
         ZK_ACCS(0, fe_sub(NXT(0), fe_add(CUR(0), one)));
         const fe b01 = fe_mul(b0, b1);
@@ -1812,6 +1742,8 @@ __global__ void __launch_bounds__(256, KE == 1 ? ZK_EVAL_WAVES : ZK_EVAL_WAVES_E
             const fe p0 = fe_mul(b0n1, nb2);     // b0 (1-b1)(1-b2)
             const fe p0b3 = fe_mul(p0, b3);
             const fe p0n3 = fe_sub(p0, p0b3);
+            // is_push = b0 (1-b1)(1-b2)(1-b3)(1-b4) = p0n3 (1-b4)  (flags.rs); constraint 13's s0' is_push
+            stash[1][tid] = fe_mul(s0n, fe_mul(p0n3, nb4));
             is_read2 = fe_mul(p0b3, nb4);
             const fe zd1 = fe_mul(p0n3, fe_sub(NXT(13), s0));
             const fe i89 = fe_add(S.ct[8], fe_mul(b4, fe_sub(S.ct[9], S.ct[8])));
@@ -1834,6 +1766,78 @@ __global__ void __launch_bounds__(256, KE == 1 ? ZK_EVAL_WAVES : ZK_EVAL_WAVES_E
         if (LZ) t = fe_add(t, acc288_reduce(aS));
 #undef ZK_ACCS
 #undef ZK_SEQS
+    }
+    ZK_SEQ(cb, t.lo);
+    // 12..19 Rescue round / copy (constrains.rs:182-216)
+    {
+        const fe opc = stash[0][tid], push_term = stash[1][tid];
+        const fe *per = periodic + (i & 127) * 9;
+        // 12..15 are ct_r ((INV_MDS y)_r^3 - m0_r) with m0_r = (MDS x)_r + ark_r, + opc for r = 0, + push_term for r = 1.
+        // The m0 half is linear in the cubes x: sum_r (-ct_r) m0_r = sum_k u_k x_k + pv[i mod 128] - ct_0 opc - ct_1 push_term
+        // (u and pv folded per proof: air_fold_mds, AirConsts::pv), summed lazily from pv on -- no MDS row per step
+        acc288 aR = acc288_zero(), aR2 = acc288_zero();
+        {
+            const fe pv = K->pv[i & 127];
+            aR.w[0] = lo32(pv.lo), aR.w[1] = hi32(pv.lo), aR.w[2] = lo32(pv.hi), aR.w[3] = hi32(pv.hi);
+            acc288_madd(aR, S.nct[0], opc);
+            acc288_madd(aR, S.nct[1], push_term);
+            if (KE == 2) {
+                const fe pvb = K2->pv[i & 127];
+                aR2.w[0] = lo32(pvb.lo), aR2.w[1] = hi32(pvb.lo), aR2.w[2] = lo32(pvb.hi), aR2.w[3] = hi32(pvb.hi);
+                acc288_madd(aR2, S.nctb[0], opc);
+                acc288_madd(aR2, S.nctb[1], push_term);
+            }
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const fe c = CUR(7 + k);
+            if (k < 2) stash[2 + k][tid] = c;
+            const fe x = cube(c);
+            acc288_madd(aR, S.u[k], x);
+            if (KE == 2) acc288_madd(aR2, S.ub[k], x);
+        }
+        ZK_SEQ(cb, aR.w[0]);
+        const fe h0 = CUR(6);
+        const fe fh = fe_mul(per[0], h0);
+        const fe nfh = fe_sub(h0, fh);  // (1 - hash_flag) * h0
+        fe y[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) y[k] = fe_sub(NXT(7 + k), per[5 + k]);
+        // 12..15 share the factor fh and 16..19 the factor nfh: sum the coefficient-weighted values first,
+        // multiply by the flag once (ct_k (v_k f) summed = f (sum ct_k v_k): 6 multiplies fewer per row)
+        fe sR = fe_zero(), sR2 = fe_zero();
+        {
+            // ct_r (INV_MDS y)_r^3 = ct3_r (adj_r y)^3, into the same lazy sums
+#pragma unroll
+            for (int r2 = 0; r2 < 4; r2++) {
+                const fe v3 = cube(adj_row(r2, y));
+                acc288_madd(aR, S.ct3[r2], v3);
+                if (KE == 2) acc288_madd(aR2, S.ct3b[r2], v3);
+            }
+            sR = acc288_reduce(aR);
+            if (KE == 2) sR2 = acc288_reduce(aR2);
+        }
+        t = fe_add(t, fe_mul(sR, fh));
+        if (KE == 2) t2 = fe_add(t2, fe_mul(sR2, fh));
+        ZK_SEQ(cb, t.lo);
+        {
+            const fe c7 = stash[2][tid], c8 = stash[3][tid];
+            const fe d16 = fe_sub(NXT(7), c7), d17 = fe_sub(NXT(8), c8), n9 = NXT(9), n10 = NXT(10);
+            acc288 aC = acc288_zero();
+            acc288_madd(aC, S.ct[16], d16);
+            acc288_madd(aC, S.ct[17], d17);
+            acc288_madd(aC, S.ct[18], n9);
+            acc288_madd(aC, S.ct[19], n10);
+            t = fe_add(t, fe_mul(acc288_reduce(aC), nfh));
+            if (KE == 2) {
+                acc288 aD = acc288_zero();
+                acc288_madd(aD, S.ct2[16], d16);
+                acc288_madd(aD, S.ct2[17], d17);
+                acc288_madd(aD, S.ct2[18], n9);
+                acc288_madd(aD, S.ct2[19], n10);
+                t2 = fe_add(t2, fe_mul(acc288_reduce(aD), nfh));
+            }
+        }
     }
     ZK_SEQ(cb, t.lo);
     // divisors (per-row factors from divisor_tables): transition (x^n - 1)/((x - g^(n-2))(x - g^(n-1)));

@@ -833,13 +833,17 @@ Coin zk::seed_coin(size_t n, const zk_options *opt, const zk_pub_inputs *pub) {
     return coin;
 }
 
-// assertions (air/src/lib.rs:170-195) sorted by (stride, first_step, column) [P3]; CE-coset constants
-static void set_bnd1(AirConsts &K) {
+// what a plane's constants derive from its own coefficients: bnd1 and the folded round constants pv
+// (per: the periodic columns over the CE steps, periodic_table(n))
+static void set_coeff_derived(AirConsts &K, const fe *per) {
     K.bnd1 = fe_zero();
     for (int k = 12; k < NUM_ASSERTS; k++) K.bnd1 = fe_add(K.bnd1, fe_mul(K.coeff_b[k], K.assert_val[k]));
+    air_fold_periodic(K.coeff_t + 12, per, K.pv);
 }
 
-static void air_static_consts(const zk_pub_inputs *pub, size_t n, AirConsts &K) {
+// assertions (air/src/lib.rs:170-195) sorted by (stride, first_step, column) [P3]; CE-coset constants
+// returns the host copy of the periodic table of n (valid for the thread's lifetime)
+static const fe *air_static_consts(const zk_pub_inputs *pub, size_t n, AirConsts &K) {
     const int log_n = ilog2(n);
     const int first_cols[12] = {0, 7, 8, 11, 12, 13, 14, 15, 16, 17, 18, 19};
     int k = 0;
@@ -862,6 +866,7 @@ static void air_static_consts(const zk_pub_inputs *pub, size_t n, AirConsts &K) 
     // 10 exponentiations, host time the GPU would otherwise wait for on every proof)
     struct DivConsts {
         fe xr[8], inv_zn[8], g_last2, g_last1;
+        std::vector<fe> per;  // periodic_table(n)
     };
     static thread_local std::map<size_t, DivConsts> cache;
     auto it = cache.find(n);
@@ -876,7 +881,8 @@ static void air_static_consts(const zk_pub_inputs *pub, size_t n, AirConsts &K) 
         }
         d.g_last2 = h_pow(g, n - 2);
         d.g_last1 = h_pow(g, n - 1);
-        it = cache.emplace(n, d).first;
+        d.per = periodic_table(n);
+        it = cache.emplace(n, std::move(d)).first;
     }
     memcpy(K.xr, it->second.xr, sizeof K.xr);
     memcpy(K.inv_zn, it->second.inv_zn, sizeof K.inv_zn);
@@ -884,7 +890,8 @@ static void air_static_consts(const zk_pub_inputs *pub, size_t n, AirConsts &K) 
     K.g_last1 = it->second.g_last1;
     K.delta = fe_make(pub->delta);
     K.lwe_size = (int)pub->lwe_size;
-    set_bnd1(K);
+    set_coeff_derived(K, it->second.per.data());
+    return it->second.per.data();
 }
 
 // K[j]: the constants with component j of every coefficient (KX planes; the record keeps the a components)
@@ -900,13 +907,13 @@ void zk::draw_air_consts(Coin &coin, const zk_pub_inputs *pub, size_t n, int KX,
         for (int j = 0; j < KX; j++) K[j].coeff_b[k] = j ? v.b : v.a;
         fe_to_bytes(v.a, R.coeff_b[k]);
     }
-    air_static_consts(pub, n, K[0]);
+    const fe *per = air_static_consts(pub, n, K[0]);
     if (KX == 2) {  // the b plane: the same constants around its own coefficients
         const AirConsts b = K[1];
         K[1] = K[0];
         memcpy(K[1].coeff_t, b.coeff_t, sizeof b.coeff_t);
         memcpy(K[1].coeff_b, b.coeff_b, sizeof b.coeff_b);
-        set_bnd1(K[1]);
+        set_coeff_derived(K[1], per);
     }
 }
 
@@ -1490,9 +1497,28 @@ static int prove_once(zk_prover *p, const TraceSrc &src, size_t n, const zk_opti
     // S5: OOD frame [P7], DEEP coefficients [P8] and evaluations.  h holds the frame flattened
     // (k base elements per E value): [T(z)]_W ++ [T(zg)]_W ++ [H(z)]_C.
     std::vector<fe> h;
-    ZK_TRY(with_kx(KX, [&](auto kx) {
-        return ood_deep_stage<decltype(kx)::value>(p, pl, coin, R, HT, C, Kp, pub, lb0 ? nullptr : deep, h);
-    }));
+    // the stage dumps up to the composition commitment (E-valued stages dump their a component, as the oracle does)
+    auto dump_front = [&]() -> int {
+        if (dump->trace_polys) ZK_CHECK_HIP(hipMemcpy(dump->trace_polys, p->polys, (size_t)W * n * 16, hipMemcpyDeviceToHost));
+        if (dump->trace_lde) coset_major_rows_to_host(p, p->lde, W, n, B, dump->trace_lde);
+        if (dump->trace_leaves) ZK_CHECK_HIP(hipMemcpy(dump->trace_leaves, p->leaves, 32 * N, hipMemcpyDeviceToHost));
+        if (dump->composition) coset_major_rows_to_host(p, comp, 1, n, 8, dump->composition);
+        if (dump->comp_polys) ZK_CHECK_HIP(hipMemcpy(dump->comp_polys, p->cpolys, (size_t)CK * n * 16, hipMemcpyDeviceToHost));
+        if (dump->comp_lde) coset_major_rows_to_host(p, clde, CK, n, B, dump->comp_lde);
+        return ZK_OK;
+    };
+    {
+        const int rc = with_kx(KX, [&](auto kx) {
+            return ood_deep_stage<decltype(kx)::value>(p, pl, coin, R, HT, C, Kp, pub, lb0 ? nullptr : deep, h);
+        });
+        // a trace the AIR rejects ends here (the out-of-domain identity): the stages that ran are still dumped, as the
+        // oracle dumps them, so the evaluator can be compared on traces no program produces
+        if (rc == ZK_ERR_DEGREE && dump) {
+            ZK_CHECK_HIP(hipStreamSynchronize(p->st));
+            ZK_TRY(dump_front());
+        }
+        if (rc != ZK_OK) return rc;
+    }
     stage_mark(p, "deep");
 
     // S6: FRI [P9, P10]; E layers are planar (k planes of L values)
@@ -1588,13 +1614,8 @@ static int prove_once(zk_prover *p, const TraceSrc &src, size_t n, const zk_opti
     collect_kernel_stats(p);
 
     if (rec) *rec = R;
-    if (dump) {  // E-valued stages dump their a component (as the oracle does)
-        if (dump->trace_polys) ZK_CHECK_HIP(hipMemcpy(dump->trace_polys, p->polys, (size_t)W * n * 16, hipMemcpyDeviceToHost));
-        if (dump->trace_lde) coset_major_rows_to_host(p, p->lde, W, n, B, dump->trace_lde);
-        if (dump->trace_leaves) ZK_CHECK_HIP(hipMemcpy(dump->trace_leaves, p->leaves, 32 * N, hipMemcpyDeviceToHost));
-        if (dump->composition) coset_major_rows_to_host(p, comp, 1, n, 8, dump->composition);
-        if (dump->comp_polys) ZK_CHECK_HIP(hipMemcpy(dump->comp_polys, p->cpolys, (size_t)CK * n * 16, hipMemcpyDeviceToHost));
-        if (dump->comp_lde) coset_major_rows_to_host(p, clde, CK, n, B, dump->comp_lde);
+    if (dump) {
+        ZK_TRY(dump_front());
         if (dump->deep) {
             if (lb0) coset_major_to_natural(p->st, deep0, log_n, log_b, deep);
             ZK_CHECK_HIP(hipStreamSynchronize(p->st));
@@ -2058,6 +2079,16 @@ extern "C" void zk_diag_dot_host(const uint8_t *a, const uint8_t *b, size_t coun
 extern "C" void zk_diag_mul_limbs_host(const uint8_t *a, const uint8_t *b, uint8_t *out, size_t count) {
     for (size_t i = 0; i < count; i++) fe_to_bytes(fe_mul_limbs(fe_from_bytes(a + 16 * i), fe_from_bytes(b + 16 * i)), out + 16 * i);
 }
+// Host: the constants the evaluator folds from the coefficients of constraints 12..15 (ct: 4 elements) at trace
+// length n: u[4] as the kernel's prologue forms them (air_fold_mds) and the pv[128] table of AirConsts
+extern "C" void zk_diag_air_fold_host(const uint8_t *ct, size_t n, uint8_t *u_out, uint8_t *pv_out) {
+    fe c[4], pv[128];
+    for (int r = 0; r < 4; r++) c[r] = fe_from_bytes(ct + 16 * r);
+    for (int k = 0; k < 4; k++) fe_to_bytes(air_fold_mds(c, k), u_out + 16 * k);
+    const std::vector<fe> per = periodic_table(n);
+    air_fold_periodic(c, per.data(), pv);
+    for (int j = 0; j < 128; j++) fe_to_bytes(pv[j], pv_out + 16 * j);
+}
 extern "C" void zk_diag_blake3_host(const uint8_t *in, size_t len, uint8_t out[32]) { b3::hash_bytes(in, len, out); }
 
 // Host: the upload plan of a host-trace commitment (upload_plan.hpp).  in[13] = have, sparse, nw8, nw32, clk_off,
@@ -2198,6 +2229,36 @@ extern "C" int zk_diag_blake3_rows(int device, const uint8_t *rows, int k, size_
     uint8_t *dout = (uint8_t *)(d + count * k);
     diag_blake3_elems(nullptr, d, k, count, dout);
     hipError_t e = hipMemcpy(out, dout, 32 * count, hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    ZK_CHECK_HIP(e);
+    return ZK_OK;
+}
+
+// GPU leaf hashes of the 28-column rows of a coset-major LDE (lde[(c blowup + r) n + q]) whose columns in `mask` are
+// virtual: never read, formed as last[c] * lagr_lde[r n + q] (hash_rows_blocks with VirtCols, as the host-trace
+// commitment launches it).  Two launches, blocks [0, split) and [split, 7); leaves in natural order (32 B each).
+extern "C" int zk_diag_hash_rows_virtual(int device, const uint8_t *lde, size_t n, uint32_t blowup, uint32_t mask,
+                                         const uint8_t *last, const uint8_t *lagr_lde, int split, uint8_t *leaves) {
+    if (!lde || !last || !lagr_lde || !leaves || n < 2 || (n & (n - 1)) || blowup < 2 || (blowup & (blowup - 1)) ||
+        blowup > 64 || split < 1 || split > W / 4 || (mask >> W))
+        ZK_FAIL(ZK_ERR_INVALID_ARG, "invalid argument");
+    ZK_CHECK_HIP(hipSetDevice(device));
+    const size_t N = n * blowup;
+    fe_ws ws[W];
+    for (int c = 0; c < W; c++) ws[c] = make_fe_ws(fe_from_bytes(last + 16 * c));
+    uint8_t *d = nullptr;
+    const size_t o_lagr = (size_t)W * N * sizeof(fe), o_ws = o_lagr + N * sizeof(fe), o_leaves = o_ws + sizeof ws;
+    ZK_CHECK_HIP(hipMalloc(&d, o_leaves + 32 * N));
+    hipError_t e = hipMemcpy(d, lde, o_lagr, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d + o_lagr, lagr_lde, N * sizeof(fe), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(d + o_ws, ws, sizeof ws, hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+        const VirtCols v{mask, (const fe_ws *)(d + o_ws), (const fe *)(d + o_lagr)};
+        hash_rows_blocks(nullptr, (const fe *)d, W, ilog2(n), ilog2(blowup), 0, split, d + o_leaves, v);
+        if (split < W / 4) hash_rows_blocks(nullptr, (const fe *)d, W, ilog2(n), ilog2(blowup), split, W / 4, d + o_leaves, v);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(leaves, d + o_leaves, 32 * N, hipMemcpyDeviceToHost);
     (void)hipFree(d);
     ZK_CHECK_HIP(e);
     return ZK_OK;

@@ -211,6 +211,7 @@ struct zk_prover {
     fe_ws *fix_ws = nullptr;      // zk_vm_prove: the W sets of the last-row values of the preprocessed columns
     unsigned *sp_nz = nullptr;    // sparse-column flags of the current trace (SparseCols), W entries + 2W width flags
     fe *sp_last = nullptr;        // ... and the trace's last row
+    fe_ws *sp_last_ws = nullptr;  // host traces: the W sets of the hinted sparse columns' last rows (VirtCols)
     // Hints (host-resident traces, prove_impl): the columns the previous proof of the same trace length AND program
     // (zk_pub_inputs::program_hash: column classes are a property of the program) found sparse are taken as sparse from
     // their last row alone and never uploaded; host threads check them during the proof (sp_bad: the hinted columns

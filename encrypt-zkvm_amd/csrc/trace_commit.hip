@@ -205,6 +205,7 @@ int zk::sparse_begin(zk_prover *p, Plan *pl, SparseCols *out, const SparseCols *
     if (!p->sp_nz) {
         ZK_CHECK_HIP(p->arena.alloc(&p->sp_nz, 4 * W));  // nonzero, 8-bit, 32-bit flags; [3W]: column 0 not the clock
         ZK_CHECK_HIP(p->arena.alloc(&p->sp_last, W));
+        ZK_CHECK_HIP(p->arena.alloc(&p->sp_last_ws, W));
         ZK_CHECK_HIP(hipHostMalloc((void **)&p->sp_h, 3 * W * sizeof(unsigned), hipHostMallocDefault));
     }
     ZK_CHECK_HIP(hipMemsetAsync(p->sp_nz, 0, 4 * W * sizeof(unsigned), p->st));
@@ -421,7 +422,7 @@ struct HostTraceCommit {
         while (b < W / 4 && ready[4 * b] && ready[4 * b + 1] && ready[4 * b + 2] && ready[4 * b + 3]) b++;
         if (b - hashed >= 2 || (last && b > hashed)) {
             hash_rows_blocks(p->st, p->lde, W, pl->log_n, pl->log_b, hashed, b, p->leaves,
-                             VirtCols{p->tc.virt, p->sp_last, pl->lagr_lde});
+                             VirtCols{p->tc.virt, p->sp_last_ws, pl->lagr_lde});
             hashed = b;
         }
     }
@@ -467,6 +468,12 @@ struct HostTraceCommit {
         fe lastv[W] = {};
         for (int i = 0; i < u.nh; i++) lastv[u.hin[i]] = last_of(u.hin[i]);
         ZK_TRY(h2d_small(p, p->sp_last, lastv, sizeof lastv));
+        if (u.virt) {  // the row hash multiplies e_(n-1)'s LDE by these through their W sets
+            fe_ws ws[W] = {};
+            for (int c = 0; c < W; c++)
+                if ((u.virt >> c) & 1u) ws[c] = make_fe_ws(lastv[c]);
+            ZK_TRY(h2d_small(p, p->sp_last_ws, ws, sizeof ws));
+        }
         if (u.coeff_src)
             for (int i = 0; i < u.nh; i++) source(u.hin[i], CoeffSrc::ZERO, nullptr, lastv[u.hin[i]]);
         else

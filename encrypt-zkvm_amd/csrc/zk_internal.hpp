@@ -188,10 +188,13 @@ void commit_rows_coset_major(hipStream_t st, const fe *base, int ncols, int log_
 // blocks b0 .. b1 - 1 of the leaf hashes of all B n rows of a coset-major column set of ncols (a multiple of 4,
 // <= 64) columns: columns 4 b .. 4 b + 3 compressed into the chaining value each leaf slot carries between launches
 // Virtual trace columns (host traces, trace_commit.hip): sparse columns whose LDE is never written; the row hashing forms
-// column c's value at LDE point (coset r, position q) as last[c] * lagr_lde[r n + q]
+// column c's value at LDE point (coset r, position q) as last[c] * lagr_lde[r n + q], last[c] the column's last row.
+// last_ws[c] = make_fe_ws(last[c]): the value is uniform over the launch, so the product goes through
+// fe_mul_uniform, as in fixed_hash
 struct VirtCols {
     uint32_t mask = 0;
-    const fe *last = nullptr, *lagr_lde = nullptr;
+    const fe_ws *last_ws = nullptr;
+    const fe *lagr_lde = nullptr;
 };
 void hash_rows_blocks(hipStream_t st, const fe *base, int ncols, int log_n, int log_b, int b0, int b1, uint8_t *leaves,
                       VirtCols virt = VirtCols());
@@ -273,7 +276,34 @@ struct AirConsts {
     fe delta;
     fe bnd1;  // sum_k coeff_b[12+k] * assert_val[12+k]: the step n-2 group's values, subtracted once per row
     int lwe_size;
+    // pv[j] = sum_r (-coeff_t[12+r]) periodic[j][1+r] over the 128 CE steps j = i mod 128: the round constants' share
+    // of constraints 12..15, folded with this plane's coefficients (air_fold_periodic)
+    fe pv[128];
 };
+// |MDS| of the Rescue round (crypto/src/rescue.rs:197-214): row r = (-a, +b, -c, +d), every entry below 2^26
+ZK_HD uint32_t mds_abs(int i) {
+    constexpr uint32_t M[16] = {729, 1080, 390, 40, 29160, 42471, 14520, 1210,
+                                882090, 1277640, 429429, 33880, 24698520, 35708310, 11935560, 925771};
+    return M[i];
+}
+// Constraints 12..15 are ct_r (v_r - m0_r) with m0_r = (MDS x)_r + ark_r (+ opcode, + push) linear in the cubes x: their
+// linear half sum_r (-ct_r) m0_r is folded per proof into u_k = sum_r (-ct_r) MDS[r][k] and the table pv above, so a row
+// pays four products u_k x_k and no MDS row.  ct = coeff_t + 12.  (Four 128 x 26-bit products stay below 2^160.)
+ZK_HD fe air_fold_mds(const fe *ct, int k) {
+    acc160 a = acc160_zero();
+    for (int r = 0; r < 4; r++) acc160_madd(a, ct[r], mds_abs(4 * r + k));
+    const fe s = acc160_reduce(a);  // column k is negative for even k: (-ct_r)(-|M|) = ct_r |M|
+    return (k & 1) ? fe_neg(s) : s;
+}
+// per: the 128 x 9 table of the periodic columns over the CE steps (the evaluator's `periodic`, on the host)
+inline void air_fold_periodic(const fe *ct, const fe *per, fe pv[128]) {
+    const fe nct[4] = {fe_neg(ct[0]), fe_neg(ct[1]), fe_neg(ct[2]), fe_neg(ct[3])};
+    for (int j = 0; j < 128; j++) {
+        fe s = fe_zero();
+        for (int r = 0; r < 4; r++) s = fe_add(s, fe_mul(nct[r], per[9 * j + 1 + r]));  // (host fe_mul: ~5 ns)
+        pv[j] = s;
+    }
+}
 // inverse of (x - a) * (x - b) over the B cosets, written coset-major: out[r*n + q] for the point
 // x = xr[r] * w_n^q (natural domain index i = r + B*q)
 void batch_inv_pairs(hipStream_t st, const NttTables &Tn, const fe *xr, int log_b, int log_n, fe a, fe b,

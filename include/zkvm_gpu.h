@@ -94,7 +94,8 @@ typedef struct {
     uint64_t positions[ZK_MAX_QUERIES + 1];
 } zk_record;
 
-/* Optional host copies of full-size intermediates (NULL = skip), natural LDE order. */
+/* Optional host copies of full-size intermediates (NULL = skip), natural LDE order.  A trace the AIR rejects at
+ * the out-of-domain identity (ZK_ERR_DEGREE before the DEEP stage) still fills the six up to comp_lde. */
 typedef struct {
     uint8_t *trace_polys;  /* 28 * n coefficients, column-major */
     uint8_t *trace_lde;    /* N * 28, row-major */
