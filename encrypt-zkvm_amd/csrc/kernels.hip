@@ -1919,49 +1919,28 @@ hipError_t upload_rescue_consts(hipStream_t st) {
     return e;
 }
 
-hipError_t eval_constraints(hipStream_t st, const fe *lde, int log_n, int log_b, const fe *periodic, const fe *divs,
-                      const AirConsts *consts_dev, fe *comp, bool bnd, int nce) {
+EvalMap eval_map_whole(int log_b, int nce, bool bnd) {
     // (with bnd the kernel reads the boundary divisor planes at stride nce * n: all 8 cosets then)
     if (bnd) nce = 8;
-    return eval_constraints_mapped(st, lde, log_n, EvalMap{nce, 0, 1, log_b - 3, 1 << log_b}, periodic, divs, consts_dev, comp,
-                            bnd);
+    return EvalMap{nce, 0, 1, log_b - 3, 1 << log_b};
 }
 
-hipError_t eval_constraints_mapped(hipStream_t st, const fe *lde, int log_n, EvalMap map, const fe *periodic,
-                             const fe *divs, const AirConsts *consts_dev, fe *comp, bool bnd) {
+hipError_t eval_constraints(hipStream_t st, int KX, const fe *lde, int log_n, EvalMap map, const fe *periodic,
+                            const fe *divs, const AirConsts *consts, size_t plane, fe *comp, bool bnd) {
     // the __constant__ MDS tables of this device (normally uploaded by zk_prover_create already)
     if (const hipError_t e = upload_rescue_consts(st)) return e;
     const size_t CE = (size_t)map.nce << log_n;
-    const double bytes = (448.0 * (map.lshift == 0 ? 1 : 2) + (bnd ? 64.0 : 32.0)) * CE;
-    if (bnd)
-        ZK_PROF(st, "eval_constraints", bytes, hipLaunchKernelGGL((k_eval_constraints<1, true>), dim3(cdiv(CE, 256)), dim3(256), 0, st,
-                                                                  lde, log_n, map, periodic, divs, consts_dev, consts_dev, (size_t)0, comp));
-    else
-        ZK_PROF(st, "eval_constraints", bytes, hipLaunchKernelGGL((k_eval_constraints<1, false>), dim3(cdiv(CE, 256)), dim3(256), 0, st,
-                                                                  lde, log_n, map, periodic, divs, consts_dev, consts_dev, (size_t)0, comp));
+    const double bytes = (448.0 * (map.lshift == 0 ? 1 : 2) + (KX == 1 ? (bnd ? 64.0 : 32.0) : (bnd ? 80.0 : 48.0))) * CE;
+    if (KX == 1) plane = 0;
+#define ZK_EVAL(KE, BND, name)                                                                                        \
+    ZK_PROF(st, name, bytes, hipLaunchKernelGGL((k_eval_constraints<KE, BND>), dim3(cdiv(CE, 256)), dim3(256), 0, st, \
+                                                lde, log_n, map, periodic, divs, consts, consts + (KX == 2), plane, comp))
+    if (KX == 1 && bnd) ZK_EVAL(1, true, "eval_constraints");
+    else if (KX == 1) ZK_EVAL(1, false, "eval_constraints");
+    else if (bnd) ZK_EVAL(2, true, "eval_constraints_ext");
+    else ZK_EVAL(2, false, "eval_constraints_ext");
+#undef ZK_EVAL
     return hipGetLastError();
-}
-
-hipError_t eval_constraints_ext_mapped(hipStream_t st, const fe *lde, int log_n, EvalMap map, const fe *periodic,
-                                 const fe *divs, const AirConsts *consts2_dev, size_t plane, fe *comp, bool bnd) {
-    // the __constant__ MDS tables of this device (normally uploaded by zk_prover_create already)
-    if (const hipError_t e = upload_rescue_consts(st)) return e;
-    const size_t CE = (size_t)map.nce << log_n;
-    const double bytes = (448.0 * (map.lshift == 0 ? 1 : 2) + (bnd ? 80.0 : 48.0)) * CE;
-    if (bnd)
-        ZK_PROF(st, "eval_constraints_ext", bytes, hipLaunchKernelGGL((k_eval_constraints<2, true>), dim3(cdiv(CE, 256)), dim3(256), 0,
-                                                                      st, lde, log_n, map, periodic, divs, consts2_dev, consts2_dev + 1, plane, comp));
-    else
-        ZK_PROF(st, "eval_constraints_ext", bytes, hipLaunchKernelGGL((k_eval_constraints<2, false>), dim3(cdiv(CE, 256)), dim3(256), 0,
-                                                                      st, lde, log_n, map, periodic, divs, consts2_dev, consts2_dev + 1, plane, comp));
-    return hipGetLastError();
-}
-
-hipError_t eval_constraints_ext(hipStream_t st, const fe *lde, int log_n, int log_b, const fe *periodic, const fe *divs,
-                          const AirConsts *consts2_dev, fe *comp, bool bnd, int nce) {
-    if (bnd) nce = 8;
-    return eval_constraints_ext_mapped(st, lde, log_n, EvalMap{nce, 0, 1, log_b - 3, 1 << log_b}, periodic, divs, consts2_dev,
-                                (size_t)8 << log_n, comp, bnd);
 }
 
 // ================================================================ trace validation
@@ -2209,17 +2188,6 @@ __global__ void __launch_bounds__(256) k_comp_cross(CrossMap m, const fe *wi_lo,
         }
         if (nz) atomicOr(nonzero, 1u);
     }
-}
-
-void comp_cross_coset(hipStream_t st, const fe *c, int log_n, const NttTables &T8n, const PowTable &inv3, fe scale,
-                      fe w8inv, fe inv3n, int ncols, fe *polys, unsigned *nonzero_flag) {
-    const size_t n = (size_t)1 << log_n;
-    CrossMap m;
-    for (int r = 0; r < 8; r++) m.c[r] = c + (size_t)r * n;
-    m.k0 = 0;
-    m.kcount = n;
-    m.pstride = n;
-    comp_cross_mapped(st, m, T8n, inv3, scale, w8inv, inv3n, ncols, polys, nonzero_flag);
 }
 
 void comp_cross_mapped(hipStream_t st, const CrossMap &m, const NttTables &T8n, const PowTable &inv3, fe scale,

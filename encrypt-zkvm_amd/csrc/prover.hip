@@ -38,6 +38,7 @@ struct HostTimer {
     std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
     std::string log;
     void start() { t = std::chrono::steady_clock::now(); }
+    void lap(const char *what) { stop(what), start(); }
     void stop(const char *what) {
         if (!on) return;
         const double us = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t).count();
@@ -53,8 +54,6 @@ struct HostTimer {
 using namespace zk;
 
 const char *zk_last_error(void) { return g_err.c_str(); }
-
-
 
 struct zk_trace_lde {
     zk_prover *p;
@@ -781,13 +780,6 @@ void zk::plan_batch(size_t nl, const std::vector<uint64_t> &idx, BatchPlan &bp) 
     }
 }
 
-BatchPlan zk::plan_batch(size_t nl, const std::vector<uint64_t> &idx) {
-    BatchPlan bp;
-    plan_batch(nl, idx, bp);
-    return bp;
-}
-
-// ---------------------------------------------------------------- the prove path
 // ---------------------------------------------------------------- protocol steps (host side)
 // the two checks of a trace alone, shared with the validation entry points (same bounds, same messages)
 static int check_trace_len(size_t n, size_t max_n) {
@@ -1087,13 +1079,6 @@ std::vector<std::vector<uint64_t>> zk::fri_fold_positions(const std::vector<uint
     return out;
 }
 
-std::vector<uint8_t> zk::serialize_proof(size_t n, const zk_options *opt, int C, const zk_record &R, const fe *ood,
-                                         const Openings &O, const std::vector<fe> *rem_flat) {
-    std::vector<uint8_t> out;
-    serialize_proof(n, opt, C, R, ood, O, rem_flat, out);
-    return out;
-}
-
 void zk::serialize_proof(size_t n, const zk_options *opt, int C, const zk_record &R, const fe *ood, const Openings &O,
                          const std::vector<fe> *rem_flat, std::vector<uint8_t> &out) {
     const int nl = (int)R.num_fri_layers;
@@ -1354,10 +1339,7 @@ int zk::fri_lead_layers(zk_prover *p, const Plan *pl, int KX, uint32_t fold, uin
         if (!fe_eq(alpha.a, dalpha[2 * l]) || (KX == 2 && !fe_eq(alpha.b, dalpha[2 * l + 1])))
             ZK_FAIL(ZK_ERR_DEVICE, "device FRI transcript diverged from the host transcript");
     }
-    if (ht) {
-        ht->stop("fri_replay");
-        ht->start();
-    }
+    if (ht) ht->lap("fri_replay");
     return remainder_step(KX, rv, B, coin, R, degree_flag, Y.rem_flat);
 }
 
@@ -1411,105 +1393,122 @@ static int ood_deep_stage(zk_prover *p, Plan *pl, Coin &coin, zk_record &R, Host
     return check_ood_identity(e, C, Kp, KX, X::wide(z), (size_t)1 << log_n, pub);
 }
 
-static int prove_once(zk_prover *p, const TraceSrc &src, size_t n, const zk_options *opt, const zk_pub_inputs *pub,
-                      uint8_t *proof_out, size_t *proof_len, zk_record *rec, const zk_dump *dump) {
-    if (!p || !proof_len) ZK_FAIL(ZK_ERR_INVALID_ARG, "null argument");
-    ZK_REQUIRE_FULL_PROVER(p);
-    ZK_TRY(check_prove_args(n, p->max_n, p->max_b, opt, pub));
-    // copies from the caller's host columns may still be in flight on an early error return: the caller
-    // may free those columns as soon as this returns (a completed proof has long finished them).  Kernels of
-    // a failed proof may also still be queued on st: the next proof's uploads into d_trace (on the upload stream,
-    // ordered only by the previous proof having drained st) must not race them, so both drain here.
-    // proofs in flight on the device: alone, the trace goes up on the latency schedule (trace_commit.hip).  Declared
-    // before the copy guard, so this proof counts as in flight until its uploads and kernels have drained.
-    DeviceBusy busy{p->dev_busy};
-    struct CopyGuard {
-        zk_prover *p;
-        ~CopyGuard() {
-            upload_drain(p);
-            (void)hipStreamSynchronize(p->st);
-        }
-    } copy_guard{p};
-    // the AUTO rule (include/zkvm_gpu.h, zk_proof_info): the latency schedule iff no other proof is in flight here
-    const int sched = p->upload_sched;
-    p->lat_sched = sched == ZK_SCHED_LATENCY || (sched == ZK_SCHED_AUTO && busy.others == 0);
-    p->last_sched = src.cols ? (p->lat_sched ? ZK_SCHED_LATENCY : ZK_SCHED_THROUGHPUT) : 0;
-    const uint32_t B = opt->blowup, fold = opt->fri_folding;
-    const size_t N = n * B;
-    ZK_CHECK_HIP(hipSetDevice(p->device));
-    IoScope io_scope(p);
+// ---- the stages both provers run the same way (ProofRun, prover_internal.hpp)
+int ProofRun::fri_shape() {
+    nl = fri_num_layers(N, opt);
+    if (nl > ZK_MAX_FRI_LAYERS) ZK_FAIL(ZK_ERR_INVALID_ARG, "too many FRI layers");
+    R.num_fri_layers = (uint32_t)nl;
+    Y = FriLayers(nl);
+    Y.len[0] = N;
+    return ZK_OK;
+}
+
+int ProofRun::open_plans(zk_prover *lead, size_t rows0) {
+    ZK_TRY(grind_and_positions(lead, coin, opt, N, R, pos));
+    fri_pos = fri_fold_positions(pos, N, fold, nl);
+    if (ht) ht->lap("positions");
+    if (!lead->open) lead->open = new Openings();
+    O = lead->open;
+    O->reset(2 + nl);
+    plan_batch(N, pos, O->plans[0]);
+    O->plans[1] = O->plans[0];  // the composition tree opens the same positions
+    for (int l = 0; l < nl; l++) plan_batch(l == 0 ? rows0 : Y.len[l] / fold, fri_pos[l], O->plans[2 + l]);
+    return ZK_OK;
+}
+
+int ProofRun::finish(zk_prover *lead, uint8_t *proof_out, size_t *proof_len, zk_record *rec) {
+    if (ht) ht->start();
+    serialize_proof(n, opt, C, R, h.data(), *O, KX == 2 ? &Y.rem_flat : nullptr, lead->proof_bytes);
+    if (ht) ht->stop("serialize");
+    stage_mark(lead, "serialize");
+    ZK_CHECK_HIP(hipStreamSynchronize(lead->st));
+    stage_collect(lead);
+    collect_kernel_stats(lead);
+    if (rec) *rec = R;
+    return deliver_proof(lead->proof_bytes, degree_flag, proof_out, proof_len);
+}
+
+// One single-GPU proof: the per-proof state and the protocol's stages S0 .. S9 (the list at the top of this file) as
+// methods that prove_once calls in order.  A stage queues its GPU work before its host segment (HT) starts.
+struct SingleProof : ProofRun {
+    zk_prover *const p;
+    const TraceSrc &src;
+    const zk_dump *const dump;
+    const uint32_t B = opt->blowup;
     Plan *pl = nullptr;
-    ZK_TRY(get_plan(p, n, B, &pl));
-    const int log_n = pl->log_n, log_b = pl->log_b;
-    const int C = num_comp_cols(n);
-    if (C > 8) ZK_FAIL(ZK_ERR_INVALID_ARG, "composition column count exceeds 8");
-    zk_record R = record_init(n, N, C);
-    stage_begin(p);
-    stage_mark(p, "start");
-
-    // S0: coin seed [P1]
-    Coin coin = seed_coin(n, opt, pub);
-
-    // S2: trace LDE + commitment
-    ZK_TRY(trace_lde_commit(p, pl, src, n, R.trace_root));
-    ZK_TRY(d2h_flush(p));
-    stage_mark(p, "trace_commit");
+    int log_n = 0, log_b = 0;
+    Planes pb = {};
     HostTimer HT;
-    HT.start();
-    coin.reseed(R.trace_root);
-
-    // S3: constraint composition coefficients [P4] and evaluation over the CE domain.  With
-    // FieldExtension::Quadratic the coefficients are E values and the composition has two planes
-    // (a, b): the evaluator runs once per plane with that component of every coefficient.
-    const int KX = (int)opt->field_extension, CK = C * KX;
-    if (KX == 2) ZK_TRY(ensure_ext(p));
-    const Planes pb = planes(p, KX);
-    fe *comp = pb.comp, *ctmp = pb.ctmp, *clde = pb.clde, *deep = pb.deep;
-    // The assertion terms are not evaluated per row here: S4 adds them in coefficient form (unless the
-    // caller dumps the composition values, which must then include them).
+    // The assertion terms are not evaluated per row: S4 adds them in coefficient form (unless the caller dumps the
+    // composition values, which must then include them).
     const bool bnd_rows = dump && dump->composition;
-    // CE cosets evaluated: 7 when the composition has at most 7 columns (the stage derives the 8th)
+    // CE cosets evaluated: 7 when the composition has at most 7 columns (the composition stage derives the 8th)
     const int nce = (!bnd_rows && C <= 7) ? 7 : 8;
     AirConsts Kp[2];
-    draw_air_consts(coin, pub, n, KX, Kp, R);
-    ZK_TRY(h2d_small(p, pb.air_consts, Kp, KX * sizeof Kp[0]));
-    const fe *binv = boundary_inverses(p, pl);
-    if (!binv) ZK_FAIL(ZK_ERR_OUT_OF_MEMORY, "boundary divisor table");
-    ZK_CHECK_HIP((KX == 1 ? eval_constraints : eval_constraints_ext)(p->st, p->lde, log_n, log_b, pl->periodic, binv,
-                                                                     (const AirConsts *)pb.air_consts, comp, bnd_rows, nce));
-    HT.stop("air_consts");
-    stage_mark(p, "constraints");
-
-    // S4: composition polynomial (interpolate over the CE coset, segment into C columns) + commit.
-    ZK_TRY(composition_stage(p, pl, KX, C, comp, ctmp, clde, R.constraint_root, bnd_rows ? nullptr : Kp, nce, &p->csrc,
-                             p->csrc_w));
-    unsigned degree_flag = 0;
-    ZK_TRY(d2h_small(p, &degree_flag, p->flag, 4));
-    ZK_TRY(d2h_flush(p));
-    stage_mark(p, "composition");
-    HT.start();
-    coin.reseed(R.constraint_root);
-
     // FRI layer 0 is the DEEP LDE, coset-major as the coset NTT wrote it (FriLayout lb0 = log_b), unless it is
     // already the remainder (no fold layers), which the host reads in natural order
-    const int nl = fri_num_layers(N, opt);
-    const int lb0 = nl > 0 ? log_b : 0;
-    // S5: OOD frame [P7], DEEP coefficients [P8] and evaluations.  h holds the frame flattened
-    // (k base elements per E value): [T(z)]_W ++ [T(zg)]_W ++ [H(z)]_C.
-    std::vector<fe> h;
-    // the stage dumps up to the composition commitment (E-valued stages dump their a component, as the oracle does)
-    auto dump_front = [&]() -> int {
-        if (dump->trace_polys) ZK_CHECK_HIP(hipMemcpy(dump->trace_polys, p->polys, (size_t)W * n * 16, hipMemcpyDeviceToHost));
-        if (dump->trace_lde) coset_major_rows_to_host(p, p->lde, W, n, B, dump->trace_lde);
-        if (dump->trace_leaves) ZK_CHECK_HIP(hipMemcpy(dump->trace_leaves, p->leaves, 32 * N, hipMemcpyDeviceToHost));
-        if (dump->composition) coset_major_rows_to_host(p, comp, 1, n, 8, dump->composition);
-        if (dump->comp_polys) ZK_CHECK_HIP(hipMemcpy(dump->comp_polys, p->cpolys, (size_t)CK * n * 16, hipMemcpyDeviceToHost));
-        if (dump->comp_lde) coset_major_rows_to_host(p, clde, CK, n, B, dump->comp_lde);
+    int lb0 = 0;
+    size_t na = 0;  // chunks the proof opens (open_addresses)
+    SingleProof(zk_prover *p_, const TraceSrc &src_, size_t n_, const zk_options *opt_, const zk_pub_inputs *pub_,
+                const zk_dump *dump_)
+        : ProofRun(opt_, pub_, n_, num_comp_cols(n_)), p(p_), src(src_), dump(dump_) {
+        ht = &HT;
+    }
+    int start(int others) {
+        // the AUTO rule (include/zkvm_gpu.h, zk_proof_info): the latency schedule iff no other proof is in flight on the
+        // device (others = 0)
+        const int sched = p->upload_sched;
+        p->lat_sched = sched == ZK_SCHED_LATENCY || (sched == ZK_SCHED_AUTO && others == 0);
+        p->last_sched = src.cols ? (p->lat_sched ? ZK_SCHED_LATENCY : ZK_SCHED_THROUGHPUT) : 0;
+        ZK_TRY(get_plan(p, n, B, &pl));
+        log_n = pl->log_n, log_b = pl->log_b;
+        if (C > 8) ZK_FAIL(ZK_ERR_INVALID_ARG, "composition column count exceeds 8");
+        if (KX == 2) ZK_TRY(ensure_ext(p));
+        pb = planes(p, KX);
+        lb0 = fri_num_layers(N, opt) > 0 ? log_b : 0;
+        stage_begin(p);
+        stage_mark(p, "start");
+        coin = seed_coin(n, opt, pub);  // S0 [P1]
         return ZK_OK;
-    };
-    {
+    }
+    // S2: trace LDE + commitment
+    int commit_trace() {
+        ZK_TRY(trace_lde_commit(p, pl, src, n, R.trace_root));
+        ZK_TRY(d2h_flush(p));
+        stage_mark(p, "trace_commit");
+        HT.start();
+        coin.reseed(R.trace_root);
+        return ZK_OK;
+    }
+    // S3: constraint composition coefficients [P4] and evaluation over the CE domain.  With FieldExtension::Quadratic
+    // the coefficients are E values and the composition has two planes (a, b): the evaluator folds every constraint
+    // value into both, each with that component of every coefficient.
+    int constraints() {
+        draw_air_consts(coin, pub, n, KX, Kp, R);
+        ZK_TRY(h2d_small(p, pb.air_consts, Kp, KX * sizeof Kp[0]));
+        const fe *binv = boundary_inverses(p, pl);
+        if (!binv) ZK_FAIL(ZK_ERR_OUT_OF_MEMORY, "boundary divisor table");
+        ZK_CHECK_HIP(eval_constraints(p->st, KX, p->lde, log_n, eval_map_whole(log_b, nce, bnd_rows), pl->periodic, binv,
+                                      (const AirConsts *)pb.air_consts, (size_t)8 << log_n, pb.comp, bnd_rows));
+        HT.stop("air_consts");
+        stage_mark(p, "constraints");
+        return ZK_OK;
+    }
+    // S4: composition polynomial (interpolate over the CE coset, segment into C columns) + commit
+    int composition() {
+        ZK_TRY(composition_stage(p, pl, KX, C, pb.comp, pb.ctmp, pb.clde, R.constraint_root, bnd_rows ? nullptr : Kp, nce,
+                                 &p->csrc, p->csrc_w));
+        ZK_TRY(d2h_small(p, &degree_flag, p->flag, 4));
+        ZK_TRY(d2h_flush(p));
+        stage_mark(p, "composition");
+        HT.start();
+        coin.reseed(R.constraint_root);
+        return ZK_OK;
+    }
+    // S5: OOD frame [P7], DEEP coefficients [P8] and evaluations (ood_deep_stage)
+    int ood_deep() {
         const int rc = with_kx(KX, [&](auto kx) {
-            return ood_deep_stage<decltype(kx)::value>(p, pl, coin, R, HT, C, Kp, pub, lb0 ? nullptr : deep, h);
+            return ood_deep_stage<decltype(kx)::value>(p, pl, coin, R, HT, C, Kp, pub, lb0 ? nullptr : pb.deep, h);
         });
         // a trace the AIR rejects ends here (the out-of-domain identity): the stages that ran are still dumped, as the
         // oracle dumps them, so the evaluator can be compared on traces no program produces
@@ -1517,116 +1516,155 @@ static int prove_once(zk_prover *p, const TraceSrc &src, size_t n, const zk_opti
             ZK_CHECK_HIP(hipStreamSynchronize(p->st));
             ZK_TRY(dump_front());
         }
-        if (rc != ZK_OK) return rc;
+        if (rc == ZK_OK) stage_mark(p, "deep");
+        return rc;
     }
-    stage_mark(p, "deep");
-
-    // S6: FRI [P9, P10]; E layers are planar (k planes of L values)
-    if (nl > ZK_MAX_FRI_LAYERS) ZK_FAIL(ZK_ERR_INVALID_ARG, "too many FRI layers");
-    R.num_fri_layers = (uint32_t)nl;
-    {
+    // S6: FRI [P9, P10]; E layers are planar (KX planes of L values)
+    int fri() {
+        ZK_TRY(fri_shape());
         size_t tot = 0, s = N;
         for (int l = 0; l < nl; l++) tot += (s /= fold);
         if (tot > p->max_n * p->max_b) ZK_FAIL(ZK_ERR_INVALID_ARG, "FRI layers exceed the prover's buffers");
+        Y.vals[0] = lb0 ? pb.ulde : pb.deep;
+        ZK_TRY(fri_lead_layers(p, pl, KX, fold, B, N, 0, lb0, pb.fri, p->fri_dig, Y, coin, R, degree_flag, &HT));
+        stage_mark(p, "fri");
+        HT.lap("remainder");
+        return ZK_OK;
     }
-    FriLayers Y(nl);
-    const fe *deep0 = lb0 ? pb.ulde : deep;
-    Y.vals[0] = deep0;
-    Y.len[0] = N;
-    ZK_TRY(fri_lead_layers(p, pl, KX, fold, B, N, 0, lb0, pb.fri, p->fri_dig, Y, coin, R, degree_flag, &HT));
-    stage_mark(p, "fri");
-
-    HT.stop("remainder");
-    HT.start();
-    // S7: grinding and query positions [P10, P11]
-    std::vector<uint64_t> pos;
-    ZK_TRY(grind_and_positions(p, coin, opt, N, R, pos));
-    const size_t nu = pos.size();
-    const auto fri_pos = fri_fold_positions(pos, N, fold, nl);
-    HT.stop("positions");
-    HT.start();
-
-    // S8: openings.  Every value and digest the proof opens, as a list of 16-byte device chunks: one
-    // address upload, one gather kernel, one download.
-    // The Openings and the address list live in the prover (pinned / capacity kept across proofs):
-    // fresh host allocations here cost page faults on every proof (~100 us at 2^20).
-    if (!p->open) p->open = new Openings();
-    Openings &O = *p->open;
-    O.reset(2 + nl);
-    plan_batch(N, pos, O.plans[0]);
-    O.plans[1] = O.plans[0];  // the composition tree opens the same positions
-    for (int l = 0; l < nl; l++) plan_batch(Y.len[l] / fold, fri_pos[l], O.plans[2 + l]);
-    uint64_t *addr = p->h_gather_idx;
-    size_t na = 0;
-    auto fe_at = [&](const fe *base, size_t idx) { addr[na++] = (uint64_t)(uintptr_t)(base + idx); };
-    auto row_at = [&](const fe *base, int ncols, uint64_t i) {  // coset-major LDE row i
-        for (int c = 0; c < ncols; c++) {
-            if (base == p->lde && ((p->tc.virt >> c) & 1u)) fe_at(p->tc.virt_lagr, (i & (B - 1)) * n + (i >> log_b));
-            else fe_at(base, ((size_t)c * B + (i & (B - 1))) * n + (i >> log_b));
-        }
-    };
-    size_t need = nu * (W + CK);
-    for (int l = 0; l < nl; l++) need += fri_pos[l].size() * fold * KX;
-    for (int b = 0; b < 2 + nl; b++) need += 2 * O.plans[b].count();
-    if (need > ZK_GATHER_CAP) ZK_FAIL(ZK_ERR_INVALID_ARG, "too many opened values for the gather buffer");
-    for (size_t q = 0; q < nu; q++) row_at(p->lde, W, pos[q]);
-    for (size_t q = 0; q < nu; q++) row_at(clde, CK, pos[q]);
-    for (int l = 0; l < nl; l++) {
-        const size_t rows = Y.len[l] / fold;
-        for (uint64_t r : fri_pos[l])
-            for (uint32_t k = 0; k < fold; k++)
-                for (int j = 0; j < KX; j++) {
-                    const uint64_t i = r + k * rows;  // natural index in layer l
-                    fe_at(Y.vals[l], j * Y.len[l] + ((l || !lb0) ? i : ((i & (B - 1)) << log_n) + (i >> log_b)));
-                }
+    // S7, S8: positions, then every value and digest the proof opens as a list of 16-byte device chunks: one address
+    // upload, one gather kernel, one download
+    int openings() {
+        ZK_TRY(open_plans(p, N / fold));
+        ZK_TRY(open_addresses());
+        HT.stop("plans_addresses");
+        ZK_TRY(gather());
+        scale_virtual();
+        stage_mark(p, "queries");
+        return ZK_OK;
     }
-    const size_t off_dig = na;
-    for (int b = 0; b < 2 + nl; b++) {
-        const uint8_t *lv = b == 0 ? p->leaves : b == 1 ? p->cleaves : Y.leaves[b - 2];
-        const uint8_t *nd = b == 0 ? p->nodes : b == 1 ? p->cnodes : Y.nodes[b - 2];
-        for (auto &path : O.plans[b].paths)
-            for (auto &e : path) {
-                const uint8_t *d = (e.first ? nd : lv) + 32 * e.second;
-                addr[na++] = (uint64_t)(uintptr_t)d;
-                addr[na++] = (uint64_t)(uintptr_t)(d + 16);
+    // the chunks' addresses into the prover's pinned list (na of them): the trace rows, the composition rows, every
+    // layer's fold rows, then from off_dig every plan's digests.  A virtual column's chunk is e_(n-1)'s LDE instead.
+    int open_addresses() {
+        uint64_t *addr = p->h_gather_idx;
+        na = 0;
+        auto fe_at = [&](const fe *base, size_t idx) { addr[na++] = (uint64_t)(uintptr_t)(base + idx); };
+        auto row_at = [&](const fe *base, int ncols, uint64_t i) {  // coset-major LDE row i
+            for (int c = 0; c < ncols; c++) {
+                if (base == p->lde && ((p->tc.virt >> c) & 1u)) fe_at(p->tc.virt_lagr, (i & (B - 1)) * n + (i >> log_b));
+                else fe_at(base, ((size_t)c * B + (i & (B - 1))) * n + (i >> log_b));
             }
+        };
+        size_t need = pos.size() * (W + CK);
+        for (int l = 0; l < nl; l++) need += fri_pos[l].size() * fold * KX;
+        for (int b = 0; b < 2 + nl; b++) need += 2 * O->plans[b].count();
+        if (need > ZK_GATHER_CAP) ZK_FAIL(ZK_ERR_INVALID_ARG, "too many opened values for the gather buffer");
+        for (uint64_t q : pos) row_at(p->lde, W, q);
+        for (uint64_t q : pos) row_at(pb.clde, CK, q);
+        for (int l = 0; l < nl; l++) {
+            const size_t rows = Y.len[l] / fold;
+            for (uint64_t r : fri_pos[l])
+                for (uint32_t k = 0; k < fold; k++)
+                    for (int j = 0; j < KX; j++) {
+                        const uint64_t i = r + k * rows;  // natural index in layer l
+                        fe_at(Y.vals[l], j * Y.len[l] + ((l || !lb0) ? i : ((i & (B - 1)) << log_n) + (i >> log_b)));
+                    }
+        }
+        off_dig = na;
+        for (int b = 0; b < 2 + nl; b++) {
+            const uint8_t *lv = b == 0 ? p->leaves : b == 1 ? p->cleaves : Y.leaves[b - 2];
+            const uint8_t *nd = b == 0 ? p->nodes : b == 1 ? p->cnodes : Y.nodes[b - 2];
+            for (auto &path : O->plans[b].paths)
+                for (auto &e : path) {
+                    const uint8_t *d = (e.first ? nd : lv) + 32 * e.second;
+                    addr[na++] = (uint64_t)(uintptr_t)d;
+                    addr[na++] = (uint64_t)(uintptr_t)(d + 16);
+                }
+        }
+        return ZK_OK;
     }
-    HT.stop("plans_addresses");
-    ZK_CHECK_HIP(hipMemcpyAsync(p->gather_idx, p->h_gather_idx, na * 8, hipMemcpyHostToDevice, p->st));
-    gather_chunks(p->st, p->gather_idx, na, p->gather_out);
-    ZK_CHECK_HIP(hipMemcpyAsync(p->h_gather_out, p->gather_out, na * sizeof(fe), hipMemcpyDeviceToHost, p->st));
-    ZK_CHECK_HIP(hipStreamSynchronize(p->st));
-    O.unpack(p->h_gather_out, nu, CK, fri_pos, fold, KX, off_dig);
-    if (p->tc.virt)  // virtual columns: the gather read e_(n-1)'s LDE there; times the column's last row
-        for (size_t q = 0; q < nu; q++)
+    int gather() {
+        ZK_CHECK_HIP(hipMemcpyAsync(p->gather_idx, p->h_gather_idx, na * 8, hipMemcpyHostToDevice, p->st));
+        gather_chunks(p->st, p->gather_idx, na, p->gather_out);
+        ZK_CHECK_HIP(hipMemcpyAsync(p->h_gather_out, p->gather_out, na * sizeof(fe), hipMemcpyDeviceToHost, p->st));
+        ZK_CHECK_HIP(hipStreamSynchronize(p->st));
+        O->unpack(p->h_gather_out, pos.size(), CK, fri_pos, fold, KX, off_dig);
+        return ZK_OK;
+    }
+    void scale_virtual() {  // virtual columns: the gather read e_(n-1)'s LDE there; times the column's last row
+        if (!p->tc.virt) return;
+        for (size_t q = 0; q < pos.size(); q++)
             for (int c = 0; c < W; c++)
-                if ((p->tc.virt >> c) & 1u) O.trace_rows[q * W + c] = fe_mul(O.trace_rows[q * W + c], p->tc.virt_last[c]);
-    stage_mark(p, "queries");
+                if ((p->tc.virt >> c) & 1u) O->trace_rows[q * W + c] = fe_mul(O->trace_rows[q * W + c], p->tc.virt_last[c]);
+    }
 
-    // S9: proof bytes [P13, P14]
-    HT.start();
-    std::vector<uint8_t> &bytes = p->proof_bytes;
-    serialize_proof(n, opt, C, R, h.data(), O, KX == 2 ? &Y.rem_flat : nullptr, bytes);
-    HT.stop("serialize");
-    stage_mark(p, "serialize");
-    ZK_CHECK_HIP(hipStreamSynchronize(p->st));
-    stage_collect(p);
-    collect_kernel_stats(p);
-
-    if (rec) *rec = R;
-    if (dump) {
-        ZK_TRY(dump_front());
+    // the stage dumps up to the composition commitment (E-valued stages dump their a component, as the oracle does)
+    int dump_front() {
+        if (dump->trace_polys) ZK_CHECK_HIP(hipMemcpy(dump->trace_polys, p->polys, (size_t)W * n * 16, hipMemcpyDeviceToHost));
+        if (dump->trace_lde) coset_major_rows_to_host(p, p->lde, W, n, B, dump->trace_lde);
+        if (dump->trace_leaves) ZK_CHECK_HIP(hipMemcpy(dump->trace_leaves, p->leaves, 32 * N, hipMemcpyDeviceToHost));
+        if (dump->composition) coset_major_rows_to_host(p, pb.comp, 1, n, 8, dump->composition);
+        if (dump->comp_polys) ZK_CHECK_HIP(hipMemcpy(dump->comp_polys, p->cpolys, (size_t)CK * n * 16, hipMemcpyDeviceToHost));
+        if (dump->comp_lde) coset_major_rows_to_host(p, pb.clde, CK, n, B, dump->comp_lde);
+        return ZK_OK;
+    }
+    // ... and after it: DEEP in natural order, FRI layer 1
+    int dump_back() {
         if (dump->deep) {
-            if (lb0) coset_major_to_natural(p->st, deep0, log_n, log_b, deep);
+            if (lb0) coset_major_to_natural(p->st, Y.vals[0], log_n, log_b, pb.deep);
             ZK_CHECK_HIP(hipStreamSynchronize(p->st));
-            ZK_CHECK_HIP(hipMemcpy(dump->deep, deep, N * 16, hipMemcpyDeviceToHost));
+            ZK_CHECK_HIP(hipMemcpy(dump->deep, pb.deep, N * 16, hipMemcpyDeviceToHost));
         }
         if (dump->fri_layer1 && nl > 0)
             ZK_CHECK_HIP(hipMemcpy(dump->fri_layer1, Y.vals[1], Y.len[1] * 16, hipMemcpyDeviceToHost));
+        return ZK_OK;
     }
-    p->last_n = n;
-    p->last_b = B;
-    return deliver_proof(bytes, degree_flag, proof_out, proof_len);
+    // S9: proof bytes, then the dumps of a completed proof (the stream is idle)
+    int finish(uint8_t *proof_out, size_t *proof_len, zk_record *rec) {
+        const int rc = ProofRun::finish(p, proof_out, proof_len, rec);
+        if (!p->stage_done) return rc;  // (the stream did not drain)
+        if (dump) {
+            ZK_TRY(dump_front());
+            ZK_TRY(dump_back());
+        }
+        p->last_n = n;
+        p->last_b = B;
+        return rc;
+    }
+};
+
+// Copies from the caller's host columns may still be in flight on an early error return: the caller may free those
+// columns as soon as the proof returns (a completed proof has long finished them).  Kernels of a failed proof may also
+// still be queued on st: the next proof's uploads into d_trace (on the upload stream, ordered only by the previous proof
+// having drained st) must not race them, so both drain on every way out.
+struct CopyGuard {
+    zk_prover *p;
+    ~CopyGuard() {
+        upload_drain(p);
+        (void)hipStreamSynchronize(p->st);
+    }
+};
+
+static int prove_once(zk_prover *p, const TraceSrc &src, size_t n, const zk_options *opt, const zk_pub_inputs *pub,
+                      uint8_t *proof_out, size_t *proof_len, zk_record *rec, const zk_dump *dump) {
+    if (!p || !proof_len) ZK_FAIL(ZK_ERR_INVALID_ARG, "null argument");
+    ZK_REQUIRE_FULL_PROVER(p);
+    ZK_TRY(check_prove_args(n, p->max_n, p->max_b, opt, pub));
+    // proofs in flight on the device: alone, the trace goes up on the latency schedule (trace_commit.hip).  Declared
+    // before the copy guard, so this proof counts as in flight until its uploads and kernels have drained; a stage
+    // that ends the proof early returns through all three guards.
+    DeviceBusy busy{p->dev_busy};
+    CopyGuard copy_guard{p};
+    ZK_CHECK_HIP(hipSetDevice(p->device));
+    IoScope io_scope(p);
+    SingleProof S(p, src, n, opt, pub, dump);
+    ZK_TRY(S.start(busy.others));
+    ZK_TRY(S.commit_trace());
+    ZK_TRY(S.constraints());
+    ZK_TRY(S.composition());
+    ZK_TRY(S.ood_deep());
+    ZK_TRY(S.fri());
+    ZK_TRY(S.openings());
+    return S.finish(proof_out, proof_len, rec);
 }
 
 // ---------------------------------------------------------------- trace validation
@@ -1967,7 +2005,8 @@ static int query_committed_rows(zk_prover *p, const fe *base, int ncols, size_t 
     gather_rows(p->st, base, ncols, ilog2(n), ilog2(B), p->gather_idx, k, p->gather_out);
     ZK_CHECK_HIP(hipMemcpyAsync(rows_out, p->gather_out, k * ncols * 16, hipMemcpyDeviceToHost, p->st));
     ZK_CHECK_HIP(hipStreamSynchronize(p->st));
-    BatchPlan bp = plan_batch(N, pos);
+    BatchPlan bp;
+    plan_batch(N, pos, bp);
     Bytes out;
     out.u8((uint8_t)bp.paths.size());
     for (auto &path : bp.paths) {
@@ -2013,8 +2052,8 @@ int zk_eval_constraints(zk_trace_lde *h, const zk_pub_inputs *pub, const uint8_t
     ZK_CHECK_HIP(hipMemcpyAsync(p->air_consts, &K, sizeof K, hipMemcpyHostToDevice, p->st));
     const fe *binv = boundary_inverses(p, pl);
     if (!binv) ZK_FAIL(ZK_ERR_OUT_OF_MEMORY, "boundary divisor table");
-    ZK_CHECK_HIP(eval_constraints(p->st, p->lde, pl->log_n, pl->log_b, pl->periodic, binv, (const AirConsts *)p->air_consts,
-                                  p->comp));
+    ZK_CHECK_HIP(eval_constraints(p->st, 1, p->lde, pl->log_n, eval_map_whole(pl->log_b, 8, true), pl->periodic, binv,
+                                  (const AirConsts *)p->air_consts, 0, p->comp, true));
     ZK_CHECK_HIP(hipStreamSynchronize(p->st));
     coset_major_rows_to_host(p, p->comp, 1, n, 8, out);
     return ZK_OK;

@@ -366,8 +366,8 @@ struct zk_prover {
 namespace zk {
 
 // One proof in flight on a device (zk_prover::dev_busy, process-wide per device) for the lifetime of the object;
-// `others` = the proofs already in flight when it started.  The single-GPU AUTO upload schedule reads it (prove_once);
-// sharded proofs count themselves on each local prover's device.
+// `others` = the proofs already in flight when it started.  The single-GPU AUTO upload schedule reads it
+// (SingleProof::start); sharded proofs count themselves on each local prover's device.
 struct DeviceBusy {
     std::atomic<int> *b;
     int others;
@@ -608,7 +608,6 @@ struct BatchPlan {
         return k;
     }
 };
-BatchPlan plan_batch(size_t nl, const std::vector<uint64_t> &idx);
 void plan_batch(size_t nl, const std::vector<uint64_t> &idx, BatchPlan &out);  // reuses out's storage
 
 // ---------------------------------------------------------------- protocol steps (host side)
@@ -705,11 +704,44 @@ int fri_lead_layers(zk_prover *p, const Plan *pl, int KX, uint32_t fold, uint32_
 // S9: Proof::to_bytes [P13, P14].  E values are k = opt->field_extension base elements each:
 // ood_flat = [T(z)]_W ++ [T(zg)]_W ++ [H(z)]_C flattened, comp_rows nu x C*k, fri_rows |pos| x fold*k;
 // the remainder is R.remainder (k = 1) or rem_flat (rem_len x k).
-std::vector<uint8_t> serialize_proof(size_t n, const zk_options *opt, int C, const zk_record &R, const fe *ood_flat,
-                                     const Openings &O, const std::vector<fe> *rem_flat = nullptr);
 void serialize_proof(size_t n, const zk_options *opt, int C, const zk_record &R, const fe *ood_flat, const Openings &O,
                      const std::vector<fe> *rem_flat, std::vector<uint8_t> &out);  // into out (storage reused)
 // copy the proof out (proof_len in/out) and fold the degree flag into the status
 int deliver_proof(const std::vector<uint8_t> &bytes, unsigned degree_flag, uint8_t *proof_out, size_t *proof_len);
+
+// What both provers keep per proof (SingleProof in prover.hip, ShardedProof in shard.hip derive from it), and the
+// stages that do not depend on where the data lives, written once (prover.hip).  `lead`: the prover whose stream, pinned
+// openings and proof storage the stage uses (the single GPU; local rank 0 of a sharded proof).
+struct ProofRun {
+    const zk_options *const opt;
+    const zk_pub_inputs *const pub;
+    const size_t n, N;
+    // FieldExtension: KX = 1 (None) or 2 (Quadratic, every E-valued buffer planar); C composition columns over E
+    const int KX, C, CK;
+    const uint32_t fold;
+    zk_record R;
+    Coin coin;
+    std::vector<fe> h;  // the OOD frame, flattened (KX base elements per E value)
+    unsigned degree_flag = 0;
+    int nl = 0;  // FRI layers (fri_shape)
+    FriLayers Y{0};
+    // (the openings and their plans live in the lead prover, storage kept across proofs: fresh host allocations here
+    // cost page faults on every proof, ~100 us at 2^20)
+    Openings *O = nullptr;
+    std::vector<uint64_t> pos;
+    std::vector<std::vector<uint64_t>> fri_pos;
+    size_t off_dig = 0;       // where the digests start in the gathered chunks (Openings::unpack)
+    HostTimer *ht = nullptr;  // ZK_HOST_TIMING: the single-GPU proof's segments
+    ProofRun(const zk_options *opt_, const zk_pub_inputs *pub_, size_t n_, int C_)
+        : opt(opt_), pub(pub_), n(n_), N(n_ * opt_->blowup), KX((int)opt_->field_extension), C(C_), CK(C_ * KX),
+          fold(opt_->fri_folding), R(record_init(n, N, C)) {}
+    // S6: the number of layers, recorded, and the layers' table with layer 0 the N DEEP evaluations
+    int fri_shape();
+    // S7 and the plans of S8: grinding and the query positions [P10, P11], folded down the layers, and a batch plan per
+    // tree.  rows0: the leaves of FRI layer 0's tree (N / fold)
+    int open_plans(zk_prover *lead, size_t rows0);
+    // S9: the proof bytes [P13, P14] into lead->proof_bytes, the stage times closed, the record and the proof delivered
+    int finish(zk_prover *lead, uint8_t *proof_out, size_t *proof_len, zk_record *rec);
+};
 
 }  // namespace zk

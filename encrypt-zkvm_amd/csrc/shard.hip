@@ -527,16 +527,12 @@ int dist_commit(Ctx &X, DistTree &T, size_t M, HashFn hash, const char *digests_
 //                sharded layer 1, or the staging of a gathered layer 1 / remainder layer
 //   CTMP         S6: layer 1 over this rank's cosets, which the openings read
 //   sh_buf       the receive area of every small all-gather (flags, totals, OOD parts) and of the openings
-struct ShardedProof {
+struct ShardedProof : ProofRun {  // (ProofRun: the state and stages shared with the single-GPU proof; N = 8 n)
     Ctx &X;
     const uint8_t *const trace;  // the caller's host trace, or null: the trace is in every rank's HBM
-    const zk_options *const opt;
-    const zk_pub_inputs *const pub;
-    const int G = X.G, Bl = X.Bl, log_n = X.log_n, C = X.C, nlp = (int)X.P.size();
-    // FieldExtension: KX = 1 (None) or 2 (Quadratic, every E-valued buffer planar: plane stride Bl*n per rank)
-    const int KX = (int)opt->field_extension, CK = C * KX;
-    const size_t n = X.n, N = 8 * n, col = n * sizeof(fe), kg = n / G;  // kg: a rank's coefficient range
-    const uint32_t fold = opt->fri_folding;
+    // (FieldExtension::Quadratic: every E-valued buffer planar, plane stride Bl*n per rank)
+    const int G = X.G, Bl = X.Bl, log_n = X.log_n, nlp = (int)X.P.size();
+    const size_t col = n * sizeof(fe), kg = n / G;  // kg: a rank's coefficient range
     const size_t m = n / fold, m1 = m / fold, rows0 = N / fold;  // layer-0 / -1 positions per coset, layer-0 leaves
     const int log_m = ilog2(m);
     const fe g = h_root_of_unity(log_n), inv_n = h_inv(fe_make(n));
@@ -549,10 +545,6 @@ struct ShardedProof {
     std::vector<std::atomic<uint32_t>> bad = std::vector<std::atomic<uint32_t>>(nlp);  // (value-initialised: zero)
     std::vector<std::atomic<uint32_t>> pack_bad = std::vector<std::atomic<uint32_t>>(nlp);
 
-    zk_record R = record_init(n, N, C);
-    Coin coin;
-    std::vector<fe> h;  // the OOD frame, flattened (k base elements per E value)
-    unsigned degree_flag = 0;
     Bufs xb{X};  // the send / receive pointers of the exchange being issued
     // column classes
     int U[W], nU = 0;   // the columns interpolated, ascending
@@ -575,9 +567,8 @@ struct ShardedProof {
     std::vector<const fe *> Dk = std::vector<const fe *>(nlp);  // each rank's DEEP coefficients
     // FRI: layer 1 committed and folded on every rank (sh1) and then layer lg = 2 all-gathered, else layer lg = 1; the
     // gathered layer's storage: natural (lbg 0) or coset-major over 8 cosets (3; FriLayout)
-    int nl = 0, lg = 1, lbg = 0;
+    int lg = 1, lbg = 0;
     bool sh1 = false;
-    FriLayers Y{0};
     // openings: chunk requests -- owner rank (-1: host top node), local buffer id, byte offset
     enum { B_LDE, B_CLDE, B_DEEP, B_TN, B_CN, B_F0N, B_FRI, B_FRI_DIG, B_TB, B_CB, B_F0B, B_CT, B_F1N, B_F1B };
     struct Req {
@@ -585,15 +576,12 @@ struct ShardedProof {
         size_t off;
         const uint8_t *host;
     };
-    // (the openings, their plans and the request list keep their storage across proofs: this host work sits on every
-    // rank's critical path, in the lead rank's segment, where fresh allocations cost page faults)
+    // (the request list, like the openings and their plans, keeps its storage across proofs: this host work sits on
+    // every rank's critical path, in the lead rank's segment, where fresh allocations cost page faults)
     inline static thread_local std::vector<Req> req;
-    Openings *O = nullptr;
-    std::vector<uint64_t> pos;
-    std::vector<std::vector<uint64_t>> fri_pos;
-    size_t off_dig = 0;
     ShardedProof(Ctx &X_, const uint8_t *trace_, const zk_options *opt_, const zk_pub_inputs *pub_)
-        : X(X_), trace(trace_), opt(opt_), pub(pub_) {}
+        : ProofRun(opt_, pub_, X_.n, X_.C), X(X_), trace(trace_) {}
+    using ProofRun::finish;  // (S9, beside a trace round's finish(k))
     // Every way out: first the host tasks are waited for (they read the caller's trace and write bad / pack_bad); then,
     // only when a host trace was given, the upload, compute and exchange streams are drained: on an early error return
     // copies from the trace may still be in flight, and the caller may free it as soon as prove_sharded returns.  The
@@ -1020,14 +1008,9 @@ struct ShardedProof {
             ZK_TRY(each_rank(X, [this, j](int l, zk_prover *p, Plan *pl) -> int {
                 const EvalMap em{1, X.rank[l] * Bl + j, 1, 0, Bl, (size_t)Bl * n};
                 const Planes b = pb(p);
-                if (KX == 1)
-                    ZK_CHECK_HIP(eval_constraints_mapped(p->st, p->lde + (size_t)j * n, log_n, em, pl->periodic,
-                                                         pl->sh_divs + (size_t)j * n, (const AirConsts *)p->air_consts,
-                                                         p->comp + (size_t)j * n, !range_split));
-                else
-                    ZK_CHECK_HIP(eval_constraints_ext_mapped(p->st, p->lde + (size_t)j * n, log_n, em, pl->periodic,
-                                                             pl->sh_divs + (size_t)j * n, (const AirConsts *)p->x_air,
-                                                             (size_t)Bl * n, p->x_comp + (size_t)j * n, !range_split));
+                ZK_CHECK_HIP(eval_constraints(p->st, KX, p->lde + (size_t)j * n, log_n, em, pl->periodic,
+                                              pl->sh_divs + (size_t)j * n, (const AirConsts *)b.air_consts, (size_t)Bl * n,
+                                              b.comp + (size_t)j * n, !range_split));
                 fe *scr = p->tmp, *send = scr + (size_t)KX * n * (1 + j);
                 ntt(p->st, pl->Tn, b.comp + (size_t)j * n, (size_t)Bl * n, b.ctmp + (size_t)j * n, (size_t)Bl * n, KX, true,
                     nullptr, nullptr, scr);
@@ -1340,11 +1323,7 @@ struct ShardedProof {
                                degree_flag);
     }
     int fri() {
-        nl = fri_num_layers(N, opt);
-        if (nl > ZK_MAX_FRI_LAYERS) ZK_FAIL(ZK_ERR_INVALID_ARG, "too many FRI layers");
-        R.num_fri_layers = (uint32_t)nl;
-        Y = FriLayers(nl);
-        Y.len[0] = N;
+        ZK_TRY(fri_shape());
         ZK_TRY(nl == 0 ? fri_none() : fri_sharded());
         if (nl > 0) ZK_TRY(fri_lead());
         stage_mark(P0, "fri");
@@ -1352,17 +1331,6 @@ struct ShardedProof {
     }
 
     // ---- S7 / S8: positions, then every rank gathers the chunks it owns; all-gather; the host combines
-    int open_plans() {
-        ZK_TRY(grind_and_positions(P0, coin, opt, N, R, pos));
-        fri_pos = fri_fold_positions(pos, N, fold, nl);
-        if (!P0->open) P0->open = new Openings();
-        O = P0->open;
-        O->reset(2 + nl);
-        plan_batch(N, pos, O->plans[0]);
-        O->plans[1] = O->plans[0];  // the composition tree opens the same positions
-        for (int l = 0; l < nl; l++) plan_batch(l == 0 ? rows0 : Y.len[l] / fold, fri_pos[l], O->plans[2 + l]);
-        return ZK_OK;
-    }
     void request_row(int buf, int ncols, uint64_t i) {  // row i of the trace or composition LDE
         const int r = (int)(i & 7), own = r / Bl, j = r % Bl;
         const size_t q = i >> 3;
@@ -1447,7 +1415,7 @@ struct ShardedProof {
         return xchg(X, "openings", AG, xb, NK * sizeof(fe));
     }
     int openings() {
-        ZK_TRY(open_plans());
+        ZK_TRY(open_plans(P0, rows0));
         request_values();
         request_digests();
         const size_t NK = req.size();
@@ -1466,15 +1434,6 @@ struct ShardedProof {
         O->unpack(got.data(), pos.size(), CK, fri_pos, fold, KX, off_dig);
         stage_mark(P0, "queries");
         return ZK_OK;
-    }
-    int finish(uint8_t *proof_out, size_t *proof_len, zk_record *rec) {
-        const std::vector<uint8_t> bytes = serialize_proof(n, opt, C, R, h.data(), *O, KX == 2 ? &Y.rem_flat : nullptr);
-        stage_mark(P0, "serialize");
-        ZK_CHECK_HIP(hipStreamSynchronize(P0->st));
-        stage_collect(P0);
-        collect_kernel_stats(P0);
-        if (rec) *rec = R;
-        return deliver_proof(bytes, degree_flag, proof_out, proof_len);
     }
 };
 
@@ -1495,7 +1454,7 @@ int prove_sharded(Ctx &X, const uint8_t *trace, const zk_options *opt, const zk_
     ZK_TRY(S.ood_deep());
     ZK_TRY(S.fri());
     ZK_TRY(S.openings());
-    return S.finish(proof_out, proof_len, rec);
+    return S.finish(X.P[0], proof_out, proof_len, rec);
 }
 
 }  // namespace

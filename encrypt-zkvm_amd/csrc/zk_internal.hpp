@@ -326,9 +326,14 @@ struct EvalMap {
 // Rescue MDS / inverse-MDS __constant__ tables on the current device (once per device; thread-safe).
 // zk_prover_create calls it; the evaluator launches check it again (the plug point may run first).
 hipError_t upload_rescue_consts(hipStream_t st);
+// the map of a launch over a whole LDE of blowup 2^log_b: CE cosets 0 .. nce-1 (8: all; 7: the composition stage
+// derives the last one, bnd = false; with bnd always 8)
+EvalMap eval_map_whole(int log_b, int nce, bool bnd);
+// Composition evaluations over the CE cosets of `map`, written coset-major: comp[jl*n + q].  KX coefficient planes
+// (chal.hpp): consts = {a components} or, KX = 2, {a components, b components}, the b plane written at comp + plane.
 // bnd: the boundary (assertion) terms are evaluated per row (else: boundary_poly_add after interpolation)
-hipError_t eval_constraints_mapped(hipStream_t st, const fe *lde, int log_n, EvalMap map, const fe *periodic,
-                             const fe *divs, const AirConsts *consts_dev, fe *comp, bool bnd = true);
+hipError_t eval_constraints(hipStream_t st, int KX, const fe *lde, int log_n, EvalMap map, const fe *periodic,
+                            const fe *divs, const AirConsts *consts, size_t plane, fe *comp, bool bnd);
 // Trace validation (kernels.hip k_validate_trace; zk_validate_device): the device report of one launch.  The host
 // initialises it in-stream: counts 0, firsts UINT64_MAX, a_mask 0 and a_found[k] = the value assertion k asserts
 // (get_assertions order, air/src/lib.rs:170-195), which the kernel replaces with the asserted cell's value.
@@ -354,12 +359,6 @@ struct CrossMap {
     int derive7 = 0;
     fe k7[7] = {};
 };
-void comp_cross_mapped(hipStream_t st, const CrossMap &m, const NttTables &T8n, const PowTable &inv3, fe scale,
-                       fe w8inv, fe inv3n, int ncols, fe *polys, unsigned *nonzero_flag);
-// composition evaluations over the CE domain (8n), written coset-major: comp[r*n + q], i = 8q + r
-// nce: evaluate CE cosets 0 .. nce-1 (8: all; 7: the composition stage derives the last one, bnd = false)
-hipError_t eval_constraints(hipStream_t st, const fe *lde, int log_n, int log_b, const fe *periodic, const fe *divs,
-                      const AirConsts *consts_dev, fe *comp, bool bnd = true, int nce = 8);
 // add the boundary terms' quotient polynomial (one coefficient plane K) into col0 (n coefficients);
 // c = g^(n-2); scratch: DeepScratch (KX = 1); sets *flag when an assertion fails.  S: the trace coefficients' sources;
 // w: the 28 scalars w_c of its BASE and ZERO columns (host; may be null when every column is PLAIN)
@@ -374,9 +373,9 @@ void boundary_range_end(hipStream_t st, int log_n, fe c, fe *scratch, size_t k0,
                         unsigned *flag);
 // cross-coset step of the size-8n interpolation: per k1 < n, from the 8 per-coset inverse NTTs
 // (c_r[k1]), produce coefficients a[k1 + n*k2] = 3^-(k1+n k2) / (8n) * sum_r w8^(-r k2) w_8n^(-r k1) c_r[k1]
-// and write column k2 < ncols of the segmented composition polynomial: polys[k2*n + k1].
-void comp_cross_coset(hipStream_t st, const fe *c, int log_n, const NttTables &T8n, const PowTable &inv3,
-                      fe scale, fe w8inv, fe inv3n, int ncols, fe *polys, unsigned *nonzero_flag);
+// and write column k2 < ncols of the segmented composition polynomial, for the k1 range of the CrossMap.
+void comp_cross_mapped(hipStream_t st, const CrossMap &m, const NttTables &T8n, const PowTable &inv3, fe scale,
+                       fe w8inv, fe inv3n, int ncols, fe *polys, unsigned *nonzero_flag);
 
 // ---------------------------------------------------------------- OOD / DEEP / FRI
 // Written once over the challenge field (chal.hpp): KX = 1 the base field, KX = 2 FieldExtension::Quadratic.  A
@@ -492,12 +491,6 @@ void coset_major_to_natural(hipStream_t st, const fe *src, int log_n, int log_b,
 void fri_coin_launch(hipStream_t st, uint32_t *seed_dev, const uint8_t *root_dev, int k, fe *alpha_dev,
                      fe *alpha_log);
 
-// composition over E: consts2_dev = {a components, b components}; planes comp[0, 8n), comp[8n, 16n)
-hipError_t eval_constraints_ext(hipStream_t st, const fe *lde, int log_n, int log_b, const fe *periodic, const fe *divs,
-                          const AirConsts *consts2_dev, fe *comp, bool bnd = true, int nce = 8);
-// ... over the CE cosets of `map` (see eval_constraints_mapped), b plane at comp + plane
-hipError_t eval_constraints_ext_mapped(hipStream_t st, const fe *lde, int log_n, EvalMap map, const fe *periodic,
-                                 const fe *divs, const AirConsts *consts2_dev, size_t plane, fe *comp, bool bnd = true);
 // out[k] = src[idx[k]] for field elements
 void gather_fe(hipStream_t st, const fe *src, const uint64_t *idx, size_t k, fe *out);
 

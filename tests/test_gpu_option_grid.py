@@ -213,7 +213,7 @@ def test_option_changes_on_one_warm_prover(oracle):
         otherwise `fixed_drop(p, H->snap)` forgets it, FS stays null, this proof forms nothing from it (fixed == [])
         and snap_now retakes it at the new B, so the proof after that is FIXED again.  B is the plan's blowup
         (1 << pl->log_b): only a change of blowup (or lwe_size) takes this branch.  The field extension and the FRI
-        folding enter after the trace commitment (prove_once S3 onward), so changing them alone keeps FIXED."""
+        folding enter after the trace commitment (SingleProof::constraints onward), so changing them alone keeps FIXED."""
     t, p = get_trace(13, "cipher", 41)
     opub = oracle_pub(oracle, p)
     want = {}
