@@ -2494,6 +2494,142 @@ extern "C" int zk_diag_deep_parts(int device, const uint8_t *tpolys, const uint8
     return diag_deep(device, tpolys, cpolys, ccols, n, ext, z, zg, alpha_t, alpha_c, parts, out);
 }
 
+// ---- the composition stage (S4) on inputs of the caller's choice (tests/test_gpu_composition.py; the reference is
+// tests/back_half_ref.py).  comp: ext planes of 8 cosets x n values in the evaluator's coset-major layout,
+// comp[(8 j + r) n + q] = plane j at 3 w_8n^r w_n^q.  tpolys (optional): 28 planes of n trace coefficients, with
+// coeff_b (ext x 22) and bnd1 (ext values) the assertion terms' constants of each plane; the second divisor point is
+// g^(n-2), as draw_air_consts sets it.  Every value canonical.
+static int diag_comp_args(const char *who, const uint8_t *comp, size_t n, int ext, int ncols, const uint8_t *tpolys,
+                          const uint8_t *coeff_b, const uint8_t *bnd1, const void *polys_out, const void *flag_out,
+                          AirConsts *K) {
+    bool ok = comp && polys_out && flag_out && n >= 16 && !(n & (n - 1)) && n <= ((size_t)1 << 22) &&
+              (ext == 1 || ext == 2) && ncols >= 1 && ncols <= 8 && (!tpolys || (coeff_b && bnd1));
+    memset(K, 0, 2 * sizeof K[0]);
+    for (size_t i = 0; ok && i < (size_t)ext * 8 * n; i++) ok = fe_canonical(fe_from_bytes(comp + 16 * i));
+    for (size_t i = 0; ok && tpolys && i < (size_t)W * n; i++) ok = fe_canonical(fe_from_bytes(tpolys + 16 * i));
+    for (int j = 0; ok && tpolys && j < ext; j++) {
+        for (int k = 0; k < NUM_ASSERTS; k++) {
+            K[j].coeff_b[k] = fe_from_bytes(coeff_b + 16 * (NUM_ASSERTS * j + k));
+            ok = ok && fe_canonical(K[j].coeff_b[k]);
+        }
+        K[j].bnd1 = fe_from_bytes(bnd1 + 16 * j);
+        ok = ok && fe_canonical(K[j].bnd1);
+    }
+    if (!ok)
+        ZK_FAIL(ZK_ERR_INVALID_ARG, std::string(who) + ": n a power of two in [16, 2^22], ext 1 or 2, 1 .. 8 columns, "
+                                    "canonical values, coeff_b and bnd1 with tpolys");
+    for (int j = 0; j < ext; j++) K[j].g_last2 = h_pow(h_root_of_unity(ilog2(n)), n - 2);
+    return ZK_OK;
+}
+
+// composition_stage as SingleProof::composition calls it, with the all-PLAIN coefficient table: the per-coset inverse
+// NTTs of nce cosets (7: coset 7 of comp is not read, the cross step derives it), comp_cross_mapped per plane,
+// boundary_poly_add per plane when tpolys is given, lde_commit over `blowup`.  polys_out: the ext ncols column
+// polynomials (base column (c, j) at (c ext + j) n); root_out: the constraint root; *flag_out: the degree flag as the
+// kernels left it (0 or 1) -- a set flag is the caller's to judge, not an error here.
+extern "C" int zk_diag_composition(int device, const uint8_t *comp, size_t n, uint32_t blowup, int ext, int ncols,
+                                   int nce, const uint8_t *tpolys, const uint8_t *coeff_b, const uint8_t *bnd1,
+                                   uint8_t *polys_out, uint8_t *root_out, uint32_t *flag_out) {
+    AirConsts K[2];
+    ZK_TRY(diag_comp_args("zk_diag_composition", comp, n, ext, ncols, tpolys, coeff_b, bnd1, polys_out, flag_out, K));
+    if (!root_out || (nce != 7 && nce != 8) || (nce == 7 && ncols > 7) || blowup < 8 || blowup > 64 ||
+        (blowup & (blowup - 1)))
+        ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_composition: nce 8, or 7 with at most 7 columns; blowup a power of two in [8, 64]");
+    zk_prover *p = nullptr;
+    ZK_TRY(zk_prover_create(device, n, blowup, &p));
+    std::unique_ptr<zk_prover, void (*)(zk_prover *)> guard(p, zk_prover_destroy);
+    IoScope io_scope(p);
+    Plan *pl = nullptr;
+    ZK_TRY(get_plan(p, n, blowup, &pl));
+    if (ext == 2) ZK_TRY(ensure_ext(p));
+    const Planes b = planes(p, ext);
+    ZK_CHECK_HIP(hipMemcpy(b.comp, comp, (size_t)ext * 8 * n * 16, hipMemcpyHostToDevice));
+    if (tpolys) ZK_CHECK_HIP(hipMemcpy(p->polys, tpolys, (size_t)W * n * 16, hipMemcpyHostToDevice));
+    uint8_t root[32];
+    unsigned degree_flag = 0;
+    ZK_TRY(composition_stage(p, pl, ext, ncols, b.comp, b.ctmp, b.clde, root, tpolys ? K : nullptr, nce));
+    ZK_TRY(d2h_small(p, &degree_flag, p->flag, 4));
+    ZK_TRY(d2h_flush(p));  // root and flag
+    ZK_CHECK_HIP(hipMemcpy(polys_out, p->cpolys, (size_t)ext * ncols * n * 16, hipMemcpyDeviceToHost));
+    memcpy(root_out, root, 32);
+    *flag_out = degree_flag;
+    return ZK_OK;
+}
+
+// The cross step and the assertion quotient by coefficient ranges, as the ranks of a sharded proof compute them
+// (ShardedProof::cross_step, boundary_begin, boundary_quotient), on one device in rank order: `parts` ranges of
+// kg = n / parts coefficients (a whole number of ZK_DEEP_RANGE_QUANTUM each).  It takes comp, as zk_diag_composition
+// does, and runs the per-coset inverse NTTs once for all ranges (the call composition_stage makes for nce = 8): a
+// rank's share of their output is what the all-to-all hands it, and the ranges never transform again.  Per range g and
+// plane: comp_cross_mapped with k0 = g kg, kcount = kg, pstride = ext kg, no derived coset and the sources offset to
+// the range, into the range's slices [(c ext + plane) kg]; then per plane boundary_range_begin for every range, the
+// later ranges' sums added here as the all-gather and k_sh_suffix_carry do, boundary_range_end into the range's slice
+// of column 0.  The ranges share one division scratch, so each range's block carries are kept aside between its begin
+// and its end (as in zk_diag_deep_parts).  polys_out: the slices assembled in zk_diag_composition's layout;
+// *flag_out: the degree flag.  No LDE, no commitment.
+extern "C" int zk_diag_composition_parts(int device, const uint8_t *comp, size_t n, int ext, int ncols, int parts,
+                                         const uint8_t *tpolys, const uint8_t *coeff_b, const uint8_t *bnd1,
+                                         uint8_t *polys_out, uint32_t *flag_out) {
+    AirConsts K[2];
+    ZK_TRY(diag_comp_args("zk_diag_composition_parts", comp, n, ext, ncols, tpolys, coeff_b, bnd1, polys_out, flag_out, K));
+    if (parts < 2 || parts > 8 || (parts & (parts - 1)) || n < (size_t)parts * ZK_DEEP_RANGE_QUANTUM)
+        ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_composition_parts: 2, 4 or 8 ranges of a multiple of 2048 coefficients");
+    zk_prover *p = nullptr;
+    ZK_TRY(zk_prover_create(device, n, 8, &p));
+    std::unique_ptr<zk_prover, void (*)(zk_prover *)> guard(p, zk_prover_destroy);
+    Plan *pl = nullptr;
+    ZK_TRY(get_plan(p, n, 8, &pl));
+    if (ext == 2) ZK_TRY(ensure_ext(p));
+    const Planes b = planes(p, ext);
+    const int log_n = pl->log_n;
+    const size_t kg = n / parts, slice = (size_t)ncols * ext * kg;
+    ZK_CHECK_HIP(hipMemcpy(b.comp, comp, (size_t)ext * 8 * n * 16, hipMemcpyHostToDevice));
+    if (tpolys) ZK_CHECK_HIP(hipMemcpy(p->polys, tpolys, (size_t)W * n * 16, hipMemcpyHostToDevice));
+    ntt(p->st, pl->Tn, b.comp, n, b.ctmp, n, 8 * ext, true, nullptr, nullptr, p->tmp);
+    ZK_CHECK_HIP(hipMemsetAsync(p->flag, 0, 4, p->st));
+    fe *out = b.comp;  // the ranges' slices, range after range (the transform has consumed the values)
+    const fe scale = h_inv(fe_make(8 * n)), w8inv = h_inv(h_root_of_unity(3)), inv3n = h_inv(h_pow(fe_make(3), n));
+    for (int g = 0; g < parts; g++)
+        for (int pln = 0; pln < ext; pln++) {
+            CrossMap cm;
+            for (int r = 0; r < 8; r++) cm.c[r] = b.ctmp + (size_t)(8 * pln + r) * n + g * kg;
+            cm.k0 = g * kg;
+            cm.kcount = kg;
+            cm.pstride = (size_t)ext * kg;
+            comp_cross_mapped(p->st, cm, pl->Tce, pl->inv3, scale, w8inv, inv3n, ncols, out + g * slice + pln * kg, p->flag);
+        }
+    const DeepScratch S(p->dscratch, n, 1);
+    const size_t ncarry = 2 * (kg / ZK_DEEP_BLOCK);
+    for (int pln = 0; tpolys && pln < ext; pln++) {
+        std::vector<fe> tot((size_t)parts * 2);
+        for (int g = 0; g < parts; g++) {
+            const fe *t = boundary_range_begin(p->st, coeff_plain(p->polys, n), nullptr, log_n, K[pln], K[0].g_last2,
+                                               p->dscratch, g * kg, kg);
+            ZK_CHECK_HIP(hipMemcpyAsync(p->clde + g * ncarry, S.bs, ncarry * sizeof(fe), hipMemcpyDeviceToDevice, p->st));
+            ZK_CHECK_HIP(hipMemcpyAsync(&tot[g * 2], t, 2 * sizeof(fe), hipMemcpyDeviceToHost, p->st));
+        }
+        ZK_CHECK_HIP(hipStreamSynchronize(p->st));
+        std::vector<fe> later((size_t)parts * 2, fe_zero());
+        for (int g = parts - 2; g >= 0; g--)
+            for (int c = 0; c < 2; c++) later[g * 2 + c] = fe_add(later[(g + 1) * 2 + c], tot[(g + 1) * 2 + c]);
+        fe *ext_sums = p->ood + (size_t)pln * parts * 2;
+        ZK_CHECK_HIP(hipMemcpy(ext_sums, later.data(), later.size() * sizeof(fe), hipMemcpyHostToDevice));
+        for (int g = 0; g < parts; g++) {
+            ZK_CHECK_HIP(hipMemcpyAsync(S.bs, p->clde + g * ncarry, ncarry * sizeof(fe), hipMemcpyDeviceToDevice, p->st));
+            boundary_range_end(p->st, log_n, K[0].g_last2, p->dscratch, g * kg, kg, ext_sums + g * 2,
+                               out + g * slice + pln * kg - g * kg, p->flag);
+        }
+    }
+    ZK_CHECK_HIP(hipStreamSynchronize(p->st));
+    std::vector<fe> h((size_t)parts * slice);
+    ZK_CHECK_HIP(hipMemcpy(h.data(), out, h.size() * sizeof(fe), hipMemcpyDeviceToHost));
+    for (int g = 0; g < parts; g++)
+        for (int c = 0; c < ncols * ext; c++)
+            memcpy(polys_out + 16 * ((size_t)c * n + g * kg), &h[g * slice + (size_t)c * kg], kg * sizeof(fe));
+    ZK_CHECK_HIP(hipMemcpy(flag_out, p->flag, 4, hipMemcpyDeviceToHost));
+    return ZK_OK;
+}
+
 // The three consumers of the trace coefficients through a CoeffSrc (tests/test_coeff_sources.py): tplanes = 29 planes of
 // n coefficients, plane c < 28 column c's (mode PLAIN: the column; BASE: its base; ZERO: not read) and plane 28 standing
 // for e_(n-1) (any polynomial: the consumers are linear in it); modes[28]; w[28] the columns' scalars (canonical).

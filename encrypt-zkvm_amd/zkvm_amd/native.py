@@ -299,6 +299,11 @@ def lib():
             L.zk_diag_deep_parts.argtypes = [i32, vp, vp, i32, sz, i32, vp, vp, vp, vp, i32, vp]
             # (device, layer, L, ext, fold, lb, wstride, alpha, root_out, next_out)
             L.zk_diag_fri_layer.argtypes = [i32, vp, sz, i32, i32, i32, sz, vp, vp, vp]
+        if hasattr(L, "zk_diag_composition"):
+            # (device, comp, n, blowup, ext, ncols, nce, tpolys, coeff_b, bnd1, polys_out, root_out, flag_out)
+            L.zk_diag_composition.argtypes = [i32, vp, sz, u32, i32, i32, i32, vp, vp, vp, vp, vp, C.POINTER(u32)]
+            # (device, comp, n, ext, ncols, parts, tpolys, coeff_b, bnd1, polys_out, flag_out)
+            L.zk_diag_composition_parts.argtypes = [i32, vp, sz, i32, i32, i32, vp, vp, vp, vp, C.POINTER(u32)]
         _lib = L
     return _lib
 

@@ -1,4 +1,5 @@
-"""Plain-integer reference of the back half of a proof, for tests/test_gpu_back_half.py (not a test module).
+"""Plain-integer reference of the back half of a proof, for tests/test_gpu_back_half.py, and of the composition stage
+before it, for tests/test_gpu_composition.py (not a test module).
 
 Everything after the constraint commitment, restated over Python integers mod p = 2^128 - 45 2^40 + 1 and, over the
 quadratic extension E = F[X] / (X^2 - X - 1), over pairs (a, b) = a + b X:
@@ -11,7 +12,10 @@ quadratic extension E = F[X] / (X^2 - X - 1), over pairs (a, b) = a + b X:
   * BatchMerkleProof::get_root: the root rebuilt from opened rows, their positions and the serialized batch proof
     (u8 number of paths, per path u8 length and 32-byte digests: what verifier.cpp parses and wire.py cuts out);
   * one FRI layer: its rows, their Merkle root by pairwise merges, and the fold: per row the interpolant of the
-    `fold` values over x_r <zeta> evaluated at alpha by Lagrange's formula (over E by components).
+    `fold` values over x_r <zeta> evaluated at alpha by Lagrange's formula (over E by components);
+  * the composition stage: a polynomial's 8 n values over the CE coset in the evaluator's coset-major order, its
+    segmentation into column polynomials, the assertion terms' quotient (f0 - f0(1)) / (x - 1) + (f1 - f1(c)) / (x - c)
+    with its remainder flag, and the constraint root over the columns' LDE rows.
 
 The hash is the CPU oracle's BLAKE3 (oracle.blake3, pinned against the specification by tests/test_blake3_pin.py);
 tests/test_back_half_ref_cpu.py checks each part of this file against the oracle and the golden proofs.
@@ -338,3 +342,54 @@ def fri_layer_root(blake3, layer, fold, ext):
     while len(level) > 1:
         level = [blake3(level[i] + level[i + 1]) for i in range(0, len(level), 2)]
     return level[0]
+
+
+# ---------------------------------------------------------------- the composition stage
+CE_BLOWUP = 8  # the constraint evaluation domain: 8 n points 3 w_8n^i
+ASSERT_COL0 = [0, 7, 8, 11] + list(range(12, 20))  # the step 0 assertions' columns (coefficients 0 .. 11)
+ASSERT_COL1 = [7, 8] + list(range(12, 20))  # the step n - 2 assertions' columns (coefficients 12 .. 21)
+
+
+def composition_values(coeffs, n, eval_coset=None):
+    """The 8 n values of the polynomial with the given (at most 8 n) coefficients over the CE coset, coset-major as
+    the evaluator writes them: out[r n + q] = P(3 w_8n^r w_n^q) = P(3 w_8n^(r + 8 q)).  eval_coset: the oracle's
+    transform (natural order) where its speed is wanted; without it every point by Horner's rule."""
+    ce = CE_BLOWUP * n
+    assert len(coeffs) <= ce
+    if eval_coset is not None:
+        nat = eval_coset(list(coeffs), ce, FRI_OFFSET)
+    else:
+        w = pow(TWO_ADIC_ROOT, (1 << 40) // ce, P)
+        nat = [horner(coeffs, FRI_OFFSET * x % P) for x in powers(w, ce)]
+    return [nat[r + CE_BLOWUP * q] for r in range(CE_BLOWUP) for q in range(n)]
+
+
+def segment(coeffs, n, ncols):
+    """the column polynomials: column c holds coefficients [c n, (c + 1) n), zeros past the end of coeffs"""
+    full = list(coeffs) + [0] * max(0, ncols * n - len(coeffs))
+    return [full[c * n:(c + 1) * n] for c in range(ncols)]
+
+
+def boundary_quotient(tpolys, cb, bnd1, c):
+    """The assertion terms' quotient of one coefficient plane: with f0 = sum_{i<12} cb[i] T_col0[i] and
+    f1 = sum_{j<10} cb[12+j] T_col1[j] - bnd1, the n coefficients of (f0 - f0(1)) / (x - 1) + (f1 - f1(c)) / (x - c),
+    and flag = 1 iff a remainder f0(1) or f1(c) is non-zero (an assertion fails).  The quotient is defined either way.
+    Over the quadratic extension the coefficients cb and bnd1 are E values but the trace polynomials and both divisor
+    points are base-field, so component j of the quotient is this function of component j of every cb and of bnd1: the
+    planes are independent and the caller takes them one at a time (test_back_half_ref_cpu checks that against e_mul
+    and the E division term by term)."""
+    cols0, cols1 = [tpolys[k] for k in ASSERT_COL0], [tpolys[k] for k in ASSERT_COL1]
+    f0 = [sum(map(mul, cb[:12], col)) % P for col in zip(*cols0)]
+    f1 = [sum(map(mul, cb[12:22], col)) % P for col in zip(*cols1)]
+    f1[0] = (f1[0] - bnd1) % P
+    q0, r0 = divide_out(f0, 1, 1)
+    q1, r1 = divide_out(f1, c, 1)
+    return [(x + y) % P for x, y in zip(q0, q1)], int(r0 != 0 or r1 != 0)
+
+
+def composition_root(blake3, merkle_root, eval_coset, polys, n, blowup):
+    """The constraint commitment of the base columns `polys` (in column order: over E the components a, b of each E
+    column): every column extended over the blowup n points 3 w_N^i by the oracle's transform, row i the columns'
+    values there, each row hashed (row_digest) and the rows' Merkle root taken by the oracle."""
+    ldes = [eval_coset(list(col), blowup * n, FRI_OFFSET) for col in polys]
+    return merkle_root(b"".join(row_digest(blake3, row) for row in zip(*ldes)))

@@ -243,3 +243,146 @@ def test_grinding_reference_finds_the_golden_nonce(oracle, name):
     assert ref.nonce_zeros(oracle.blake3, seed, nonce) >= bits
     assert ref.grind(oracle.blake3, seed, nonce, 1, bits) == nonce and ref.grind(oracle.blake3, seed, 1, 1, 0) == 1
     assert ref.grind(oracle.blake3, seed, 1, 64, 64) == ref.NO_NONCE
+
+
+# ---------------------------------------------------------------- the composition stage
+def test_composition_values_by_horner_and_by_the_oracles_transform_agree(oracle):
+    rnd = random.Random(21)
+    n = 16
+    full = [rnd.randrange(P) for _ in range(8 * n)]
+    for coeffs in (full, full[:7 * n], [5], [0] * (7 * n) + [1], [P - 1] * (7 * n)):
+        assert ref.composition_values(coeffs, n) == ref.composition_values(coeffs, n, oracle.eval_coset)
+    # the layout: entry r n + q is the value at 3 w_8n^r w_n^q
+    vals = ref.composition_values(full, n)
+    w8n, wn = oracle.root_of_unity(7), oracle.root_of_unity(4)
+    for r, q in ((0, 0), (1, 0), (0, 1), (7, 15), (3, 9)):
+        assert vals[r * n + q] == ref.horner(full, 3 * pow(w8n, r, P) * pow(wn, q, P) % P)
+    # and back: the natural-order values interpolate to the coefficients, which segment() cuts into columns
+    nat = [vals[(i % 8) * n + i // 8] for i in range(8 * n)]
+    assert oracle.interp_coset(nat, 3) == full
+    assert ref.segment(full, n, 8) == [full[c * n:(c + 1) * n] for c in range(8)]
+    assert ref.segment([1, 2, 3], 2, 3) == [[1, 2], [3, 0], [0, 0]] and ref.segment([1, 2, 3], 2, 1) == [[1, 2]]
+
+
+def cross_step_model(oracle, comp, n, ncols, nce):
+    """The cross-coset step in plain integers, as k_comp_cross is written: from the per-coset interpolants c_r, per k1
+    the values d_r = c_r[k1] w_8n^(-r k1), with nce = 7 the derived d_7 = -sum_{r<7} w_8^(r+1) d_r, the size-8 transform
+    b_k2 = sum_r w_8^(-r k2) d_r and a[k1 + n k2] = b_k2 3^-(k1 + n k2) / 8.  -> (ncols columns, top-block flag)"""
+    w8n, w8 = oracle.root_of_unity((8 * n).bit_length() - 1), oracle.root_of_unity(3)
+    c = [oracle.interp_coset(comp[r * n:(r + 1) * n], 1) for r in range(nce)]
+    cols, flag = [[0] * n for _ in range(ncols)], 0
+    for k1 in range(n):
+        d = [c[r][k1] * pow(w8n, -r * k1, P) % P for r in range(nce)]
+        if nce == 7:
+            d.append(-sum(pow(w8, r + 1, P) * d[r] for r in range(7)) % P)
+        for k2 in range(8):
+            b = sum(pow(w8, -r * k2, P) * d[r] for r in range(8)) % P
+            a = b * pow(8 * pow(3, k1 + n * k2, P), -1, P) % P
+            if k2 < ncols:
+                cols[k2][k1] = a
+            else:
+                flag |= a != 0
+    return cols, int(flag)
+
+
+def test_cross_step_with_a_derived_coset_model(oracle):
+    """What tests/test_gpu_composition.py expects of the derived coset: for degree < 7n the polynomial itself, coset 7
+    never read; for degree in [7n, 8n) a polynomial with a zero top block that agrees with the input on cosets 0 .. 6
+    (flag 0); and with all eight cosets the flag is set exactly by a coefficient at or past ncols n."""
+    rnd = random.Random(23)
+    n = 16
+    for coeffs in ([rnd.randrange(P) for _ in range(7 * n)], [0] * (7 * n - 1) + [1], [P - 1] * (7 * n), [P - 1]):
+        vals = ref.composition_values(coeffs, n)
+        hidden = vals[:7 * n] + [P - 1] * n
+        assert cross_step_model(oracle, hidden, n, 7, 7) == (ref.segment(coeffs, n, 7), 0)
+        assert cross_step_model(oracle, vals, n, 7, 8) == (ref.segment(coeffs, n, 7), 0)
+    for coeffs in ([0] * (7 * n) + [1], [rnd.randrange(P) for _ in range(8 * n)]):
+        vals = ref.composition_values(coeffs, n)
+        cols, flag = cross_step_model(oracle, vals[:7 * n] + [P - 1] * n, n, 7, 7)
+        q = [v for col in cols for v in col]
+        assert flag == 0 and q != coeffs[:7 * n]
+        assert ref.composition_values(q, n)[:7 * n] == vals[:7 * n]
+        assert cross_step_model(oracle, vals, n, 7, 8) == (ref.segment(coeffs, n, 7), 1)
+    for ncols in (1, 5):
+        for k, want in ((ncols * n - 1, 0), (ncols * n, 1), (7 * n - 1, 1)):
+            coeffs = [0] * k + [1]
+            vals = ref.composition_values(coeffs, n)
+            assert cross_step_model(oracle, vals, n, ncols, 7) == (ref.segment(coeffs, n, ncols), want)
+
+
+def test_boundary_quotient_planes_are_the_extension_quotients_components():
+    """The quotient over E, term by term with e_mul and divided at the lifted base points, is plane by plane the
+    base-field quotient of that plane's coefficients; a remainder in either plane alone raises that plane's flag."""
+    rnd = random.Random(22)
+    n = 16
+    tp = [[rnd.randrange(P) for _ in range(n)] for _ in range(28)]
+    cb = [[rnd.randrange(P) for _ in range(22)] for _ in range(2)]
+    bnd1 = [rnd.randrange(P) for _ in range(2)]
+    c = pow(pow(ref.TWO_ADIC_ROOT, (1 << 40) // n, P), n - 2, P)
+    cbe = list(zip(*cb))
+    f0 = [(0, 0)] * n
+    f1 = [(0, 0)] * n
+    for k in range(n):
+        for i, col in enumerate(ref.ASSERT_COL0):
+            f0[k] = ref.e_add(f0[k], ref.e_mul(cbe[i], (tp[col][k], 0)))
+        for j, col in enumerate(ref.ASSERT_COL1):
+            f1[k] = ref.e_add(f1[k], ref.e_mul(cbe[12 + j], (tp[col][k], 0)))
+    f1[0] = ref.e_sub(f1[0], tuple(bnd1))
+    q0, r0 = ref.divide_out(f0, (1, 0), 2)
+    q1, r1 = ref.divide_out(f1, (c, 0), 2)
+    planes = [ref.boundary_quotient(tp, cb[j], bnd1[j], c) for j in range(2)]
+    assert [ref.e_add(x, y) for x, y in zip(q0, q1)] == list(zip(planes[0][0], planes[1][0]))
+    assert [int(r0[j] != 0 or r1[j] != 0) for j in range(2)] == [planes[0][1], planes[1][1]] == [1, 1]
+    # remainders removed in plane 0 alone (its f0(1) through column 0's constant, its f1(c) through bnd1)
+    s0 = sum(cb[0][i] * sum(tp[col]) for i, col in enumerate(ref.ASSERT_COL0)) % P
+    tp[0][0] = (tp[0][0] - s0 * pow(cb[0][0], -1, P)) % P
+    good1 = sum(cb[0][12 + j] * ref.horner(tp[col], c) for j, col in enumerate(ref.ASSERT_COL1)) % P
+    q, flag = ref.boundary_quotient(tp, cb[0], good1, c)
+    assert flag == 0 and q[n - 1] == 0
+    assert ref.boundary_quotient(tp, cb[1], bnd1[1], c)[1] == 1
+    assert ref.boundary_quotient(tp, cb[0], (good1 + 1) % P, c)[1] == 1
+
+
+@pytest.mark.parametrize("name", ["lr", "lr_quad"])
+def test_composition_reference_on_a_golden_workload(oracle, name):
+    """The oracle's dumps of a golden workload: the composition values interpolate and segment into the column
+    polynomials it commits to (over E the dump carries the a plane), whose root by composition_root is the recorded
+    constraint root; and the boundary quotient of the trace polynomials under the recorded coefficients, evaluated at
+    every CE point, is the point-wise f0(x) / (x - 1) + f1(x) / (x - c), with no remainder."""
+    import numpy as np
+
+    c = CASES[name]
+    trace = np.load(GOLD / f"{name}.trace.npy", allow_pickle=False)
+    ints = lambda hs: [int(h, 16) for h in hs]  # noqa: E731
+    pub = oracle.make_pub(ints(c["program_hash"]), ints(c["stack_outputs"]), c["lwe_size"], c["delta"])
+    opts = c["options"]
+    _, rec, dumps = oracle.prove(trace, pub, oracle.default_options(**opts), want=("composition", "comp_polys"))
+    n, K, ncols = c["trace_len"], opts["field_extension"], rec.num_ccols
+    assert ncols == 7
+    comp = oracle.array_to_elems(dumps["composition"])
+    coeffs = oracle.interp_coset(comp, 3)
+    assert not any(coeffs[ncols * n:])
+    cpolys = oracle.array_to_elems(dumps["comp_polys"])[:ncols * K * n]
+    base_cols = [cpolys[i * n:(i + 1) * n] for i in range(ncols * K)]
+    assert ref.segment(coeffs, n, ncols) == base_cols[::K]
+    assert ref.composition_values(coeffs, n, oracle.eval_coset) == [comp[r + 8 * q] for r in range(8) for q in range(n)]
+    assert ref.composition_root(oracle.blake3, oracle.merkle_root, oracle.eval_coset, base_cols, n,
+                                opts["blowup"]) == bytes(rec.constraint_root)
+    # the assertion quotient (the record keeps the a component of every coefficient: plane a)
+    tp = [oracle.interp_coset(oracle.array_to_elems(trace[k]), 1) for k in range(28)]
+    cb = oracle.from_bytes(bytes(rec.coeff_b))[:22]
+    asserted = ints(c["program_hash"])[:2] + ints(c["stack_outputs"])[:8]
+    bnd1 = sum(x * v for x, v in zip(cb[12:], asserted)) % P
+    g = oracle.root_of_unity(n.bit_length() - 1)
+    cc = pow(g, n - 2, P)
+    q, flag = ref.boundary_quotient(tp, cb, bnd1, cc)
+    assert flag == 0 and q[n - 1] == 0 and any(q)
+    ev = {k: oracle.eval_coset(tp[k], 8 * n, 3) for k in ref.ASSERT_COL0}
+    w = oracle.root_of_unity((8 * n).bit_length() - 1)
+    x = 3
+    for i in range(8 * n):
+        f0 = sum(cb[t] * ev[k][i] for t, k in enumerate(ref.ASSERT_COL0))
+        f1 = sum(cb[12 + t] * ev[k][i] for t, k in enumerate(ref.ASSERT_COL1)) - bnd1
+        want = (f0 * pow(x - 1, -1, P) + f1 * pow(x - cc, -1, P)) % P
+        assert ref.horner(q, x) == want, i
+        x = x * w % P
