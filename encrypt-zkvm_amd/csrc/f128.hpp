@@ -672,6 +672,47 @@ ZK_HD fe acc288_reduce(const acc288 &acc) {
     return fe_add(v, top);
 }
 
+// ---- lazy sums of products by wave-uniform constants: a term is the unreduced column sum of the W-set product
+// (ws_columns_s: sum_i x_i W_i with x_i < 2^32, W_i < p < 2^128, so below 2^162), not the 256-bit product.
+// acc192 takes sums whose every term is such a product (plus at most one canonical start value): N terms stay below
+// N 2^162 + 2^128, so the 64 bits above bit 128 hold T < N 2^34 + 1, and one ws_fold reduces the sum -- its
+// m1 = hi32((s4 + 1) K) + s5 K needs s5 K < 2^32 - 2^15, i.e. s5 = T >> 32 <= 4 N < 2^18, and its result is canonical
+// for T C < 2^127.  ACC192_MAX_TERMS = 2^15 keeps both with room; the evaluator's longest sum has 12 terms.
+// acc288_madd_uniform adds the same term to a 288-bit sum that also holds 256-bit products (acc288's own 2^32-term
+// bound covers it: a term is smaller than a 256-bit product).
+constexpr int ACC192_MAX_TERMS = 1 << 15;
+struct acc192 {
+    uint32_t w[6];
+};
+__device__ __forceinline__ acc192 acc192_zero() { return acc192{{0, 0, 0, 0, 0, 0}}; }
+__device__ __forceinline__ acc192 acc192_from(fe v) { return acc192{{lo32(v.lo), hi32(v.lo), lo32(v.hi), hi32(v.hi), 0, 0}}; }
+__device__ __forceinline__ void acc192_madd_uniform(acc192 &acc, fe x, const fe_ws &W) {
+    uint32_t r[4], s4, s5, c;
+    asm volatile("" : "+v"(x.lo), "+v"(x.hi) : "v"(acc.w[0]));  // products in the order of the sum, as in acc288_madd
+    ws_columns_s(x, W, r, s4, s5);
+    acc.w[0] = __builtin_addc(acc.w[0], r[0], 0u, &c);
+#pragma unroll
+    for (int k = 1; k < 4; k++) acc.w[k] = __builtin_addc(acc.w[k], r[k], c, &c);
+    acc.w[4] = __builtin_addc(acc.w[4], s4, c, &c);
+    acc.w[5] += s5 + c;
+}
+__device__ __forceinline__ fe acc192_reduce(const acc192 &acc) {
+    return ws_fold(acc.w[0], acc.w[1], acc.w[2], acc.w[3], acc.w[4], acc.w[5]);
+}
+__device__ __forceinline__ void acc288_madd_uniform(acc288 &acc, fe x, const fe_ws &W) {
+    uint32_t r[4], s4, s5, c;
+    asm volatile("" : "+v"(x.lo), "+v"(x.hi) : "v"(acc.w[0]));
+    ws_columns_s(x, W, r, s4, s5);
+    acc.w[0] = __builtin_addc(acc.w[0], r[0], 0u, &c);
+#pragma unroll
+    for (int k = 1; k < 4; k++) acc.w[k] = __builtin_addc(acc.w[k], r[k], c, &c);
+    acc.w[4] = __builtin_addc(acc.w[4], s4, c, &c);
+    acc.w[5] = __builtin_addc(acc.w[5], s5, c, &c);
+    acc.w[6] = __builtin_addc(acc.w[6], 0u, c, &c);
+    acc.w[7] = __builtin_addc(acc.w[7], 0u, c, &c);
+    acc.w[8] += c;
+}
+
 // device and host overloads (clang resolves by target)
 __device__ __forceinline__ fe fe_mul(fe a, fe b) { return fe_mul_asm(a, b); }
 // host: unsigned __int128 with the same two folds

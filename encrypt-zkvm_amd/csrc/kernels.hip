@@ -1564,14 +1564,21 @@ __device__ __forceinline__ fe adj_row(int r, const fe y[4]) {
 // 3^-72 mod p: the adjugate path's cubes carry 3^72, folded into the coefficients (ct3 = ct 3^-72)
 static constexpr fe ZK_INV3_72 = fe{0x8092deb1ab776293ull, 0xf0185d00eca40a3bull};
 
-// Block-shared constants of one evaluation (read through LDS so that none of them is pinned in
-// SGPRs across the whole kernel -- the cause of SGPR spills and 1-wave occupancy before).
-struct EvalShared {
-    fe ct[20], cb[22], ct2[20], cb2[22];
-    fe ct3[4], nct[4], ct3b[4], nctb[4];  // constraints 12..15: ct 3^-72 and -ct (planes a, b)
-    fe u[4], ub[4];                       // their linear half's weights of the cubes (air_fold_mds; planes a, b)
-    fe delta, bnd1, bnd1b;
-};
+// The launch-uniform multipliers of one evaluation (composition coefficients and what the host folds from them, delta)
+// are never held in registers or LDS: each product reads its W set from AirConsts::ws by scalar loads at the point of
+// use (fe_mul_uniform and the lazy acc192 / acc288_madd_uniform sums, f128.hpp), 16 SGPRs for the length of one
+// product.  The table index carries a zero offset that is laundered with the row pointer between sections (ZK_SEQK
+// below), so that a section's scalar loads are not hoisted above the section before it and pinned in SGPRs across
+// the kernel (laundering the pointer itself would lose its address space, and with it the scalar loads).
+void air_build_ws(AirConsts &K) {
+    for (int k = 0; k < 20; k++)
+        K.ws[EW_CT + k] = make_fe_ws(k >= 12 && k < 16 ? fe_mul(K.coeff_t[k], ZK_INV3_72) : K.coeff_t[k]);
+    for (int r = 0; r < 2; r++) K.ws[EW_NCT + r] = make_fe_ws(fe_neg(K.coeff_t[12 + r]));
+    for (int k = 0; k < 4; k++) K.ws[EW_U + k] = make_fe_ws(air_fold_mds(K.coeff_t + 12, k));
+    K.ws[EW_D89] = make_fe_ws(fe_sub(K.coeff_t[9], K.coeff_t[8]));
+    K.ws[EW_DELTA] = make_fe_ws(K.delta);
+    for (int k = 0; k < 22; k++) K.ws[EW_CB + k] = make_fe_ws(K.coeff_b[k]);
+}
 
 #ifndef ZK_EVAL_LAZY
 #define ZK_EVAL_LAZY 1  // lazy 288-bit sum over the selector section's terms (base field)
@@ -1589,38 +1596,25 @@ struct EvalShared {
 // in coefficient form instead (boundary_poly_add); the plug point and the sharded prover pass true.
 template <int KE, bool BND>
 __global__ void __launch_bounds__(256, KE == 1 ? ZK_EVAL_WAVES : ZK_EVAL_WAVES_EXT) k_eval_constraints(const fe *lde, int log_n, EvalMap map, const fe *periodic,
-                                                          const fe *divs, const AirConsts *K, const AirConsts *K2,
-                                                          size_t plane, fe *comp) {
-    __shared__ EvalShared S;
+                                                          const fe *divs, const AirConsts *__restrict__ K,
+                                                          const AirConsts *__restrict__ K2, size_t plane,
+                                                          fe *comp) {
+    // (K, K2 __restrict__: nothing the kernel stores aliases the constants, so their loads stay scalar after the
+    // first plane's store; with one plane K2 == K, both only read)
     // lane-private stash of what a later section reads again (the opcode value and the push term the selector section
     // forms from the 5 opcode bits, sponge 7 and 8): an LDS slot instead of a second global load, which missed L2 (PMC:
     // 4.30 GB per launch without, 3.42 with, against 3.52 GB algorithmic; profiles/r04_pmc_traffic_eval_stash.txt).
     // 4 x 256 x 16 B = 16 KiB per block: four 256-thread blocks (16 waves, the register budget's 4 per SIMD) fit a
-    // CU's 160 KiB with room to spare (up to 8 slots would)
+    // CU's 160 KiB with room to spare (up to 8 slots would).  Slot 2 first carries constraint 1's selector-free part
+    // through the selector section.
     __shared__ fe stash[4][256];
     const int tid = threadIdx.x;
-    {
-        // one LDS slot per thread, every range bounded on both sides
-        const int t = threadIdx.x;
-        if (t < 20) S.ct[t] = K->coeff_t[t];
-        else if (t < 42) S.cb[t - 20] = K->coeff_b[t - 20];
-        else if (t == 42) S.bnd1 = K->bnd1;
-        else if (t == 43) S.bnd1b = KE == 2 ? K2->bnd1 : fe_zero();
-        else if (t == 44) S.delta = K->delta;
-        else if (t >= 80 && t < 84) {
-            S.ct3[t - 80] = fe_mul(K->coeff_t[12 + t - 80], ZK_INV3_72);
-            S.nct[t - 80] = fe_neg(K->coeff_t[12 + t - 80]);
-        } else if (KE == 2 && t >= 84 && t < 88) {
-            S.ct3b[t - 84] = fe_mul(K2->coeff_t[12 + t - 84], ZK_INV3_72);
-            S.nctb[t - 84] = fe_neg(K2->coeff_t[12 + t - 84]);
-        }
-        else if (t >= 88 && t < 92) S.u[t - 88] = air_fold_mds(K->coeff_t + 12, t - 88);
-        else if (KE == 2 && t >= 92 && t < 96) S.ub[t - 92] = air_fold_mds(K2->coeff_t + 12, t - 92);
-        else if (KE == 2 && t >= 128 && t < 148) S.ct2[t - 128] = K2->coeff_t[t - 128];
-        else if (KE == 2 && t >= 148 && t < 170) S.cb2[t - 148] = K2->coeff_b[t - 148];
-        __syncthreads();
-    }
     const int L = K->lwe_size;
+    // W set `idx` (EvalWs) of plane a / b.  wo is zero, but laundered by ZK_SEQK between sections: a scalar load is
+    // addressed through it, so it cannot be issued before the section that uses it
+    int wo = 0;
+#define ZK_WA(idx) load_fe_ws(K->ws, wo + (idx))
+#define ZK_WB(idx) load_fe_ws(K2->ws, wo + (idx))
     const size_t n = (size_t)1 << log_n;
     const size_t CE = n * map.nce;
     // thread t -> local CE coset jl = t / n, position q = t % n (a wave reads 64 consecutive positions of
@@ -1639,14 +1633,20 @@ __global__ void __launch_bounds__(256, KE == 1 ? ZK_EVAL_WAVES : ZK_EVAL_WAVES_E
     const fe one = fe_one();
     fe t = fe_zero();  // sum of coeff_t[k] * C_k (kept reduced: a lazy 288-bit sum here costs 130 spills)
     fe t2 = fe_zero();  // the b-plane sum (KE = 2)
-#define ZK_ACC(k, val)                                                    \
-    do {                                                                  \
-        const fe v_ = (val);                                              \
-        t = fe_add(t, fe_mul(S.ct[k], v_));                               \
-        if (KE == 2) {                                                    \
-            t2 = fe_add(t2, fe_mul(S.ct2[k], v_));                        \
-            asm volatile("" : "+v"(t2.lo), "+v"(t2.hi));                  \
-        }                                                                 \
+    // the row pointer and the W-set offset of the next section wait for `dep`, a value of the section before it
+#define ZK_SEQK(dep)                            \
+    do {                                        \
+        ZK_SEQ(cb, dep);                        \
+        asm volatile("" : "+s"(wo) : "v"(dep)); \
+    } while (0)
+#define ZK_ACC(k, val)                                                        \
+    do {                                                                      \
+        const fe v_ = (val);                                                  \
+        t = fe_add(t, fe_mul_uniform(v_, ZK_WA(EW_CT + (k))));                \
+        if (KE == 2) {                                                        \
+            t2 = fe_add(t2, fe_mul_uniform(v_, ZK_WB(EW_CT + (k))));          \
+            asm volatile("" : "+v"(t2.lo), "+v"(t2.hi));                      \
+        }                                                                     \
     } while (0)
     // 0..11 first: degree-5 selectors (flags.rs:45-79) with shared prefixes, each consumed right away.  The Rescue
     // section after it needs only the opcode value and s0' is_push from the flags, and is_push is one more factor on
@@ -1660,12 +1660,12 @@ __global__ void __launch_bounds__(256, KE == 1 ? ZK_EVAL_WAVES : ZK_EVAL_WAVES_E
     {
         constexpr bool LZ = KE == 1 && ZK_EVAL_LAZY;
         acc288 aS = acc288_zero();
-#define ZK_ACCS(k, val)                                  \
-    do {                                                 \
-        if (LZ) acc288_madd(aS, S.ct[k], (val));    \
-        else ZK_ACC(k, val);                             \
+#define ZK_ACCS(k, val)                                                 \
+    do {                                                                \
+        if (LZ) acc288_madd_uniform(aS, (val), ZK_WA(EW_CT + (k)));     \
+        else ZK_ACC(k, val);                                            \
     } while (0)
-#define ZK_SEQS() ZK_SEQ(cb, LZ ? aS.w[0] : (uint32_t)t.lo)
+#define ZK_SEQS() ZK_SEQK(LZ ? aS.w[0] : (uint32_t)t.lo)
         const fe b0 = CUR(5), b1 = CUR(4), b2 = CUR(3), b3 = CUR(2), b4 = CUR(1);
         {
             // opcode = 16 b0 + 8 b1 + 4 b2 + 2 b3 + b4  (Horner by doubling: bits are field elements)
@@ -1682,31 +1682,40 @@ __global__ void __launch_bounds__(256, KE == 1 ? ZK_EVAL_WAVES : ZK_EVAL_WAVES_E
         // 0 clock, 2 shift
         ZK_ACCS(0, fe_sub(NXT(0), fe_add(CUR(0), one)));
         const fe b01 = fe_mul(b0, b1);
+        // constraint 1's part that needs neither selector, d' - d - shr + shl: parked in a stash slot the Rescue section
+        // fills only later, instead of four registers (or b0 and b1) across the whole section
+        stash[2][tid] = fe_add(fe_sub(NXT(11), CUR(11)), fe_sub(b1, b0));
         ZK_ACCS(2, b01);
         const fe b0n1 = fe_sub(b0, b01);   // b0 (1-b1)
         const fe n0_1 = fe_sub(b1, b01);   // (1-b0) b1
         const fe n01 = fe_sub(nb0, n0_1);  // (1-b0)(1-b1)
+        const fe n34 = fe_mul(nb3, nb4);  // (1-b3)(1-b4): noop and smul
         // 11 noop
         {
-            const fe is_noop = fe_mul(fe_mul(fe_mul(n01, nb2), nb3), nb4);
+            const fe is_noop = fe_mul(fe_mul(n01, nb2), n34);
             ZK_ACCS(11, fe_mul(is_noop, fe_sub(s0n, s0)));
         }
         ZK_SEQS();
+        // the prefixes the later blocks need, formed here so that their factors (b0n1, nb2, nb3, n0_1_b2) are not live
+        // across the section's widest point, the 256-bit product of constraints 3 / 6
+        const fe p0 = fe_mul(b0n1, nb2);  // b0 (1-b1)(1-b2): push / read
         const fe n0_1_b2 = fe_mul(n0_1, b2);
         const fe n0_1_n2 = fe_sub(n0_1, n0_1_b2);
+        const fe is_smul = fe_mul(n0_1_b2, n34);
         const fe Y = fe_mul(n0_1_n2, b3);  // (1-b0) b1 (1-b2) b3
         fe is_add2, is_read2;
         {
             // 3 add, 6 mul: X = (1-b0) b1 (1-b2)(1-b3)
             const fe X = fe_sub(n0_1_n2, Y);
-            const fe e3 = fe_mul(S.ct[3], fe_sub(s0n, fe_add(s0, s1)));
-            const fe e6 = fe_mul(S.ct[6], fe_sub(s0n, fe_mul(s0, s1)));
+            const fe d3 = fe_sub(s0n, fe_add(s0, s1)), d6 = fe_sub(s0n, fe_mul(s0, s1));
+            const fe e3 = fe_mul_uniform(d3, ZK_WA(EW_CT + 3));
+            const fe e6 = fe_mul_uniform(d6, ZK_WA(EW_CT + 6));
             const fe i36 = fe_add(e3, fe_mul(b4, fe_sub(e6, e3)));
             if (LZ) acc288_madd(aS, X, i36);
             else t = fe_add(t, fe_mul(X, i36));
             if (KE == 2) {
-                const fe f3 = fe_mul(S.ct2[3], fe_sub(s0n, fe_add(s0, s1)));
-                const fe f6 = fe_mul(S.ct2[6], fe_sub(s0n, fe_mul(s0, s1)));
+                const fe f3 = fe_mul_uniform(d3, ZK_WB(EW_CT + 3));
+                const fe f6 = fe_mul_uniform(d6, ZK_WB(EW_CT + 6));
                 t2 = fe_add(t2, fe_mul(X, fe_add(f3, fe_mul(b4, fe_sub(f6, f3)))));
                 asm volatile("" : "+v"(t2.lo), "+v"(t2.hi));
             }
@@ -1716,7 +1725,6 @@ __global__ void __launch_bounds__(256, KE == 1 ? ZK_EVAL_WAVES : ZK_EVAL_WAVES_E
             // 4 sadd / 5 add2 / 7 smul over the lwe_size ciphertext limbs (fhe/src/server_key.rs:89-124)
             is_add2 = fe_mul(Y, b4);
             const fe is_sadd = fe_sub(Y, is_add2);
-            const fe is_smul = fe_mul(fe_mul(n0_1_b2, nb3), nb4);
             // Three column sums carry all three constraints (exact regrouping of the per-limb terms):
             //   4: sum_k (sn_k - s1_k) - delta s0           = sum_sn - sum_s1 - delta s0
             //   5: sum_k (sn_k - s_k - s_(L+k))             = sum_sn - sum_s1 - s0 - sum_hi
@@ -1730,7 +1738,8 @@ __global__ void __launch_bounds__(256, KE == 1 ? ZK_EVAL_WAVES : ZK_EVAL_WAVES_E
             for (int k = 1; k < L; k++) sum_hi = fe_add(sum_hi, CUR(12 + L + k));
             const fe base = fe_sub(sum_sn, sum_s1);
             const fe acc7 = fe_sub(sum_sn, fe_mul(sum_s1, s0));
-            const fe acc4 = fe_sub(base, fe_mul(S.delta, s0));  // encrypt_trivial body delta * s0 in limb L-1
+            // encrypt_trivial body delta * s0 in limb L-1
+            const fe acc4 = fe_sub(base, fe_mul_uniform(s0, ZK_WA(EW_DELTA)));
             const fe acc5 = fe_sub(base, fe_add(s0, sum_hi));
             ZK_ACCS(4, fe_mul(is_sadd, acc4));
             ZK_ACCS(5, fe_mul(is_add2, acc5));
@@ -1739,25 +1748,25 @@ __global__ void __launch_bounds__(256, KE == 1 ? ZK_EVAL_WAVES : ZK_EVAL_WAVES_E
         ZK_SEQS();
         {
             // 8 push / 9 read / 10 read2
-            const fe p0 = fe_mul(b0n1, nb2);     // b0 (1-b1)(1-b2)
             const fe p0b3 = fe_mul(p0, b3);
             const fe p0n3 = fe_sub(p0, p0b3);
             // is_push = b0 (1-b1)(1-b2)(1-b3)(1-b4) = p0n3 (1-b4)  (flags.rs); constraint 13's s0' is_push
             stash[1][tid] = fe_mul(s0n, fe_mul(p0n3, nb4));
             is_read2 = fe_mul(p0b3, nb4);
             const fe zd1 = fe_mul(p0n3, fe_sub(NXT(13), s0));
-            const fe i89 = fe_add(S.ct[8], fe_mul(b4, fe_sub(S.ct[9], S.ct[8])));
+            // ct8 + b4 (ct9 - ct8): the difference is a constant of the proof (EW_D89)
+            const fe i89 = fe_add(K->coeff_t[8], fe_mul_uniform(b4, ZK_WA(EW_D89)));
             if (LZ) acc288_madd(aS, zd1, i89);
             else t = fe_add(t, fe_mul(zd1, i89));
             if (KE == 2) {
-                t2 = fe_add(t2, fe_mul(zd1, fe_add(S.ct2[8], fe_mul(b4, fe_sub(S.ct2[9], S.ct2[8])))));
+                t2 = fe_add(t2, fe_mul(zd1, fe_add(K2->coeff_t[8], fe_mul_uniform(b4, ZK_WB(EW_D89)))));
                 asm volatile("" : "+v"(t2.lo), "+v"(t2.hi));
             }
             ZK_ACCS(10, fe_mul(is_read2, fe_sub(NXT(17), s0)));
         }
         // 1 depth: (d' - d - shr + shl) - 4 read2 + 4 add2   (x4 as two doublings)
         {
-            fe v = fe_add(fe_sub(fe_sub(NXT(11), CUR(11)), b0), b1);
+            const fe v = stash[2][tid];
             fe d = fe_sub(is_add2, is_read2);
             d = fe_add(d, d);
             d = fe_add(d, d);
@@ -1767,36 +1776,32 @@ __global__ void __launch_bounds__(256, KE == 1 ? ZK_EVAL_WAVES : ZK_EVAL_WAVES_E
 #undef ZK_ACCS
 #undef ZK_SEQS
     }
-    ZK_SEQ(cb, t.lo);
+    ZK_SEQK(t.lo);
     // 12..19 Rescue round / copy (constrains.rs:182-216)
     {
         const fe opc = stash[0][tid], push_term = stash[1][tid];
         const fe *per = periodic + (i & 127) * 9;
         // 12..15 are ct_r ((INV_MDS y)_r^3 - m0_r) with m0_r = (MDS x)_r + ark_r, + opc for r = 0, + push_term for r = 1.
         // The m0 half is linear in the cubes x: sum_r (-ct_r) m0_r = sum_k u_k x_k + pv[i mod 128] - ct_0 opc - ct_1 push_term
-        // (u and pv folded per proof: air_fold_mds, AirConsts::pv), summed lazily from pv on -- no MDS row per step
-        acc288 aR = acc288_zero(), aR2 = acc288_zero();
-        {
-            const fe pv = K->pv[i & 127];
-            aR.w[0] = lo32(pv.lo), aR.w[1] = hi32(pv.lo), aR.w[2] = lo32(pv.hi), aR.w[3] = hi32(pv.hi);
-            acc288_madd(aR, S.nct[0], opc);
-            acc288_madd(aR, S.nct[1], push_term);
-            if (KE == 2) {
-                const fe pvb = K2->pv[i & 127];
-                aR2.w[0] = lo32(pvb.lo), aR2.w[1] = hi32(pvb.lo), aR2.w[2] = lo32(pvb.hi), aR2.w[3] = hi32(pvb.hi);
-                acc288_madd(aR2, S.nctb[0], opc);
-                acc288_madd(aR2, S.nctb[1], push_term);
-            }
+        // (u and pv folded per proof: air_fold_mds, AirConsts::pv), summed lazily from pv on -- no MDS row per step.
+        // Every multiplier of the sum is a constant of the proof: ten W-set terms on top of pv, a 192-bit sum (acc192)
+        acc192 aR = acc192_from(K->pv[i & 127]), aR2 = acc192_zero();
+        acc192_madd_uniform(aR, opc, ZK_WA(EW_NCT + 0));
+        acc192_madd_uniform(aR, push_term, ZK_WA(EW_NCT + 1));
+        if (KE == 2) {
+            aR2 = acc192_from(K2->pv[i & 127]);
+            acc192_madd_uniform(aR2, opc, ZK_WB(EW_NCT + 0));
+            acc192_madd_uniform(aR2, push_term, ZK_WB(EW_NCT + 1));
         }
 #pragma unroll
         for (int k = 0; k < 4; k++) {
             const fe c = CUR(7 + k);
             if (k < 2) stash[2 + k][tid] = c;
             const fe x = cube(c);
-            acc288_madd(aR, S.u[k], x);
-            if (KE == 2) acc288_madd(aR2, S.ub[k], x);
+            acc192_madd_uniform(aR, x, ZK_WA(EW_U + k));
+            if (KE == 2) acc192_madd_uniform(aR2, x, ZK_WB(EW_U + k));
         }
-        ZK_SEQ(cb, aR.w[0]);
+        ZK_SEQK(aR.w[0]);
         const fe h0 = CUR(6);
         const fe fh = fe_mul(per[0], h0);
         const fe nfh = fe_sub(h0, fh);  // (1 - hash_flag) * h0
@@ -1811,35 +1816,35 @@ __global__ void __launch_bounds__(256, KE == 1 ? ZK_EVAL_WAVES : ZK_EVAL_WAVES_E
 #pragma unroll
             for (int r2 = 0; r2 < 4; r2++) {
                 const fe v3 = cube(adj_row(r2, y));
-                acc288_madd(aR, S.ct3[r2], v3);
-                if (KE == 2) acc288_madd(aR2, S.ct3b[r2], v3);
+                acc192_madd_uniform(aR, v3, ZK_WA(EW_CT + 12 + r2));
+                if (KE == 2) acc192_madd_uniform(aR2, v3, ZK_WB(EW_CT + 12 + r2));
             }
-            sR = acc288_reduce(aR);
-            if (KE == 2) sR2 = acc288_reduce(aR2);
+            sR = acc192_reduce(aR);
+            if (KE == 2) sR2 = acc192_reduce(aR2);
         }
         t = fe_add(t, fe_mul(sR, fh));
         if (KE == 2) t2 = fe_add(t2, fe_mul(sR2, fh));
-        ZK_SEQ(cb, t.lo);
+        ZK_SEQK(t.lo);
         {
             const fe c7 = stash[2][tid], c8 = stash[3][tid];
             const fe d16 = fe_sub(NXT(7), c7), d17 = fe_sub(NXT(8), c8), n9 = NXT(9), n10 = NXT(10);
-            acc288 aC = acc288_zero();
-            acc288_madd(aC, S.ct[16], d16);
-            acc288_madd(aC, S.ct[17], d17);
-            acc288_madd(aC, S.ct[18], n9);
-            acc288_madd(aC, S.ct[19], n10);
-            t = fe_add(t, fe_mul(acc288_reduce(aC), nfh));
+            acc192 aC = acc192_zero();
+            acc192_madd_uniform(aC, d16, ZK_WA(EW_CT + 16));
+            acc192_madd_uniform(aC, d17, ZK_WA(EW_CT + 17));
+            acc192_madd_uniform(aC, n9, ZK_WA(EW_CT + 18));
+            acc192_madd_uniform(aC, n10, ZK_WA(EW_CT + 19));
+            t = fe_add(t, fe_mul(acc192_reduce(aC), nfh));
             if (KE == 2) {
-                acc288 aD = acc288_zero();
-                acc288_madd(aD, S.ct2[16], d16);
-                acc288_madd(aD, S.ct2[17], d17);
-                acc288_madd(aD, S.ct2[18], n9);
-                acc288_madd(aD, S.ct2[19], n10);
-                t2 = fe_add(t2, fe_mul(acc288_reduce(aD), nfh));
+                acc192 aD = acc192_zero();
+                acc192_madd_uniform(aD, d16, ZK_WB(EW_CT + 16));
+                acc192_madd_uniform(aD, d17, ZK_WB(EW_CT + 17));
+                acc192_madd_uniform(aD, n9, ZK_WB(EW_CT + 18));
+                acc192_madd_uniform(aD, n10, ZK_WB(EW_CT + 19));
+                t2 = fe_add(t2, fe_mul(acc192_reduce(aD), nfh));
             }
         }
     }
-    ZK_SEQ(cb, t.lo);
+    ZK_SEQK(t.lo);
     // divisors (per-row factors from divisor_tables): transition (x^n - 1)/((x - g^(n-2))(x - g^(n-1)));
     // boundary groups (x - 1) and (x - g^(n-2)).  res = t dT + bs0 d0 + bs1 d1 as one lazy sum.
     const size_t P = map.dplane ? map.dplane : CE;
@@ -1851,21 +1856,26 @@ __global__ void __launch_bounds__(256, KE == 1 ? ZK_EVAL_WAVES : ZK_EVAL_WAVES_E
         const fe d0 = divs[P + t_id], d1 = divs[2 * P + t_id];
         // assertions (air/src/lib.rs:170-195), sorted: step 0 -> cols 0,7,8,11,12..19 (value 0);
         // step n-2 -> cols 7,8 (program hash), 12..19 (outputs)
-        acc288 a0 = acc288_zero(), a1 = acc288_zero();
-        acc288_madd(a0, S.cb[0], CUR(0));
-        acc288_madd(a0, S.cb[1], CUR(7));
-        acc288_madd(a0, S.cb[2], CUR(8));
-        acc288_madd(a0, S.cb[3], CUR(11));
-        acc288_madd(a1, S.cb[12], CUR(7));
-        acc288_madd(a1, S.cb[13], CUR(8));
+        // (every multiplier a constant of the proof: two 192-bit sums of 12 and 10 W-set terms)
+        auto bnd_sums = [&](const AirConsts *__restrict__ Kp, fe &bs0, fe &bs1) {
+            acc192 a0 = acc192_zero(), a1 = acc192_zero();
+            acc192_madd_uniform(a0, CUR(0), load_fe_ws(Kp->ws, wo + EW_CB + 0));
+            acc192_madd_uniform(a0, CUR(7), load_fe_ws(Kp->ws, wo + EW_CB + 1));
+            acc192_madd_uniform(a0, CUR(8), load_fe_ws(Kp->ws, wo + EW_CB + 2));
+            acc192_madd_uniform(a0, CUR(11), load_fe_ws(Kp->ws, wo + EW_CB + 3));
+            acc192_madd_uniform(a1, CUR(7), load_fe_ws(Kp->ws, wo + EW_CB + 12));
+            acc192_madd_uniform(a1, CUR(8), load_fe_ws(Kp->ws, wo + EW_CB + 13));
 #pragma unroll
-        for (int k = 0; k < 8; k++) {
-            fe c = CUR(12 + k);
-            acc288_madd(a0, S.cb[4 + k], c);
-            acc288_madd(a1, S.cb[14 + k], c);
-        }
-        // sum_k cb[12+k] (c_k - v_k) = sum_k cb[12+k] c_k - bnd1 (bnd1 precomputed on the host)
-        const fe bs0 = acc288_reduce(a0), bs1 = fe_sub(acc288_reduce(a1), S.bnd1);
+            for (int k = 0; k < 8; k++) {
+                const fe c = CUR(12 + k);
+                acc192_madd_uniform(a0, c, load_fe_ws(Kp->ws, wo + EW_CB + 4 + k));
+                acc192_madd_uniform(a1, c, load_fe_ws(Kp->ws, wo + EW_CB + 14 + k));
+            }
+            // sum_k cb[12+k] (c_k - v_k) = sum_k cb[12+k] c_k - bnd1 (bnd1 precomputed on the host)
+            bs0 = acc192_reduce(a0), bs1 = fe_sub(acc192_reduce(a1), Kp->bnd1);
+        };
+        fe bs0, bs1;
+        bnd_sums(K, bs0, bs1);
         acc288 aR = acc288_zero();
         acc288_madd(aR, t, dT);
         acc288_madd(aR, bs0, d0);
@@ -1873,21 +1883,9 @@ __global__ void __launch_bounds__(256, KE == 1 ? ZK_EVAL_WAVES : ZK_EVAL_WAVES_E
         const fe res = acc288_reduce(aR);
         comp[t_id] = res;
         if (KE == 2) {
-            ZK_SEQ(cb, res.lo);
-            acc288 c0 = acc288_zero(), c1 = acc288_zero();
-            acc288_madd(c0, S.cb2[0], CUR(0));
-            acc288_madd(c0, S.cb2[1], CUR(7));
-            acc288_madd(c0, S.cb2[2], CUR(8));
-            acc288_madd(c0, S.cb2[3], CUR(11));
-            acc288_madd(c1, S.cb2[12], CUR(7));
-            acc288_madd(c1, S.cb2[13], CUR(8));
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-                fe c = CUR(12 + k);
-                acc288_madd(c0, S.cb2[4 + k], c);
-                acc288_madd(c1, S.cb2[14 + k], c);
-            }
-            const fe bs0b = acc288_reduce(c0), bs1b = fe_sub(acc288_reduce(c1), S.bnd1b);
+            ZK_SEQK(res.lo);
+            fe bs0b, bs1b;
+            bnd_sums(K2, bs0b, bs1b);
             acc288 aR2 = acc288_zero();
             acc288_madd(aR2, t2, dT);
             acc288_madd(aR2, bs0b, d0);
@@ -1895,6 +1893,9 @@ __global__ void __launch_bounds__(256, KE == 1 ? ZK_EVAL_WAVES : ZK_EVAL_WAVES_E
             comp[plane + t_id] = acc288_reduce(aR2);
         }
     }
+#undef ZK_SEQK
+#undef ZK_WA
+#undef ZK_WB
 #undef ZK_ACC
 #undef CUR
 #undef NXT
@@ -2138,9 +2139,14 @@ hipError_t validate_trace(hipStream_t st, const fe *trace, size_t n, const fe *p
 }
 
 // ================================================================ composition interpolation (K4)
+// The launch-uniform multipliers as W sets in the kernel arguments (scalar loads): the 8-point DFT's twiddles w8^-1,
+// w8^-2, w8^-3, the step 3^-n between a coefficient's blocks, and the derived coset's weights CrossMap::k7
+struct CrossWs {
+    fe_ws w1, w2, w3, inv3n, k7[7];
+};
 __global__ void __launch_bounds__(256) k_comp_cross(CrossMap m, const fe *wi_lo, const fe *wi_hi,
-                                                    const fe *i3_lo, const fe *i3_hi, fe scale, fe w8inv,
-                                                    fe inv3n, int ncols, fe *polys, unsigned *nonzero) {
+                                                    const fe *i3_lo, const fe *i3_hi, fe scale, CrossWs cw,
+                                                    int ncols, fe *polys, unsigned *nonzero) {
     for (size_t kl = blockIdx.x * (size_t)blockDim.x + threadIdx.x; kl < m.kcount; kl += (size_t)gridDim.x * blockDim.x) {
         const size_t k1 = m.k0 + kl;
         // d_r = c_r[k1] * w_8n^(-r k1)
@@ -2151,10 +2157,10 @@ __global__ void __launch_bounds__(256) k_comp_cross(CrossMap m, const fe *wi_lo,
         for (int r = 0; r < 8; r++) {
             if (r == 7 && m.derive7) {
                 // the unevaluated coset: b_7 = 0 for a composition of degree < 7n (CrossMap::derive7)
-                acc288 a7 = acc288_zero();
+                acc192 a7 = acc192_zero();
 #pragma unroll
-                for (int j = 0; j < 7; j++) acc288_madd(a7, m.k7[j], d[j]);
-                d[7] = acc288_reduce(a7);
+                for (int j = 0; j < 7; j++) acc192_madd_uniform(a7, d[j], cw.k7[j]);
+                d[7] = acc192_reduce(a7);
                 break;
             }
             fe v = m.c[r][kl];
@@ -2162,18 +2168,17 @@ __global__ void __launch_bounds__(256) k_comp_cross(CrossMap m, const fe *wi_lo,
             wr = fe_mul(wr, w);
         }
         // b_k2 = sum_r w8^(-r k2) d_r  (size-8 DFT with w8^-1, direct form: 49 products avoided by radix-2)
-        fe w2 = fe_mul(w8inv, w8inv), w3 = fe_mul(w2, w8inv);
         // radix-2 DIT on bit-reversed input
         fe e0 = d[0], e1 = d[4], e2 = d[2], e3 = d[6], e4 = d[1], e5 = d[5], e6 = d[3], e7 = d[7];
         fe t0 = fe_add(e0, e1), t1 = fe_sub(e0, e1), t2 = fe_add(e2, e3), t3 = fe_sub(e2, e3);
         fe t4 = fe_add(e4, e5), t5 = fe_sub(e4, e5), t6 = fe_add(e6, e7), t7 = fe_sub(e6, e7);
-        t3 = fe_mul(t3, w2);
-        t7 = fe_mul(t7, w2);
+        t3 = fe_mul_uniform(t3, cw.w2);
+        t7 = fe_mul_uniform(t7, cw.w2);
         fe u0 = fe_add(t0, t2), u2 = fe_sub(t0, t2), u1 = fe_add(t1, t3), u3 = fe_sub(t1, t3);
         fe u4 = fe_add(t4, t6), u6 = fe_sub(t4, t6), u5 = fe_add(t5, t7), u7 = fe_sub(t5, t7);
-        u5 = fe_mul(u5, w8inv);
-        u6 = fe_mul(u6, w2);
-        u7 = fe_mul(u7, w3);
+        u5 = fe_mul_uniform(u5, cw.w1);
+        u6 = fe_mul_uniform(u6, cw.w2);
+        u7 = fe_mul_uniform(u7, cw.w3);
         fe bk[8] = {fe_add(u0, u4), fe_add(u1, u5), fe_add(u2, u6), fe_add(u3, u7),
                     fe_sub(u0, u4), fe_sub(u1, u5), fe_sub(u2, u6), fe_sub(u3, u7)};
         // a_(k1 + n k2) = b_k2 * scale * 3^-(k1 + n k2)
@@ -2184,7 +2189,7 @@ __global__ void __launch_bounds__(256) k_comp_cross(CrossMap m, const fe *wi_lo,
             fe a = fe_mul(bk[k2], s);
             if (k2 < ncols) polys[(size_t)k2 * m.pstride + kl] = a;
             else nz |= !fe_is_zero(a);
-            s = fe_mul(s, inv3n);
+            s = fe_mul_uniform(s, cw.inv3n);
         }
         if (nz) atomicOr(nonzero, 1u);
     }
@@ -2194,8 +2199,13 @@ void comp_cross_mapped(hipStream_t st, const CrossMap &m, const NttTables &T8n, 
                        fe w8inv, fe inv3n, int ncols, fe *polys, unsigned *nonzero_flag) {
     unsigned blocks = cdiv(m.kcount, 256);
     if (blocks > 65536) blocks = 65536;
+    CrossWs cw;
+    const fe w2 = fe_mul(w8inv, w8inv);
+    cw.w1 = make_fe_ws(w8inv), cw.w2 = make_fe_ws(w2), cw.w3 = make_fe_ws(fe_mul(w2, w8inv));
+    cw.inv3n = make_fe_ws(inv3n);
+    for (int j = 0; j < 7; j++) cw.k7[j] = make_fe_ws(m.k7[j]);
     ZK_PROF(st, "comp_cross", (128.0 + 16.0 * ncols) * m.kcount, hipLaunchKernelGGL(k_comp_cross, dim3(blocks), dim3(256), 0, st, m, T8n.inv_lo,
-                                                 T8n.inv_hi, inv3.lo, inv3.hi, scale, w8inv, inv3n, ncols, polys,
+                                                 T8n.inv_hi, inv3.lo, inv3.hi, scale, cw, ncols, polys,
                                                  nonzero_flag));
 }
 
@@ -2974,6 +2984,32 @@ __global__ void k_field_op(int op, const fe *a, const fe *b, fe *out, size_t cou
         fe o[2];
         ws_fold2(A, lo32(y.lo), hi32(y.lo) & 7u, B, lo32(y2.lo), hi32(y2.lo) & 7u, o[0], o[1]);
         r = o[t & 1];
+        break;
+    }
+    // ---- the lazy sums of W-set products (f128.hpp acc192 / acc288_madd_uniform), W the W set of b[w0]:
+    // 18: a[t] + sum_(j < 16) a[(t + j) mod count] b[w0] in 192 bits; 19: a[t] b[t] (a 256-bit product) + the same 16
+    // terms in 288 bits; 20: a[t] + ACC192_MAX_TERMS times a[t] b[w0], the most terms acc192 takes
+    case 18:
+    case 19: {
+        const fe_ws Wc = load_fe_ws(ws, (int)w0);
+        acc192 s = acc192_from(x);
+        acc288 s2 = acc288_zero();
+        if (op == 19) acc288_madd(s2, x, y);
+#pragma unroll 1
+        for (int j = 0; j < 16; j++) {
+            const fe v = a[(t + j) % count];
+            if (op == 18) acc192_madd_uniform(s, v, Wc);
+            else acc288_madd_uniform(s2, v, Wc);
+        }
+        r = op == 18 ? acc192_reduce(s) : acc288_reduce(s2);
+        break;
+    }
+    case 20: {
+        const fe_ws Wc = load_fe_ws(ws, (int)w0);
+        acc192 s = acc192_from(x);
+#pragma unroll 1
+        for (int j = 0; j < ACC192_MAX_TERMS; j++) acc192_madd_uniform(s, x, Wc);
+        r = acc192_reduce(s);
         break;
     }
     case 0: r = fe_add(x, y); break;

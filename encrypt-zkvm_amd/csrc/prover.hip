@@ -825,12 +825,13 @@ Coin zk::seed_coin(size_t n, const zk_options *opt, const zk_pub_inputs *pub) {
     return coin;
 }
 
-// what a plane's constants derive from its own coefficients: bnd1 and the folded round constants pv
-// (per: the periodic columns over the CE steps, periodic_table(n))
+// what a plane's constants derive from its own coefficients (and delta): bnd1, the folded round constants pv
+// (per: the periodic columns over the CE steps, periodic_table(n)) and the evaluator's W sets
 static void set_coeff_derived(AirConsts &K, const fe *per) {
     K.bnd1 = fe_zero();
     for (int k = 12; k < NUM_ASSERTS; k++) K.bnd1 = fe_add(K.bnd1, fe_mul(K.coeff_b[k], K.assert_val[k]));
     air_fold_periodic(K.coeff_t + 12, per, K.pv);
+    air_build_ws(K);
 }
 
 // assertions (air/src/lib.rs:170-195) sorted by (stride, first_step, column) [P3]; CE-coset constants
@@ -2128,6 +2129,17 @@ extern "C" void zk_diag_air_fold_host(const uint8_t *ct, size_t n, uint8_t *u_ou
     air_fold_periodic(c, per.data(), pv);
     for (int j = 0; j < 128; j++) fe_to_bytes(pv[j], pv_out + 16 * j);
 }
+// Host: the evaluator's W sets (AirConsts::ws, air_build_ws) of the coefficients ct[20], cb[22] and delta (16 bytes
+// each): out = EW_COUNT sets of 64 bytes in EvalWs order
+extern "C" void zk_diag_air_ws_host(const uint8_t *ct, const uint8_t *cb, const uint8_t *delta, uint8_t *out) {
+    AirConsts K;
+    memset(&K, 0, sizeof K);
+    for (int k = 0; k < NUM_TCONS; k++) K.coeff_t[k] = fe_from_bytes(ct + 16 * k);
+    for (int k = 0; k < NUM_ASSERTS; k++) K.coeff_b[k] = fe_from_bytes(cb + 16 * k);
+    K.delta = fe_from_bytes(delta);
+    air_build_ws(K);
+    memcpy(out, K.ws, sizeof K.ws);
+}
 extern "C" void zk_diag_blake3_host(const uint8_t *in, size_t len, uint8_t out[32]) { b3::hash_bytes(in, len, out); }
 
 // Host: the upload plan of a host-trace commitment (upload_plan.hpp).  in[13] = have, sparse, nw8, nw32, clk_off,
@@ -2213,14 +2225,16 @@ extern "C" int zk_diag_shard_locate(uint64_t M, int G, int is_node, const uint64
 // make_fe_w2 and uploaded as a table: 11 fe_mul_uniform (the constant of the first element of each 64-element wave),
 // 12 fe_mul_wsv, 13 fe_mul_uniform2 (count a multiple of 64), 14 fe_mul_wsv2, 15 fe_mul_w2_2; 16 / 17 the raw final
 // reductions ws_fold / ws_fold2 of a + (b mod 2^35) 2^128.  The pairing of the two-output forms: kernels.hip k_field_op.
+// 18 .. 20: the lazy sums of W-set products (acc192_madd_uniform, acc288_madd_uniform), the constant as in 11; their
+// terms: kernels.hip k_field_op.
 extern "C" int zk_diag_field_op(int device, int op, const uint8_t *a, const uint8_t *b, uint8_t *out, size_t count) {
     if (!a || !b || !out || count == 0) ZK_FAIL(ZK_ERR_INVALID_ARG, "null argument");
-    if (op < 0 || op > 17 || count > ((size_t)1 << 30) || (op == 13 && count % 64 != 0))
+    if (op < 0 || op > 20 || count > ((size_t)1 << 30) || (op == 13 && count % 64 != 0))
         ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_field_op: unknown op, or a count the op does not take");
     ZK_CHECK_HIP(hipSetDevice(device));
     std::vector<fe_ws> ws;
     std::vector<fe_w2> w2;
-    if (op >= 11 && op <= 14) {
+    if ((op >= 11 && op <= 14) || op >= 18) {
         ws.resize(count);
         for (size_t i = 0; i < count; i++) ws[i] = make_fe_ws(fe_from_bytes(b + 16 * i));
     } else if (op == 15) {

@@ -279,7 +279,17 @@ struct AirConsts {
     // pv[j] = sum_r (-coeff_t[12+r]) periodic[j][1+r] over the 128 CE steps j = i mod 128: the round constants' share
     // of constraints 12..15, folded with this plane's coefficients (air_fold_periodic)
     fe pv[128];
+    // W sets (f128.hpp make_fe_ws) of every launch-uniform multiplier of k_eval_constraints, read there by scalar
+    // loads; built by air_build_ws once the coefficients are set.  Indices: EvalWs.
+    fe_ws ws[50];
 };
+// AirConsts::ws[...]: EW_CT + k = coeff_t[k], but for k = 12..15 coeff_t[k] 3^-72 (the adjugate path's cubes carry
+// 3^72); EW_NCT + r = -coeff_t[12 + r], r < 2 (the opcode and push terms); EW_U + k = air_fold_mds(coeff_t + 12, k);
+// EW_D89 = coeff_t[9] - coeff_t[8]; EW_DELTA = delta; EW_CB + k = coeff_b[k]
+enum EvalWs { EW_CT = 0, EW_NCT = 20, EW_U = 22, EW_D89 = 26, EW_DELTA = 27, EW_CB = 28, EW_COUNT = 50 };
+static_assert(EW_COUNT == sizeof(AirConsts::ws) / sizeof(fe_ws), "AirConsts::ws holds one W set per EvalWs index");
+// (kernels.hip, beside the kernel that reads them; needs coeff_t, coeff_b and delta)
+void air_build_ws(AirConsts &K);
 // |MDS| of the Rescue round (crypto/src/rescue.rs:197-214): row r = (-a, +b, -c, +d), every entry below 2^26
 ZK_HD uint32_t mds_abs(int i) {
     constexpr uint32_t M[16] = {729, 1080, 390, 40, 29160, 42471, 14520, 1210,
