@@ -2379,6 +2379,225 @@ extern "C" int zk_diag_lde(int device, const uint8_t *in, size_t n, int ncols, u
     return ZK_OK;
 }
 
+// ---- the front of the trace commitment: the column classes (sparse, the AIR clock, narrow) and what consumes them, each
+// through its production launcher on columns of the caller's choice (tests/test_gpu_trace_classes.py; the reference is
+// tests/trace_classes_ref.py).  Like zk_diag_lde: a prover of its own on `device`, the inputs uploaded into its
+// buffers, the launcher on its stream, the result read back.
+static int diag_class_flags(zk_prover *p) {  // the flag array and the last row, as sparse_begin allocates them; zeroed
+    if (!p->sp_nz) {
+        ZK_CHECK_HIP(p->arena.alloc(&p->sp_nz, 4 * W));
+        ZK_CHECK_HIP(p->arena.alloc(&p->sp_last, W));
+    }
+    ZK_CHECK_HIP(hipMemsetAsync(p->sp_nz, 0, 4 * W * sizeof(unsigned), p->st));
+    ZK_CHECK_HIP(hipMemsetAsync(p->sp_last, 0, W * sizeof(fe), p->st));
+    return ZK_OK;
+}
+
+// Column detection.  ncols columns of n elements are placed as trace columns c0 .. c0 + ncols - 1 (the others zero), the
+// flags zeroed.  how = 0: sparse_detect_rows with wstride = 28 and the clock check on (idoff = 3 * 28), in `parts`
+// launches over the row ranges [k n / parts, (k + 1) n / parts) into the same flags (a sharded rank's share each; parts
+// in {1, 2, 4, 8}, n / parts a multiple of 4096 when parts > 1); n >= 16.  how = 1: the interpolation with
+// SparseCols{fused, col0 = c0, wstride = 28} (four-step sizes: n >= 2^13), its coefficients to polys_out (ncols n).
+// flags_out[4 * 28]: [c] a row before the last is nonzero, [28 + c] a value >= 2^8, [56 + c] a value >= 2^32, [84]
+// column 0 is not the clock (how = 0 only); last_out[28]: the `last` array (how = 0 only writes it).
+extern "C" int zk_diag_detect(int device, const uint8_t *cols, size_t n, int ncols, int c0, int how, int parts,
+                              uint32_t *flags_out, uint8_t *last_out, uint8_t *polys_out) {
+    const bool ok = cols && flags_out && last_out && n >= 16 && !(n & (n - 1)) && n <= ((size_t)1 << 22) && ncols >= 1 &&
+                    c0 >= 0 && c0 + ncols <= W && (how == 0 || (how == 1 && n >= 8192 && polys_out && parts == 1)) &&
+                    (parts == 1 || ((parts == 2 || parts == 4 || parts == 8) && n / parts >= 4096 && n / parts % 4096 == 0));
+    if (!ok)
+        ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_detect: n a power of two in [16, 2^22] (how = 1: from 2^13), columns c0 .. c0 + "
+                                    "ncols - 1 within 28, parts 1, 2, 4 or 8 ranges of a multiple of 4096 rows");
+    zk_prover *p = nullptr;
+    ZK_TRY(zk_prover_create(device, n, 8, &p));
+    std::unique_ptr<zk_prover, void (*)(zk_prover *)> guard(p, zk_prover_destroy);
+    Plan *pl = nullptr;
+    ZK_TRY(get_plan(p, n, 8, &pl));
+    ZK_CHECK_HIP(hipMemsetAsync(p->d_trace, 0, (size_t)W * n * sizeof(fe), p->st));
+    ZK_TRY(diag_class_flags(p));
+    ZK_CHECK_HIP(hipStreamSynchronize(p->st));
+    ZK_CHECK_HIP(hipMemcpy(p->d_trace + (size_t)c0 * n, cols, (size_t)ncols * n * 16, hipMemcpyHostToDevice));
+    SparseCols sp{p->sp_nz, p->sp_last, pl->lagr, pl->lagr_lde, c0};
+    sp.wstride = W;
+    if (how == 0) {
+        sp.id_poly = p->polys;  // (never read by the detection: non-null turns the clock check on)
+        sp.idoff = 3 * W;
+        for (int k = 0; k < parts; k++)
+            sparse_detect_rows(p->st, p->d_trace, n, c0, ncols, sp, (size_t)k * (n / parts), (size_t)(k + 1) * (n / parts));
+    } else {
+        sp.fused = true;
+        const fe inv_n = h_inv(fe_make(n));
+        ntt(p->st, pl->Tn, p->d_trace + (size_t)c0 * n, n, p->polys + (size_t)c0 * n, n, ncols, true, nullptr, &inv_n,
+            p->tmp, &sp);
+    }
+    ZK_CHECK_HIP(hipStreamSynchronize(p->st));
+    ZK_CHECK_HIP(hipMemcpy(flags_out, p->sp_nz, 4 * W * sizeof(unsigned), hipMemcpyDeviceToHost));
+    ZK_CHECK_HIP(hipMemcpy(last_out, p->sp_last, W * 16, hipMemcpyDeviceToHost));
+    if (how == 1)
+        ZK_CHECK_HIP(hipMemcpy(polys_out, p->polys + (size_t)c0 * n, (size_t)ncols * n * 16, hipMemcpyDeviceToHost));
+    return ZK_OK;
+}
+
+// The commitment to a device-resident trace of 28 arbitrary columns (no AIR validity needed): copied into the prover's
+// trace buffer and committed through trace_lde_commit with a device TraceSrc (commit_device: detection, interpolation
+// and coset LDE with the sparse and clock columns skipped in pass 1 and filled in pass 2, row hash, Merkle tree).
+// flags_out[4 * 28] as zk_diag_detect's (this path takes no width flags: they stay 0; all 0 with ZK_SPARSE=0);
+// polys_out: 28 n coefficients; lde_out: 28 blowup n, coset-major
+// (lde[(c blowup + r) n + q]); root_out: the trace root.  n >= 2^13, blowup in {8, 16, 32, 64}.
+extern "C" int zk_diag_trace_commit(int device, const uint8_t *trace, size_t n, uint32_t blowup, uint32_t *flags_out,
+                                    uint8_t *polys_out, uint8_t *lde_out, uint8_t *root_out) {
+    if (!trace || !flags_out || !polys_out || !lde_out || !root_out || n < 8192 || (n & (n - 1)) ||
+        n > ((size_t)1 << 22) || blowup < 8 || blowup > 64 || (blowup & (blowup - 1)))
+        ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_trace_commit: n a power of two in [2^13, 2^22], blowup 8, 16, 32 or 64");
+    zk_prover *p = nullptr;
+    ZK_TRY(zk_prover_create(device, n, blowup, &p));
+    std::unique_ptr<zk_prover, void (*)(zk_prover *)> guard(p, zk_prover_destroy);
+    IoScope io_scope(p);
+    Plan *pl = nullptr;
+    ZK_TRY(get_plan(p, n, blowup, &pl));
+    ZK_CHECK_HIP(hipMemcpy(p->d_trace, trace, (size_t)W * n * 16, hipMemcpyHostToDevice));
+    TraceSrc src;
+    src.dev = p->d_trace;
+    uint8_t root[32];
+    ZK_TRY(trace_lde_commit(p, pl, src, n, root));
+    ZK_TRY(d2h_flush(p));  // the root
+    memset(flags_out, 0, 4 * W * sizeof(unsigned));
+    if (p->tc.sp_used) ZK_CHECK_HIP(hipMemcpy(flags_out, p->sp_nz, 4 * W * sizeof(unsigned), hipMemcpyDeviceToHost));
+    ZK_CHECK_HIP(hipMemcpy(polys_out, p->polys, (size_t)W * n * 16, hipMemcpyDeviceToHost));
+    ZK_CHECK_HIP(hipMemcpy(lde_out, p->lde, (size_t)W * blowup * n * 16, hipMemcpyDeviceToHost));
+    memcpy(root_out, root, 32);
+    return ZK_OK;
+}
+
+// The fills a host trace's hinted columns get, by the calls HostTraceCommit::fill_sparse and derive_clock make: for
+// each run of consecutive columns in sparse_mask, ntt and ntt_lde with SparseCols{all, col0 = run start} (k_sparse_fill);
+// with `clock`, column 0 by axpy_fill from id_poly and lagr, and from id_lde and lagr_lde, d = last[0] - (n - 1).
+// last[28]: the last rows.  Only the named columns are read back, in ascending order: polys_out n, lde_out blowup n
+// (coset-major) elements each.
+extern "C" int zk_diag_column_fills(int device, const uint8_t *last, uint32_t sparse_mask, int clock, size_t n,
+                                    uint32_t blowup, uint8_t *polys_out, uint8_t *lde_out) {
+    if (!last || !polys_out || !lde_out || n < 8192 || (n & (n - 1)) || n > ((size_t)1 << 22) || blowup < 8 ||
+        blowup > 64 || (blowup & (blowup - 1)) || (sparse_mask >> W) || (clock && (sparse_mask & 1u)) ||
+        (!clock && !sparse_mask))
+        ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_column_fills: n a power of two in [2^13, 2^22], blowup 8, 16, 32 or 64, a mask "
+                                    "of the 28 columns, column 0 sparse or the clock but not both");
+    zk_prover *p = nullptr;
+    ZK_TRY(zk_prover_create(device, n, blowup, &p));
+    std::unique_ptr<zk_prover, void (*)(zk_prover *)> guard(p, zk_prover_destroy);
+    IoScope io_scope(p);
+    Plan *pl = nullptr;
+    ZK_TRY(get_plan(p, n, blowup, &pl));
+    SparseCols spc{};
+    const SparseCols *sp = nullptr;
+    ZK_TRY(sparse_begin(p, pl, &spc, &sp));
+    if (!sp) ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_column_fills: the sparse class is switched off (ZK_SPARSE=0)");
+    const size_t B = blowup;
+    fe lastv[W];
+    int named[W], nn = 0, hin[W], nh = 0;
+    for (int c = 0; c < W; c++) {
+        lastv[c] = fe_from_bytes(last + 16 * c);
+        if ((sparse_mask >> c) & 1u) hin[nh++] = c;
+        if (((sparse_mask >> c) & 1u) || (clock && c == 0)) named[nn++] = c;
+    }
+    ZK_TRY(h2d_small(p, p->sp_last, lastv, sizeof lastv));
+    const fe inv_n = h_inv(fe_make(n));
+    ZK_TRY(for_runs(hin, nh, [&](int c0, int nc) {
+        SparseCols g = spc;
+        g.col0 = c0, g.fused = false, g.all = true;
+        const size_t o = (size_t)c0 * n;
+        ntt(p->st, pl->Tn, p->d_trace + o, n, p->polys + o, n, nc, true, nullptr, &inv_n, p->tmp, &g);
+        ntt_lde(p->st, pl->Tn, pl->ct, p->polys + o, n, nc, 0, 1, (int)B, p->lde + o * B, B * n, n, p->tmp, &g);
+        return ZK_OK;
+    }));
+    if (clock) {
+        ZK_TRY(clock_tables(p, pl));
+        const fe_ws d = make_fe_ws(fe_sub(lastv[0], fe_make(n - 1)));
+        axpy_fill(p->st, pl->id_poly, pl->lagr, d, n, p->polys);
+        axpy_fill(p->st, pl->id_lde, pl->lagr_lde, d, B * n, p->lde);
+    }
+    ZK_TRY(d2h_flush(p));
+    for (int k = 0; k < nn; k++) {
+        const size_t c = (size_t)named[k];
+        ZK_CHECK_HIP(hipMemcpy(polys_out + (size_t)k * n * 16, p->polys + c * n, n * 16, hipMemcpyDeviceToHost));
+        ZK_CHECK_HIP(hipMemcpy(lde_out + (size_t)k * B * n * 16, p->lde + c * B * n, B * n * 16, hipMemcpyDeviceToHost));
+    }
+    return ZK_OK;
+}
+
+// expand_narrow on a packed buffer of packed_len bytes: `count` columns, column col[k]'s rows as width[k]-byte integers
+// (1 or 4) at packed + off[k] (off a multiple of 16, off[k] + width[k] n <= packed_len), its last row last[k].
+// out: the count columns of n elements, in col[] order.
+extern "C" int zk_diag_expand_narrow(int device, const uint8_t *packed, size_t packed_len, int count, const int32_t *col,
+                                     const int32_t *width, const uint64_t *off, const uint8_t *last, size_t n,
+                                     uint8_t *out) {
+    bool ok = packed && col && width && off && last && out && count >= 1 && count <= W && n >= 16 && !(n & (n - 1)) &&
+              n <= ((size_t)1 << 22);
+    uint32_t seen = 0;
+    for (int k = 0; ok && k < count; k++) {
+        ok = col[k] >= 0 && col[k] < W && !((seen >> col[k]) & 1u) && (width[k] == 1 || width[k] == 4) &&
+             off[k] % 16 == 0 && off[k] <= packed_len && (size_t)width[k] * n <= packed_len - off[k];
+        if (ok) seen |= 1u << col[k];
+    }
+    if (!ok)
+        ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_expand_narrow: n a power of two in [16, 2^22], 1 .. 28 distinct columns of "
+                                    "width 1 or 4 at 16-byte offsets, each with n rows inside the packed buffer");
+    zk_prover *p = nullptr;
+    ZK_TRY(zk_prover_create(device, n, 8, &p));
+    std::unique_ptr<zk_prover, void (*)(zk_prover *)> guard(p, zk_prover_destroy);
+    uint8_t *d = nullptr;
+    ZK_CHECK_HIP(p->arena.alloc(&d, packed_len));
+    ZK_CHECK_HIP(hipMemcpy(d, packed, packed_len, hipMemcpyHostToDevice));
+    ZK_CHECK_HIP(hipMemsetAsync(p->d_trace, 0, (size_t)W * n * sizeof(fe), p->st));  // (p->st does not wait for stream 0)
+    NarrowCols nc{};
+    nc.count = count;
+    for (int k = 0; k < count; k++) {
+        nc.col[k] = col[k];
+        nc.width[k] = width[k];
+        nc.off[k] = (size_t)off[k];
+        nc.last[k] = fe_from_bytes(last + 16 * k);
+    }
+    expand_narrow(p->st, d, nc, n, p->d_trace);
+    ZK_CHECK_HIP(hipStreamSynchronize(p->st));
+    for (int k = 0; k < count; k++)
+        ZK_CHECK_HIP(hipMemcpy(out + (size_t)k * n * 16, p->d_trace + (size_t)col[k] * n, n * 16, hipMemcpyDeviceToHost));
+    return ZK_OK;
+}
+
+// The host checks of a host column's rows [r0, r1) (no GPU): op 0 pack_rows (width 1 or 4, into dst), 1 zero_rows,
+// 2 clock_rows, 3 same_rows against aux (width 1, 4 or 16).  Returns the check's verdict, 0 or 1.
+extern "C" int zk_diag_host_rows(int op, const uint8_t *col, const uint8_t *aux, size_t r0, size_t r1, int width,
+                                 uint8_t *dst) {
+    const bool ok = col && r0 <= r1 && op >= 0 && op <= 3 && (op != 0 || (dst && (width == 1 || width == 4))) &&
+                    (op != 3 || (aux && (width == 1 || width == 4 || width == 16)));
+    if (!ok) ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_host_rows: op 0 .. 3, r0 <= r1, pack: dst and width 1 or 4, same: aux and width 1, 4 or 16");
+    switch (op) {
+    case 0: return pack_rows(col, r0, r1, width, dst);
+    case 1: return zero_rows(col, r0, r1);
+    case 2: return clock_rows(col, r0, r1);
+    default: return same_rows(col, aux, r0, r1, width);
+    }
+}
+
+// row_tasks on the process pool (no GPU): the closure records its (first, end) pair; once the latch opens the pairs go to
+// ranges_out (2 per task, in the order the tasks finished), their number to *count_out.
+extern "C" int zk_diag_row_tasks(size_t r0, size_t r1, size_t R, uint64_t *ranges_out, size_t cap, size_t *count_out) {
+    if (!ranges_out || !count_out || R == 0 || (r1 > r0 && (r1 - r0 + R - 1) / R > ((size_t)1 << 20)))
+        ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_row_tasks: R >= 1, at most 2^20 tasks");
+    std::mutex mu;
+    std::vector<uint64_t> got;
+    Latch done;
+    row_tasks(done, 0, r0, r1, R, [&mu, &got](int, size_t a, size_t b) {
+        std::lock_guard<std::mutex> lk(mu);
+        got.push_back(a);
+        got.push_back(b);
+    });
+    done.wait();
+    *count_out = got.size() / 2;
+    if (got.size() / 2 > cap) ZK_FAIL(ZK_ERR_BUFFER_TOO_SMALL, "zk_diag_row_tasks: ranges_out too small");
+    if (!got.empty()) memcpy(ranges_out, got.data(), got.size() * sizeof(uint64_t));
+    return ZK_OK;
+}
+
 // ---- the back half of a proof, each stage through its production launcher on inputs of the caller's choice
 // (tests/test_gpu_back_half.py; the reference is tests/back_half_ref.py).  Like zk_diag_lde: a prover of its own on
 // `device`, the inputs uploaded into its buffers, the launcher on its stream, the result read back.

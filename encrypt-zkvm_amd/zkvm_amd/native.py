@@ -304,6 +304,18 @@ def lib():
             L.zk_diag_composition.argtypes = [i32, vp, sz, u32, i32, i32, i32, vp, vp, vp, vp, vp, C.POINTER(u32)]
             # (device, comp, n, ext, ncols, parts, tpolys, coeff_b, bnd1, polys_out, flag_out)
             L.zk_diag_composition_parts.argtypes = [i32, vp, sz, i32, i32, i32, vp, vp, vp, vp, C.POINTER(u32)]
+        if hasattr(L, "zk_diag_detect"):
+            # (device, cols, n, ncols, c0, how, parts, flags_out[4 * 28], last_out[28], polys_out)
+            L.zk_diag_detect.argtypes = [i32, vp, sz, i32, i32, i32, i32, vp, vp, vp]
+            # (device, trace, n, blowup, flags_out, polys_out, lde_out, root_out)
+            L.zk_diag_trace_commit.argtypes = [i32, vp, sz, u32, vp, vp, vp, vp]
+            # (device, last[28], sparse_mask, clock, n, blowup, polys_out, lde_out)
+            L.zk_diag_column_fills.argtypes = [i32, vp, u32, i32, sz, u32, vp, vp]
+            # (device, packed, packed_len, count, col[], width[], off[], last, n, out)
+            L.zk_diag_expand_narrow.argtypes = [i32, vp, sz, i32, vp, vp, vp, vp, sz, vp]
+            # (op, col, aux, r0, r1, width, dst) -> the check's verdict / (r0, r1, R, ranges_out, cap, count_out)
+            L.zk_diag_host_rows.argtypes = [i32, vp, vp, sz, sz, i32, vp]
+            L.zk_diag_row_tasks.argtypes = [sz, sz, sz, vp, sz, C.POINTER(sz)]
         _lib = L
     return _lib
 
