@@ -110,6 +110,19 @@ ZK_HD void merge(const uint32_t l[8], const uint32_t r[8], uint32_t out[8]) {
     compress(out, m, 0, 0, 64, CHUNK_START | CHUNK_END | ROOT);
 }
 
+// a digest in device memory (32 bytes, 16-byte aligned): two 16-byte accesses
+__device__ __forceinline__ void store_digest(uint8_t *dst, const uint32_t h[8]) {
+    uint4 *d = reinterpret_cast<uint4 *>(dst);
+    d[0] = make_uint4(h[0], h[1], h[2], h[3]);
+    d[1] = make_uint4(h[4], h[5], h[6], h[7]);
+}
+__device__ __forceinline__ void load_digest(const uint8_t *src, uint32_t h[8]) {
+    const uint4 *s = reinterpret_cast<const uint4 *>(src);
+    uint4 a = s[0], b = s[1];
+    h[0] = a.x; h[1] = a.y; h[2] = a.z; h[3] = a.w;
+    h[4] = b.x; h[5] = b.y; h[6] = b.z; h[7] = b.w;
+}
+
 // ------------------------------------------------------------- host: arbitrary-length hashing
 __host__ static inline void words_from_bytes(const uint8_t *p, uint32_t *w, int n) {
     for (int i = 0; i < n; i++) w[i] = (uint32_t)p[4 * i] | (uint32_t)p[4 * i + 1] << 8 | (uint32_t)p[4 * i + 2] << 16 | (uint32_t)p[4 * i + 3] << 24;

@@ -24,8 +24,6 @@ namespace zk {
 
 #define ZK_LAUNCH_CHECK() (void)hipGetLastError()
 
-static inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
-
 __device__ __forceinline__ fe ld_fe(const fe *p) { return *p; }
 __device__ __forceinline__ void st_fe(fe *p, fe v) { *p = v; }
 
@@ -1011,17 +1009,8 @@ void grind_launch(hipStream_t st, const uint32_t *seed_dev, uint64_t start, uint
 }
 
 // ================================================================ hashing and Merkle trees
-__device__ __forceinline__ void store_digest(uint8_t *dst, const uint32_t h[8]) {
-    uint4 *d = reinterpret_cast<uint4 *>(dst);
-    d[0] = make_uint4(h[0], h[1], h[2], h[3]);
-    d[1] = make_uint4(h[4], h[5], h[6], h[7]);
-}
-__device__ __forceinline__ void load_digest(const uint8_t *src, uint32_t h[8]) {
-    const uint4 *s = reinterpret_cast<const uint4 *>(src);
-    uint4 a = s[0], b = s[1];
-    h[0] = a.x; h[1] = a.y; h[2] = a.z; h[3] = a.w;
-    h[4] = b.x; h[5] = b.y; h[6] = b.z; h[7] = b.w;
-}
+using b3::load_digest;
+using b3::store_digest;
 
 // Leaf digests of coset-major LDE rows, one thread per row (K3/K5 of SURVEY 7): the rows i = 8q + r of the
 // 2^log_rc cosets r0 <= r < r0 + 2^log_rc (all of them: r0 = 0, log_rc = log_b), leaves in natural order.
@@ -2941,115 +2930,4 @@ void coset_major_to_natural(hipStream_t st, const fe *src, int log_n, int log_b,
     hipLaunchKernelGGL(k_coset_to_natural, dim3(blocks), dim3(256), 0, st, src, log_n, log_b, dst);
 }
 
-}  // namespace zk
-
-// ================================================================ diagnostics (C ABI: zk_diag_*)
-namespace zk {
-__global__ void k_field_op(int op, const fe *a, const fe *b, fe *out, size_t count, const fe_ws *ws, const fe_w2 *w2) {
-    size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (t >= count) return;
-    fe x = a[t], y = b[t];
-    fe r;
-    const size_t w0 = t & ~(size_t)63, mir = count - 1 - t;  // the first element of lane t's wave; the mirrored lane
-    switch (op) {
-    // ---- the constant-multiplier forms: ws[i] = make_fe_ws(b[i]), w2[i] = make_fe_w2(b[i]), built by the host
-    case 11: r = fe_mul_uniform(x, load_fe_ws(ws, (int)w0)); break;  // wave-uniform: the W set of b[w0], scalar loads
-    case 12: r = fe_mul_wsv(x, ws[t]); break;                        // per lane: the W set of b[t], vector loads
-    case 13: {
-        // pair (a[t], A) with (a[w0 + 63 - l], B), l = t - w0: A the W set of b[w0], B that of b[w0 + 63] (the wave's
-        // first and last element; count a multiple of 64); lane t returns output t & 1 of (a[t] A, a[w0 + 63 - l] B)
-        const fe_ws WA = load_fe_ws(ws, (int)w0), WB = load_fe_ws(ws, (int)w0 + 63);
-        fe o[2];
-        fe_mul_uniform2(x, WA, a[w0 + 63 - (t - w0)], WB, o[0], o[1]);
-        r = o[t & 1];
-        break;
-    }
-    case 14:
-    case 15: {
-        // pair (a[t], b[t]) with the mirrored lane's (a, b)[count - 1 - t]; lane t returns output t & 1
-        fe o[2];
-        if (op == 14) fe_mul_wsv2(x, ws[t], a[mir], ws[mir], o[0], o[1]);
-        else fe_mul_w2_2(x, w2[t], a[mir], w2[mir], o[0], o[1]);
-        r = o[t & 1];
-        break;
-    }
-    // ---- the raw final reductions: L = a[t] (128 bits), s4 = bits 0 .. 31 of b[t], s5 = bits 32 .. 34;
-    // (L + (s4 + s5 2^32) 2^128) mod p
-    case 16: r = ws_fold(lo32(x.lo), hi32(x.lo), lo32(x.hi), hi32(x.hi), lo32(y.lo), hi32(y.lo) & 7u); break;
-    case 17: {
-        // lane t's input and the mirrored lane's (count - 1 - t) in one paired block; lane t returns output t & 1
-        const fe x2 = a[mir], y2 = b[mir];
-        uint32_t A[4] = {lo32(x.lo), hi32(x.lo), lo32(x.hi), hi32(x.hi)};
-        uint32_t B[4] = {lo32(x2.lo), hi32(x2.lo), lo32(x2.hi), hi32(x2.hi)};
-        fe o[2];
-        ws_fold2(A, lo32(y.lo), hi32(y.lo) & 7u, B, lo32(y2.lo), hi32(y2.lo) & 7u, o[0], o[1]);
-        r = o[t & 1];
-        break;
-    }
-    // ---- the lazy sums of W-set products (f128.hpp acc192 / acc288_madd_uniform), W the W set of b[w0]:
-    // 18: a[t] + sum_(j < 16) a[(t + j) mod count] b[w0] in 192 bits; 19: a[t] b[t] (a 256-bit product) + the same 16
-    // terms in 288 bits; 20: a[t] + ACC192_MAX_TERMS times a[t] b[w0], the most terms acc192 takes
-    case 18:
-    case 19: {
-        const fe_ws Wc = load_fe_ws(ws, (int)w0);
-        acc192 s = acc192_from(x);
-        acc288 s2 = acc288_zero();
-        if (op == 19) acc288_madd(s2, x, y);
-#pragma unroll 1
-        for (int j = 0; j < 16; j++) {
-            const fe v = a[(t + j) % count];
-            if (op == 18) acc192_madd_uniform(s, v, Wc);
-            else acc288_madd_uniform(s2, v, Wc);
-        }
-        r = op == 18 ? acc192_reduce(s) : acc288_reduce(s2);
-        break;
-    }
-    case 20: {
-        const fe_ws Wc = load_fe_ws(ws, (int)w0);
-        acc192 s = acc192_from(x);
-#pragma unroll 1
-        for (int j = 0; j < ACC192_MAX_TERMS; j++) acc192_madd_uniform(s, x, Wc);
-        r = acc192_reduce(s);
-        break;
-    }
-    case 0: r = fe_add(x, y); break;
-    case 1: r = fe_sub(x, y); break;
-    case 2: r = fe_mul(x, y); break;
-    case 3: r = fe_inv(x); break;
-    case 5: r = fe_add_lazy(x, y); break;  // the NTT's lazy forms: x any value < 2^128, y canonical
-    case 6: r = fe_canon(x); break;
-    case 7: r = fe_mul_w2(x, fe_w2{y, fe_mul(y, fe{0, 1})}); break;  // two-part constant (w, w 2^64)
-    case 8:
-    case 9:
-    case 10: {
-        // the NTT butterflies' addsub2 forms (V = op - 8: both sums canonical, both lazy, first lazy): inputs (x, y) and
-        // (a, b)[count - 1 - t]; lane t returns output t & 3 of (x + y, x - y, x2 + y2, x2 - y2)
-        const fe x2 = a[count - 1 - t], y2 = b[count - 1 - t];
-        fe o[4];
-        if (op == 8) addsub2_v<0>(x, y, x2, y2, o[0], o[1], o[2], o[3]);
-        else if (op == 9) addsub2_v<1>(x, y, x2, y2, o[0], o[1], o[2], o[3]);
-        else addsub2_v<2>(x, y, x2, y2, o[0], o[1], o[2], o[3]);
-        r = o[t & 3];
-        break;
-    }
-    default: r = fe_exp(x, y.lo, y.hi); break;
-    }
-    out[t] = r;
-}
-
-__global__ void k_blake3_elems(const fe *in, int k, size_t count, uint8_t *out) {
-    size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
-    if (t >= count) return;
-    uint32_t h[8];
-    b3::hash_elements(k, [&](int i) { return in[t * k + i]; }, h);
-    store_digest(out + 32 * t, h);
-}
-
-void diag_field_op(hipStream_t st, int op, const fe *a, const fe *b, fe *out, size_t count, const fe_ws *ws,
-                   const fe_w2 *w2) {
-    hipLaunchKernelGGL(k_field_op, dim3(cdiv(count, 256)), dim3(256), 0, st, op, a, b, out, count, ws, w2);
-}
-void diag_blake3_elems(hipStream_t st, const fe *in, int k, size_t count, uint8_t *out) {
-    hipLaunchKernelGGL(k_blake3_elems, dim3(cdiv(count, 256)), dim3(256), 0, st, in, k, count, out);
-}
 }  // namespace zk

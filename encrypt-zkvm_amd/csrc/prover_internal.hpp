@@ -577,7 +577,15 @@ struct IoScope {
     }
 };
 
-
+// prover.hip's table builders and S4, which the test entry points (diag.hip) call as well (documented where they are
+// defined).  Hidden: they were file-local until diag.hip split off, and the library's export list stays as it was.
+#define ZK_LOCAL __attribute__((visibility("hidden")))
+ZK_LOCAL hipError_t make_pow_table(zk_prover *p, fe s, size_t n, PowTable *out);
+ZK_LOCAL hipError_t make_ntt_tables(zk_prover *p, int log_n, NttTables *T);
+ZK_LOCAL std::vector<fe> periodic_table(size_t n);
+ZK_LOCAL int composition_stage(zk_prover *p, Plan *pl, int KX, int C, fe *comp, fe *ctmp, fe *clde, uint8_t root[32],
+                               const AirConsts *bnd = nullptr, int nce = 8, const CoeffSrc *TS = nullptr,
+                               const fe *w = nullptr);
 int get_plan(zk_prover *p, size_t n, uint32_t B, Plan **out);
 void stage_begin(zk_prover *p);
 void stage_mark(zk_prover *p, const char *name);

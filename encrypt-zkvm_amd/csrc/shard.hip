@@ -39,8 +39,6 @@ using namespace zk;
 
 namespace {
 
-static inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
-
 // ---------------------------------------------------------------- loopback communicator
 // Every rank in this process: the collective is device-to-device copies, all of them on the issue stream (ordered
 // after every rank's compute stream by xchg_start), so its completion covers every rank's reads and writes.
@@ -99,11 +97,6 @@ struct HostComm : zk_comm {
 };
 
 // ---------------------------------------------------------------- local-coset kernels
-__device__ __forceinline__ void st_digest(uint8_t *dst, const uint32_t h[8]) {
-    uint4 *d = reinterpret_cast<uint4 *>(dst);
-    d[0] = make_uint4(h[0], h[1], h[2], h[3]);
-    d[1] = make_uint4(h[4], h[5], h[6], h[7]);
-}
 // Block ownership (round 6): rank g owns the cosets g Bl .. g Bl + Bl - 1, so in every group q of 8 consecutive leaves
 // 8q .. 8q + 7 (leaf 8q + r: row q of coset r) its Bl leaves are siblings: it hashes them and their subtree up to level
 // Lb = log2 Bl itself, and only that block node -- 1/Bl of the leaf digests -- crosses the link.  Each tree keeps the
@@ -121,26 +114,26 @@ __device__ __forceinline__ void blk_levels(size_t Q, size_t q, uint8_t *blk, uin
     static_assert(BL == 1 || BL == 2 || BL == 4, "a sharded rank holds 1, 2 or 4 cosets");
     uint32_t a[8];
     leaf(0, a);
-    st_digest(blk + 32 * (q * BL), a);
+    b3::store_digest(blk + 32 * (q * BL), a);
     if constexpr (BL >= 2) {
         uint32_t b[8];
         leaf(1, b);
-        st_digest(blk + 32 * (q * BL + 1), b);
+        b3::store_digest(blk + 32 * (q * BL + 1), b);
         b3::merge(a, b, a);
-        st_digest(blk + 32 * (Q * BL + q * (BL / 2)), a);
+        b3::store_digest(blk + 32 * (Q * BL + q * (BL / 2)), a);
         if constexpr (BL == 4) {
             uint32_t c[8], d[8];
             leaf(2, c);
-            st_digest(blk + 32 * (q * 4 + 2), c);
+            b3::store_digest(blk + 32 * (q * 4 + 2), c);
             leaf(3, d);
-            st_digest(blk + 32 * (q * 4 + 3), d);
+            b3::store_digest(blk + 32 * (q * 4 + 3), d);
             b3::merge(c, d, c);
-            st_digest(blk + 32 * (Q * 4 + q * 2 + 1), c);
+            b3::store_digest(blk + 32 * (Q * 4 + q * 2 + 1), c);
             b3::merge(a, c, a);
-            st_digest(blk + 32 * (Q * 6 + q), a);
+            b3::store_digest(blk + 32 * (Q * 6 + q), a);
         }
     }
-    st_digest(send_slot, a);
+    b3::store_digest(send_slot, a);
 }
 
 // LDE rows (column c, local coset j at base[(c*Bl + j)*n + q]; Q = n groups): piece k of K
@@ -201,7 +194,7 @@ __global__ void k_sh_blk_merge(const uint8_t *recv, int G, int log_QGK, int k, u
     l[0] = a0.x; l[1] = a0.y; l[2] = a0.z; l[3] = a0.w; l[4] = a1.x; l[5] = a1.y; l[6] = a1.z; l[7] = a1.w;
     r[0] = c0.x; r[1] = c0.y; r[2] = c0.z; r[3] = c0.w; r[4] = c1.x; r[5] = c1.y; r[6] = c1.z; r[7] = c1.w;
     b3::merge(l, r, h);
-    st_digest(lvl1 + 32 * ((((size_t)k << log_QGK) + qq) * hg + j), h);
+    b3::store_digest(lvl1 + 32 * ((((size_t)k << log_QGK) + qq) * hg + j), h);
 }
 
 // all-gathered chunks [s][j][q'] (source chunk s at item s * src_stride) -> natural order: item (s Bl + j) + 8 q' (local

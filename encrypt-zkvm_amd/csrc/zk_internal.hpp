@@ -12,6 +12,8 @@
 
 namespace zk {
 
+static inline unsigned cdiv(size_t a, size_t b) { return (unsigned)((a + b - 1) / b); }
+
 // ---------------------------------------------------------------- kernel profiler
 // When enabled, every kernel launch is bracketed by a pair of HIP events on its own stream, so
 // per-kernel device time is measured on the stream the kernel actually runs on.
@@ -504,11 +506,4 @@ void fri_coin_launch(hipStream_t st, uint32_t *seed_dev, const uint8_t *root_dev
 // out[k] = src[idx[k]] for field elements
 void gather_fe(hipStream_t st, const fe *src, const uint64_t *idx, size_t k, fe *out);
 
-}  // namespace zk
-
-namespace zk {
-// ws / w2: the W sets / two-part forms of b[0 .. count) (ops 11 .. 14 / op 15; else null)
-void diag_field_op(hipStream_t st, int op, const fe *a, const fe *b, fe *out, size_t count, const fe_ws *ws = nullptr,
-                   const fe_w2 *w2 = nullptr);
-void diag_blake3_elems(hipStream_t st, const fe *in, int k, size_t count, uint8_t *out);
 }  // namespace zk
