@@ -2127,6 +2127,190 @@ hipError_t validate_trace(hipStream_t st, const fe *trace, size_t n, const fe *p
     return hipGetLastError();
 }
 
+// ================================================================ transition constraint degrees
+// validate_transition_degrees of winterfell 0.9 (the debug-build step inside DefaultConstraintEvaluator::evaluate;
+// recollected, as DESIGN section 2 says of every winterfell citation) for ProcessorAir: include/zkvm_gpu.h
+// "transition constraint degrees" fixes the semantics.  k_transition_quotients evaluates the 20 constraints of
+// evaluate_transition (air/src/lib.rs:104-168) one by one over the CE domain 3 <w_8n> and divides each by the
+// transition divisor; the host interpolates the 20 x 8 coset planes with the composition's interpolation (ntt inverse
+// per coset, then k_comp_cross) and k_poly_degrees finds each quotient's degree.
+// One thread per CE row with k_eval_constraints' row mapping (coset-major LDE, EvalMap, frame partner q + 1), the
+// periodic values from the evaluator's CE-domain table and the divisor inverse from plane 0 of divisor_tables.  The
+// body is k_validate_trace's, constraint by constraint, with a store where that kernel tests for zero: no coefficient,
+// no folding of constraints into each other.  quot[k 8n + jl n + q] = C_k(x) / D(x), CE-coset-major per constraint,
+// each value stored as soon as it is formed: beside the validate body's state only the divisor inverse is live.
+__global__ void __launch_bounds__(256, ZK_EVAL_WAVES) k_transition_quotients(const fe *lde, int log_n, EvalMap map,
+                                                                              const fe *periodic, const fe *divs,
+                                                                              fe delta, int L, fe *quot) {
+    __shared__ fe vstash[6][256];  // 24 KiB, as k_validate_trace
+    const int tid = threadIdx.x;
+    const size_t n = (size_t)1 << log_n;
+    const size_t CE = n * map.nce;
+    const size_t t_id = blockIdx.x * (size_t)blockDim.x + threadIdx.x;
+    if (t_id >= CE) return;
+    const size_t jl = t_id >> log_n, q = t_id & (n - 1), qn = (q + 1) & (n - 1);
+    const size_t i = map.ce0 + map.cestep * jl + 8 * q;  // the CE step
+    const fe *tb = lde + (jl << map.lshift) * n;          // laundered by ZK_SEQ between the sections
+    const size_t cs = (size_t)map.lde_cosets * n;
+    const fe dT = divs[t_id];
+    fe *qo = quot + t_id;
+#define VCUR(c) tb[(size_t)(c)*cs + q]
+#define VNXT(c) tb[(size_t)(c)*cs + qn]
+#define VSET(k, val) qo[(size_t)(k)*CE] = fe_mul((val), dT)
+    const fe one = fe_one();
+    {
+        const fe b0 = VCUR(5), b1 = VCUR(4), b2 = VCUR(3), b3 = VCUR(2), b4 = VCUR(1);
+        const fe s0n = VNXT(12);
+        vstash[0][tid] = b0;
+        vstash[1][tid] = b1;
+        vstash[2][tid] = b2;
+        vstash[3][tid] = b3;
+        vstash[4][tid] = b4;
+        vstash[5][tid] = s0n;
+        // 12..15 Rescue round, 16..19 copy (constrains.rs:182-216)
+        // flags.rs: is_push = b0 (1 - b1)(1 - b2)(1 - b3)(1 - b4)
+        const fe is_push = fe_mul(fe_mul(fe_mul(fe_mul(b0, fe_sub(one, b1)), fe_sub(one, b2)), fe_sub(one, b3)),
+                                  fe_sub(one, b4));
+        fe opc = b0;  // 16 b0 + 8 b1 + 4 b2 + 2 b3 + b4
+        opc = fe_add(fe_add(opc, opc), b1);
+        opc = fe_add(fe_add(opc, opc), b2);
+        opc = fe_add(fe_add(opc, opc), b3);
+        opc = fe_add(fe_add(opc, opc), b4);
+        const fe push_term = fe_mul(s0n, is_push);
+        ZK_SEQ(tb, push_term.lo);
+        const fe *per = periodic + (i & 127) * 9;
+        const fe c7 = VCUR(7), c8 = VCUR(8);
+        fe x[4] = {cube(c7), cube(c8), cube(VCUR(9)), cube(VCUR(10))};
+        fe m0[4];
+#pragma unroll
+        for (int r = 0; r < 4; r++) m0[r] = fe_add(mds_row(r, x), per[1 + r]);
+        m0[0] = fe_add(m0[0], opc);
+        m0[1] = fe_add(m0[1], push_term);
+        ZK_SEQ(tb, m0[3].lo);
+        const fe hf = per[0], h0 = VCUR(6);
+        fe y[4];
+        {
+            // 16..19 first: the next-row sponge words are consumed as they arrive
+            const fe nf = fe_sub(one, hf);
+            const fe n7 = VNXT(7), n8 = VNXT(8), n9 = VNXT(9), n10 = VNXT(10);
+            VSET(16, fe_mul(fe_mul(fe_sub(n7, c7), nf), h0));
+            VSET(17, fe_mul(fe_mul(fe_sub(n8, c8), nf), h0));
+            VSET(18, fe_mul(fe_mul(n9, nf), h0));
+            VSET(19, fe_mul(fe_mul(n10, nf), h0));
+            y[0] = fe_sub(n7, per[5]);
+            y[1] = fe_sub(n8, per[6]);
+            y[2] = fe_sub(n9, per[7]);
+            y[3] = fe_sub(n10, per[8]);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            // (INV_MDS y)_r^3 = (adj_r y)^3 3^-72
+            const fe v3 = fe_mul(cube(adj_row(r, y)), ZK_INV3_72);
+            VSET(12 + r, fe_mul(fe_mul(fe_sub(v3, m0[r]), hf), h0));
+        }
+    }
+    ZK_SEQ(tb, dT.lo);
+    {
+        // 0 clock, 2 shift, 8..11 the selectors that move one value
+        const fe b0 = vstash[0][tid], b1 = vstash[1][tid], b2 = vstash[2][tid], b3 = vstash[3][tid],
+                 b4 = vstash[4][tid], s0n = vstash[5][tid];
+        const fe s0 = VCUR(12), s1 = VCUR(13);
+        VSET(0, fe_sub(VNXT(0), fe_add(VCUR(0), one)));
+        VSET(2, fe_mul(b0, b1));
+        const fe nb0 = fe_sub(one, b0), nb1 = fe_sub(one, b1), nb2 = fe_sub(one, b2), nb3 = fe_sub(one, b3),
+                 nb4 = fe_sub(one, b4);
+        fe is_read2;
+        {
+            // flags.rs: the three selectors that start b0 (1 - b1)(1 - b2)
+            const fe pp = fe_mul(fe_mul(b0, nb1), nb2), pn3 = fe_mul(pp, nb3);
+            const fe d1 = fe_sub(VNXT(13), s0);
+            VSET(8, fe_mul(fe_mul(pn3, nb4), d1));
+            VSET(9, fe_mul(fe_mul(pn3, b4), d1));
+            is_read2 = fe_mul(fe_mul(pp, b3), nb4);
+            VSET(10, fe_mul(is_read2, fe_sub(VNXT(17), s0)));
+        }
+        const fe is_noop = fe_mul(fe_mul(fe_mul(fe_mul(nb0, nb1), nb2), nb3), nb4);
+        VSET(11, fe_mul(is_noop, fe_sub(s0n, s0)));
+        // the selectors that start (1 - b0) b1: add, sadd, add2, mul over (1 - b2), smul over b2
+        const fe qq = fe_mul(nb0, b1), qa = fe_mul(qq, nb2);
+        const fe is_add = fe_mul(fe_mul(qa, nb3), nb4), is_sadd = fe_mul(fe_mul(qa, b3), nb4),
+                 is_add2 = fe_mul(fe_mul(qa, b3), b4), is_mul = fe_mul(fe_mul(qa, nb3), b4),
+                 is_smul = fe_mul(fe_mul(fe_mul(qq, b2), nb3), nb4);
+        VSET(3, fe_mul(is_add, fe_sub(s0n, fe_add(s0, s1))));
+        VSET(6, fe_mul(is_mul, fe_sub(s0n, fe_mul(s0, s1))));
+        // 1 depth: d' - d - b0 + b1 - 4 read2 + 4 add2
+        {
+            fe v = fe_add(fe_sub(fe_sub(VNXT(11), VCUR(11)), b0), b1);
+            fe r4 = fe_add(is_read2, is_read2), a4 = fe_add(is_add2, is_add2);
+            r4 = fe_add(r4, r4);
+            a4 = fe_add(a4, a4);
+            VSET(1, fe_add(fe_sub(v, r4), a4));
+        }
+        ZK_SEQ(tb, is_smul.lo);
+        // 4 sadd / 5 add2 / 7 smul over the lwe_size ciphertext limbs (fhe/src/server_key.rs:89-124), limb by
+        // limb as the reference sums them
+        fe a4 = fe_zero(), a5 = fe_zero(), a7 = fe_zero();
+        for (int l = 0; l < L; l++) {
+            const fe sn = VNXT(12 + l), si1 = VCUR(13 + l);
+            const fe triv = l == L - 1 ? fe_mul(s0, delta) : fe_zero();  // encrypt_trivial: delta s0 in the body
+            a4 = fe_add(a4, fe_sub(sn, fe_add(si1, triv)));
+            a5 = fe_add(a5, fe_sub(sn, fe_add(VCUR(12 + l), VCUR(12 + L + l))));
+            a7 = fe_add(a7, fe_sub(sn, fe_mul(si1, s0)));
+        }
+        VSET(4, fe_mul(is_sadd, a4));
+        VSET(5, fe_mul(is_add2, a5));
+        VSET(7, fe_mul(is_smul, a7));
+    }
+#undef VCUR
+#undef VNXT
+#undef VSET
+}
+
+hipError_t transition_quotients(hipStream_t st, const fe *lde, int log_n, EvalMap map, const fe *periodic,
+                                const fe *divs, fe delta, int lwe_size, fe *quot) {
+    if (const hipError_t e = upload_rescue_consts(st)) return e;
+    const size_t CE = (size_t)map.nce << log_n;
+    // two frames of 28 cells, the divisor, 20 stores
+    ZK_PROF(st, "transition_quotients", (2 * 448.0 + 16.0 + 320.0) * CE,
+            hipLaunchKernelGGL(k_transition_quotients, dim3(cdiv(CE, 256)), dim3(256), 0, st, lde, log_n, map, periodic,
+                               divs, delta, lwe_size, quot));
+    return hipGetLastError();
+}
+
+// Degrees of `count` (<= 20) polynomials of len coefficients each (polys[k len + j]): the highest non-zero index per
+// polynomial and a bit per polynomial that has a non-zero coefficient at all (polynom::degree_of gives 0 for the zero
+// polynomial and for a constant alike; the bit tells them apart).  blockIdx.y picks the polynomial; a thread keeps
+// the highest index + 1 it met, the block reduces by wave shuffles and LDS, then one device-scope integer atomicMax
+// and one atomicOr per block and polynomial: the result does not depend on the arrival order.  rep zeroed in-stream.
+__global__ void __launch_bounds__(256) k_poly_degrees(const fe *polys, size_t len, DegReport *rep) {
+    __shared__ unsigned long long sh_top[4];
+    const int k = blockIdx.y;
+    const fe *c = polys + (size_t)k * len;
+    unsigned long long top = 0;  // highest non-zero index + 1
+    for (size_t j = blockIdx.x * (size_t)blockDim.x + threadIdx.x; j < len; j += (size_t)gridDim.x * blockDim.x)
+        if (!fe_is_zero(c[j])) top = j + 1;  // (ascending per thread)
+    for (int d = 32; d > 0; d >>= 1) {
+        const unsigned long long o = __shfl_xor(top, d, 64);
+        top = o > top ? o : top;
+    }
+    if ((threadIdx.x & 63) == 0) sh_top[threadIdx.x >> 6] = top;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int w = 1; w < 4; w++) top = sh_top[w] > top ? sh_top[w] : top;
+        if (top) {
+            atomicMax(&rep->top[k], top - 1);
+            atomicOr(&rep->nonzero, 1u << k);
+        }
+    }
+}
+
+void poly_degrees(hipStream_t st, const fe *polys, size_t len, int count, DegReport *rep) {
+    unsigned blocks = cdiv(len, 256);
+    if (blocks > 1024) blocks = 1024;
+    ZK_PROF(st, "poly_degrees", 16.0 * count * (double)len,
+            hipLaunchKernelGGL(k_poly_degrees, dim3(blocks, count), dim3(256), 0, st, polys, len, rep));
+}
+
 // ================================================================ composition interpolation (K4)
 // The launch-uniform multipliers as W sets in the kernel arguments (scalar loads): the 8-point DFT's twiddles w8^-1,
 // w8^-2, w8^-3, the step 3^-n between a coefficient's blocks, and the derived coset's weights CrossMap::k7

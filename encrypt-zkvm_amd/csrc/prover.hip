@@ -392,6 +392,7 @@ static int create_prover(int device, size_t max_n, uint32_t max_b, int world, zk
     // trace validation: the report and the raw periodic table (the Rescue constants, as the AIR lists them)
     ZK_CHECK_HIP(A.alloc(&p->val_rep, 1));
     ZK_CHECK_HIP(A.alloc(&p->val_per, 16 * 9));
+    ZK_CHECK_HIP(A.alloc(&p->deg_rep, 1));  // transition constraint degrees: the device report
     {
         fe per[16 * 9];
         for (int r = 0; r < 16; r++) air_periodic_row((size_t)r, per + 9 * r);
@@ -1828,10 +1829,163 @@ static int validate_first(zk_prover *p, const void *d_trace, const uint8_t *cons
     return rc;
 }
 
+// ---------------------------------------------------------------- transition constraint degrees
+// validate_transition_degrees (winterfell 0.9, the debug-build step of DefaultConstraintEvaluator::evaluate) on the
+// GPU: include/zkvm_gpu.h "transition constraint degrees" fixes the semantics; kernels.hip k_transition_quotients and
+// k_poly_degrees are the device side.  No allocation of its own beyond the small report: the check runs in the
+// buffers of a proof, which none of its stages needs at the same time --
+//   p->polys  the 28 trace polynomials (dense interpolation of d_trace: ntt inverse, scale 1/n);
+//   p->lde    first the trace LDE over the 8 CE cosets (28 x 8 x n, the cosets 0, B/8, 2B/8, ... of the plan's blowup
+//             B), then, once the quotients are written, the 160 per-coset inverse transforms (20 x 8 x n);
+//   p->tmp    (28 x 8n) the four-step scratch of the front, then the 20 x 8n quotient values with the 8 x 8n behind them
+//             as the four-step scratch of their inverse transforms (groups of 8 constraints), and last, the values
+//             consumed, the 20 x 8n coefficients the cross-coset step writes (read by k_poly_degrees and quotients_out).
+// Rust's {:>3?} of a Vec<usize>: every element right-aligned in 3 columns
+static std::string rust_vec3(const uint64_t *v, int k) {
+    std::string s = "[";
+    for (int i = 0; i < k; i++) {
+        std::string e = std::to_string(v[i]);
+        if (e.size() < 3) e.insert(0, 3 - e.size(), ' ');
+        s += (i ? ", " : "") + e;
+    }
+    return s + "]";
+}
+
+// the trace is on p's device at d_trace; arguments are checked.  B: the blowup whose plan lends its tables
+static int degrees_on_device(zk_prover *p, const fe *d_trace, size_t n, const zk_pub_inputs *pub, uint32_t B,
+                             zk_degrees *out, uint8_t *quotients_out) {
+    ZK_CHECK_HIP(hipSetDevice(p->device));
+    IoScope io_scope(p);
+    Plan *pl = nullptr;
+    ZK_TRY(get_plan(p, n, B, &pl));
+    const int log_n = pl->log_n;
+    const size_t CE = 8 * n;
+    // the front: dense interpolation of all 28 columns, then their LDE over the 8 CE cosets
+    const fe inv_n = h_inv(fe_make(n));
+    ntt(p->st, pl->Tn, d_trace, n, p->polys, n, W, true, nullptr, &inv_n, p->tmp);
+    ntt_lde(p->st, pl->Tn, pl->ct, p->polys, n, W, 0, (int)(B / 8), 8, p->lde, CE, n, p->tmp);
+    const fe *binv = boundary_inverses(p, pl);
+    if (!binv) ZK_FAIL(ZK_ERR_OUT_OF_MEMORY, "transition divisor table");
+    const EvalMap map{8, 0, 1, 0, 8};
+    fe *quot = p->tmp, *scratch = p->tmp + NUM_TCONS * CE, *per_coset = p->lde;
+    ZK_CHECK_HIP(transition_quotients(p->st, p->lde, log_n, map, pl->periodic, binv, fe_make(pub->delta),
+                                      (int)pub->lwe_size, quot));
+    // the composition's interpolation per constraint: 8 per-coset inverse transforms (no scale), then the radix-8
+    // cross-coset step with scale 1/(8n), all 8 blocks of n coefficients kept
+    for (int k0 = 0; k0 < NUM_TCONS; k0 += 8) {
+        const int cnt = std::min(8, NUM_TCONS - k0);
+        ntt(p->st, pl->Tn, quot + k0 * CE, n, per_coset + k0 * CE, n, 8 * cnt, true, nullptr, nullptr, scratch);
+    }
+    const fe w8 = h_root_of_unity(3);
+    for (int k = 0; k < NUM_TCONS; k++) {
+        CrossMap m;
+        for (int r = 0; r < 8; r++) m.c[r] = per_coset + (size_t)(8 * k + r) * n;
+        m.k0 = 0;
+        m.kcount = n;
+        m.pstride = n;
+        comp_cross_mapped(p->st, m, pl->Tce, pl->inv3, h_inv(fe_make(CE)), h_inv(w8), h_inv(h_pow(fe_make(3), n)), 8,
+                          quot + k * CE, p->flag);
+    }
+    ZK_CHECK_HIP(hipMemsetAsync(p->deg_rep, 0, sizeof(DegReport), p->st));
+    poly_degrees(p->st, quot, CE, NUM_TCONS, p->deg_rep);
+    ZK_CHECK_HIP(hipGetLastError());
+    DegReport R;
+    ZK_TRY(d2h_small(p, &R, p->deg_rep, sizeof R));
+    ZK_TRY(d2h_flush(p));
+    if (quotients_out) {
+        ZK_CHECK_HIP(hipMemcpyAsync(quotients_out, quot, NUM_TCONS * CE * sizeof(fe), hipMemcpyDeviceToHost, p->st));
+        ZK_CHECK_HIP(hipStreamSynchronize(p->st));
+    }
+    collect_kernel_stats(p);  // (zk_prover_profile: a stand-alone check's kernels are counted like a proof's)
+    zk_degrees D;
+    memset(&D, 0, sizeof D);
+    D.trace_len = n;
+    D.ce_len = CE;
+    const DeclaredDegrees &decl = air_declared_degrees();
+    for (int k = 0; k < NUM_TCONS; k++) {
+        if (R.top[k] >= CE) ZK_FAIL(ZK_ERR_DEVICE, "constraint degrees: the device reported a coefficient outside the domain");
+        D.expected[k] = decl.evaluation_degree(k, n) - (n - 2);
+        D.actual[k] = R.top[k];
+        if (!((R.nonzero >> k) & 1u)) D.zero_mask |= 1u << k;
+        if (D.actual[k] != D.expected[k]) D.mismatch_mask |= 1u << k;
+        if (D.actual[k] > D.expected[k]) D.over_mask |= 1u << k;
+        D.max_actual = std::max(D.max_actual, D.actual[k]);
+    }
+    D.ce_len_needed = 1;
+    while (D.ce_len_needed < std::max<uint64_t>(D.max_actual, n + 1)) D.ce_len_needed *= 2;
+    p->deg_last = D;
+    p->deg_have = true;
+    *out = D;
+    if (!D.mismatch_mask) return ZK_OK;
+    ZK_FAIL(ZK_ERR_DEGREES, "transition constraint degrees didn't match\nexpected: " + rust_vec3(D.expected, NUM_TCONS) +
+                                "\nactual:   " + rust_vec3(D.actual, NUM_TCONS));
+}
+
+static int check_degrees_args(zk_prover *p, const void *trace, size_t n, const zk_pub_inputs *pub, zk_degrees *out) {
+    if (!p || !trace || !pub || !out) ZK_FAIL(ZK_ERR_INVALID_ARG, "null argument");
+    ZK_REQUIRE_FULL_PROVER(p);
+    ZK_TRY(check_trace_len(n, p->max_n));
+    return check_lwe_size(pub);
+}
+
+static int degrees_columns(zk_prover *p, const uint8_t *const *columns, size_t n, const zk_pub_inputs *pub, uint32_t B,
+                           zk_degrees *out, uint8_t *quotients_out) {
+    for (int c = 0; c < W; c++)
+        if (!columns[c]) ZK_FAIL(ZK_ERR_INVALID_ARG, "null trace column");
+    ZK_CHECK_HIP(hipSetDevice(p->device));
+    // one full upload, every column whole (a debugging aid: none of the prove path's column classes)
+    for (int c = 0; c < W; c++)
+        ZK_CHECK_HIP(hipMemcpyAsync(p->d_trace + (size_t)c * n, columns[c], n * sizeof(fe), hipMemcpyHostToDevice, p->st));
+    const int rc = degrees_on_device(p, p->d_trace, n, pub, B, out, quotients_out);
+    (void)hipStreamSynchronize(p->st);  // the caller's columns are free again on every way out
+    return rc;
+}
+
+int zk_degrees_device(zk_prover *p, const void *d_trace, size_t n, const zk_pub_inputs *pub, zk_degrees *out,
+                      uint8_t *quotients_out) {
+    ZK_TRY(check_degrees_args(p, d_trace, n, pub, out));
+    return degrees_on_device(p, (const fe *)d_trace, n, pub, 8, out, quotients_out);
+}
+
+int zk_degrees_columns(zk_prover *p, const uint8_t *const *columns, size_t n, const zk_pub_inputs *pub,
+                       zk_degrees *out, uint8_t *quotients_out) {
+    ZK_TRY(check_degrees_args(p, columns, n, pub, out));
+    return degrees_columns(p, columns, n, pub, 8, out, quotients_out);
+}
+
+int zk_prover_set_validate_degrees(zk_prover *p, int on) {
+    if (!p) ZK_FAIL(ZK_ERR_INVALID_ARG, "null prover");
+    p->validate_degrees = on != 0;
+    return ZK_OK;
+}
+
+int zk_prover_degrees(const zk_prover *p, zk_degrees *out) {
+    if (!p || !out) ZK_FAIL(ZK_ERR_INVALID_ARG, "null argument");
+    if (!p->deg_have) ZK_FAIL(ZK_ERR_INVALID_ARG, "no degree check has run on this prover");
+    *out = p->deg_last;
+    return ZK_OK;
+}
+
+// zk_prover_set_validate_degrees(p, 1): validate_transition_degrees before the proof, after validate_first (the order
+// of a debug build).  As there, arguments the prove path would refuse are left for it to report, and a mismatch ends
+// the call before prove_impl is entered.  The CE cosets come from the tables of the proof's own blowup (cosets
+// 0, B/8, ... of its LDE domain are the CE domain), so no plan is built that the proof does not need.
+static int degrees_first(zk_prover *p, const void *d_trace, const uint8_t *const *cols, size_t n, const zk_options *opt,
+                         const zk_pub_inputs *pub, size_t *proof_len) {
+    if (!p || !p->validate_degrees || !proof_len || p->shard_world > 1) return ZK_OK;
+    if (check_prove_args(n, p->max_n, p->max_b, opt, pub) != ZK_OK) return ZK_OK;
+    zk_degrees d;
+    const int rc = cols ? degrees_columns(p, cols, n, pub, opt->blowup, &d, nullptr)
+                        : degrees_on_device(p, (const fe *)d_trace, n, pub, opt->blowup, &d, nullptr);
+    if (rc != ZK_OK) *proof_len = 0;
+    return rc;
+}
+
 int zk_prove_device(zk_prover *p, const void *d_trace, size_t n, const zk_options *opt, const zk_pub_inputs *pub,
                     uint8_t *proof_out, size_t *proof_len, zk_record *rec, const zk_dump *dump) {
     if (!d_trace) ZK_FAIL(ZK_ERR_INVALID_ARG, "null argument");
     ZK_TRY(validate_first(p, d_trace, nullptr, n, opt, pub, proof_len));
+    ZK_TRY(degrees_first(p, d_trace, nullptr, n, opt, pub, proof_len));
     TraceSrc src;
     src.dev = (const fe *)d_trace;
     return prove_impl(p, src, n, opt, pub, proof_out, proof_len, rec, dump);
@@ -1893,6 +2047,7 @@ int zk_prove_columns_ex(zk_prover *p, const uint8_t *const *columns, size_t n, c
     for (int c = 0; c < W; c++)
         if (!columns[c]) ZK_FAIL(ZK_ERR_INVALID_ARG, "null trace column");
     ZK_TRY(validate_first(p, nullptr, columns, n, opt, pub, proof_len));
+    ZK_TRY(degrees_first(p, nullptr, columns, n, opt, pub, proof_len));
     TraceSrc src;
     src.cols = columns;
     return prove_impl(p, src, n, opt, pub, proof_out, proof_len, rec, dump);

@@ -361,6 +361,11 @@ struct zk_prover {
     fe *val_per = nullptr;
     bool validate = false, val_have = false;
     zk_validation val_last = {};
+    // transition constraint degrees (zk_degrees_device): the device report, the switch of
+    // zk_prover_set_validate_degrees and the last report (zk_prover_degrees)
+    zk::DegReport *deg_rep = nullptr;
+    bool validate_degrees = false, deg_have = false;
+    zk_degrees deg_last = {};
 };
 
 namespace zk {

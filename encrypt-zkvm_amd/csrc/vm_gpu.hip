@@ -540,8 +540,10 @@ int zk_vm_prove(zk_prover *p, zk_program *prog, const uint8_t *public_in, size_t
     read_last(last_row, last);
     // ZK_VM_PREPROCESS=0: every column from the device trace (no per-program preprocessed columns)
     // zk_prover_set_validate(p, 1): Trace::validate needs every column of the written trace in HBM, so the call takes
-    // the all-columns path and zk_prove_device validates before it proves (the same proof bytes either way)
-    const bool pre = env_switch("ZK_VM_PREPROCESS") && opt->blowup <= p->max_b && opt->blowup >= 8 && !p->validate;
+    // the all-columns path and zk_prove_device validates before it proves (the same proof bytes either way);
+    // zk_prover_set_validate_degrees(p, 1) likewise: the degree check interpolates all 28 written columns
+    const bool pre = env_switch("ZK_VM_PREPROCESS") && opt->blowup <= p->max_b && opt->blowup >= 8 && !p->validate &&
+                     !p->validate_degrees;
     size_t n = 0;
     zk_program::Fixed f{};
     uint32_t md = 0;

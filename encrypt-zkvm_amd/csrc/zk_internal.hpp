@@ -361,6 +361,18 @@ static_assert(sizeof(ValReport) < 1024, "the validation report stays a small tra
 // 28 x n column-major, n >= 16
 hipError_t validate_trace(hipStream_t st, const fe *trace, size_t n, const fe *per_tab, fe delta, int lwe_size,
                           ValReport *rep);
+// Transition constraint degrees (kernels.hip k_transition_quotients, k_poly_degrees; zk_degrees_device).
+// transition_quotients: quot[k 8n + jl n + q] = C_k / D at CE row (jl, q) of `map` for the 20 constraints k of
+// evaluate_transition, no coefficients; lde, periodic and divs (plane 0 of divisor_tables) as eval_constraints.
+hipError_t transition_quotients(hipStream_t st, const fe *lde, int log_n, EvalMap map, const fe *periodic,
+                                const fe *divs, fe delta, int lwe_size, fe *quot);
+// top[k]: the highest non-zero coefficient index of polynomial k; nonzero bit k: it has one.  Zeroed in-stream.
+struct DegReport {
+    unsigned long long top[20];
+    unsigned nonzero, pad_;
+};
+// polys: count (<= 20) polynomials of len coefficients each, one after the other
+void poly_degrees(hipStream_t st, const fe *polys, size_t len, int count, DegReport *rep);
 // Inputs of the cross-coset step for coefficients k0 .. k0+kcount: c[r][kl] = c_r[k0 + kl]; output
 // polys[k2 * pstride + kl].
 struct CrossMap {

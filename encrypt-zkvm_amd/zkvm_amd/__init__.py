@@ -3,6 +3,6 @@
 Product path: libzkvm_gpu.so (HIP kernels + C ABI, include/zkvm_gpu.h) driven through
 `zkvm_amd.prover`.  `zkvm_amd.workloads` builds seeded synthetic programs and inputs.
 """
-from .native import ZK_ERR_TRACE, Validation, ZkError, device_count  # noqa: F401
+from .native import ZK_ERR_DEGREES, ZK_ERR_TRACE, Degrees, Validation, ZkError, device_count  # noqa: F401
 from .prover import (REFERENCE_OPTIONS, ExecutionProver, GpuProver, ProofOptions,  # noqa: F401
                      make_pub_inputs, prove, vm_trace)

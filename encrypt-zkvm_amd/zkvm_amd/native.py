@@ -23,6 +23,7 @@ ZK_ERR_STACK = -11
 ZK_ERR_CHIPLETS = -12
 ZK_ERR_DEGREE = -20
 ZK_ERR_TRACE = -21
+ZK_ERR_DEGREES = -22
 ZK_ERR_VERIFY = -30
 
 MAX_COLS, MAX_TCONS, MAX_ASSERTS, MAX_CCOLS, MAX_FRI, MAX_REM, MAX_Q = 32, 32, 32, 16, 16, 256, 255
@@ -40,6 +41,7 @@ EXPORTED = (
     "zk_vm_prove",
     "zk_vm_prove_sharded",
     "zk_validate_device", "zk_validate_columns", "zk_prover_set_validate", "zk_prover_validation",
+    "zk_degrees_device", "zk_degrees_columns", "zk_prover_set_validate_degrees", "zk_prover_degrees",
 )
 
 
@@ -98,6 +100,29 @@ class Validation(C.Structure):
             "a_expected": [el(self.a_expected, k) for k in range(a)],
             "a_found": [el(self.a_found, k) for k in range(a)],
             "first_kind": self.first_kind, "first_index": self.first_index, "first_step": self.first_step,
+        }
+
+
+class Degrees(C.Structure):
+    """zk_degrees (include/zkvm_gpu.h): the report of one transition-constraint degree check
+    (validate_transition_degrees of winterfell 0.9)."""
+    _fields_ = [
+        ("trace_len", C.c_uint64), ("ce_len", C.c_uint64),
+        ("expected", C.c_uint64 * MAX_TCONS), ("actual", C.c_uint64 * MAX_TCONS),
+        ("mismatch_mask", C.c_uint32), ("zero_mask", C.c_uint32), ("over_mask", C.c_uint32), ("_pad", C.c_uint32),
+        ("max_actual", C.c_uint64), ("ce_len_needed", C.c_uint64),
+    ]
+
+    NUM_TCONS = 20  # ProcessorAir: evaluate_transition's results
+
+    def to_dict(self) -> dict:
+        """The report as plain ints, the arrays cut to the AIR's 20 constraints."""
+        t = self.NUM_TCONS
+        return {
+            "trace_len": self.trace_len, "ce_len": self.ce_len,
+            "expected": list(self.expected[:t]), "actual": list(self.actual[:t]),
+            "mismatch_mask": self.mismatch_mask, "zero_mask": self.zero_mask, "over_mask": self.over_mask,
+            "max_actual": self.max_actual, "ce_len_needed": self.ce_len_needed,
         }
 
 
@@ -212,6 +237,11 @@ def lib():
         L.zk_validate_columns.argtypes = [vp, C.POINTER(vp), sz, C.POINTER(PubInputs), C.POINTER(Validation)]
         L.zk_prover_set_validate.argtypes = [vp, i32]
         L.zk_prover_validation.argtypes = [vp, C.POINTER(Validation)]
+        if hasattr(L, "zk_degrees_device"):  # (an A/B library of an earlier commit, ZKVM_GPU_LIB, has none of the four)
+            L.zk_degrees_device.argtypes = [vp, vp, sz, C.POINTER(PubInputs), C.POINTER(Degrees), vp]
+            L.zk_degrees_columns.argtypes = [vp, C.POINTER(vp), sz, C.POINTER(PubInputs), C.POINTER(Degrees), vp]
+            L.zk_prover_set_validate_degrees.argtypes = [vp, i32]
+            L.zk_prover_degrees.argtypes = [vp, C.POINTER(Degrees)]
         L.zk_lde_new.argtypes = [vp, vp, sz, sz, u32, C.POINTER(vp), vp]
         L.zk_lde_read_frame.argtypes = [vp, sz, vp, vp]
         L.zk_lde_query.argtypes = [vp, vp, sz, vp, vp, C.POINTER(sz)]

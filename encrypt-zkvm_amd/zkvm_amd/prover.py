@@ -91,10 +91,11 @@ class GpuProver:
         return p.value
 
     def prove_device(self, d_trace: int, n: int, pub: PubInputs, options: ProofOptions = REFERENCE_OPTIONS,
-                     record: bool = False, dump=(), allow_degree_error=False, allow_trace_error=False):
+                     record: bool = False, dump=(), allow_degree_error=False, allow_trace_error=False,
+                     allow_degrees_error=False):
         """zk_prove_device: the trace is already in this prover's HBM (upload_trace)."""
         return self._prove(lambda *a: lib().zk_prove_device(self.handle, d_trace, n, *a), n, pub, options, record,
-                           dump, allow_degree_error, allow_trace_error)
+                           dump, allow_degree_error, allow_trace_error, allow_degrees_error)
 
     def _columns(self, trace: np.ndarray):
         """The 28 column pointers of a (28, n, 2) uint64 host array (kept on the prover and reused)."""
@@ -108,14 +109,15 @@ class GpuProver:
         return cols
 
     def prove_host(self, trace: np.ndarray, pub: PubInputs, options: ProofOptions = REFERENCE_OPTIONS,
-                   record: bool = False, dump=(), allow_degree_error=False, allow_trace_error=False):
+                   record: bool = False, dump=(), allow_degree_error=False, allow_trace_error=False,
+                   allow_degrees_error=False):
         """zk_prove_columns_ex: the trace is a (28, n, 2) uint64 host array (pinned -- HostTrace -- or
         pageable); the library uploads it column group by column group, overlapped with the interpolation."""
         trace = np.ascontiguousarray(trace, dtype=np.uint64)
         cols = self._columns(trace)
         n = trace.shape[1]
         return self._prove(lambda *a: lib().zk_prove_columns_ex(self.handle, cols, n, *a), n, pub, options, record,
-                           dump, allow_degree_error, allow_trace_error)
+                           dump, allow_degree_error, allow_trace_error, allow_degrees_error)
 
     # ---- Trace::validate (winterfell 0.9: Prover::prove's #[cfg(debug_assertions)] step), include/zkvm_gpu.h
     def _validated(self, rc, v):
@@ -149,7 +151,49 @@ class GpuProver:
         check(lib().zk_prover_validation(self.handle, C.byref(v)), "zk_prover_validation")
         return v.to_dict()
 
-    def _prove(self, call, n, pub, options, record, dump, allow_degree_error, allow_trace_error=False):
+    # ---- validate_transition_degrees (winterfell 0.9: the debug-build step of the constraint evaluator)
+    def _degrees(self, call, n, quotients):
+        """(rc, report[, quotients]) for ZK_OK and ZK_ERR_DEGREES (the report is filled either way); anything else
+        raises.  quotients: also the 20 quotient polynomials as lists of 8n ints (coefficient j of Q_k at [k][j])."""
+        d = native.Degrees()
+        q = np.zeros((20 * 8 * n, 2), dtype=np.uint64) if quotients else None
+        rc = call(C.byref(d), q.ctypes.data if quotients else None)
+        if rc not in (native.ZK_OK, native.ZK_ERR_DEGREES):
+            check(rc, "degrees")
+        if not quotients:
+            return rc, d.to_dict()
+        flat = bytes_elems(q.tobytes())
+        return rc, d.to_dict(), [flat[k * 8 * n:(k + 1) * 8 * n] for k in range(20)]
+
+    def degrees_device(self, d_trace: int, n: int, pub: PubInputs, quotients: bool = False):
+        """zk_degrees_device: the transition constraint degrees of a trace in this prover's HBM against the ones
+        ProcessorAir declares.  Returns (rc, report) -- rc ZK_OK or ZK_ERR_DEGREES (native.lib().zk_last_error() is then
+        winterfell's message), the report a dict of ints (native.Degrees.to_dict) -- and with quotients=True the 20
+        quotient polynomials' coefficients as a third item."""
+        return self._degrees(lambda d, q: lib().zk_degrees_device(self.handle, d_trace, n, C.byref(pub), d, q), n,
+                             quotients)
+
+    def degrees_host(self, trace: np.ndarray, pub: PubInputs, quotients: bool = False):
+        """zk_degrees_columns: the same for a (28, n, 2) uint64 host array, at the cost of one full upload."""
+        trace = np.ascontiguousarray(trace, dtype=np.uint64)
+        cols, n = self._columns(trace), trace.shape[1]
+        return self._degrees(lambda d, q: lib().zk_degrees_columns(self.handle, cols, n, C.byref(pub), d, q), n,
+                             quotients)
+
+    def set_validate_degrees(self, on: bool):
+        """zk_prover_set_validate_degrees: check the transition constraint degrees of every trace before proving it
+        (the other half of the reference's debug-build behaviour); a mismatch then ends the prove call with
+        ZK_ERR_DEGREES and no proof."""
+        check(lib().zk_prover_set_validate_degrees(self.handle, 1 if on else 0), "zk_prover_set_validate_degrees")
+
+    def degrees(self) -> dict:
+        """zk_prover_degrees: the report of the last degree check that ran on this prover."""
+        d = native.Degrees()
+        check(lib().zk_prover_degrees(self.handle, C.byref(d)), "zk_prover_degrees")
+        return d.to_dict()
+
+    def _prove(self, call, n, pub, options, record, dump, allow_degree_error, allow_trace_error=False,
+               allow_degrees_error=False):
         opt = options.to_c()
         # one proof buffer per prover, reused across proofs (a fresh 4 MiB ctypes buffer per call was
         # ~0.15 ms of zero-fill and page faults between two proofs); only plen bytes are copied out
@@ -172,7 +216,8 @@ class GpuProver:
         rc = call(C.byref(opt), C.byref(pub), buf, C.byref(plen), C.byref(rec) if rec is not None else None,
                   C.byref(dmp) if dmp is not None else None)
         if not (rc == 0 or (allow_degree_error and rc == native.ZK_ERR_DEGREE)
-                or (allow_trace_error and rc == native.ZK_ERR_TRACE)):
+                or (allow_trace_error and rc == native.ZK_ERR_TRACE)
+                or (allow_degrees_error and rc == native.ZK_ERR_DEGREES)):
             check(rc, "prove")
         return C.string_at(buf, plen.value), rec, held, rc
 

@@ -228,6 +228,58 @@ int zk_prover_set_validate(zk_prover *p, int on);
  * ZK_ERR_INVALID_ARG if none has run. */
 int zk_prover_validation(const zk_prover *p, zk_validation *out);
 
+/* ---- transition constraint degrees: the second check of a winterfell 0.9 debug build.  Inside
+ * DefaultConstraintEvaluator::evaluate, under #[cfg(debug_assertions)], validate_transition_degrees() takes every
+ * transition constraint's evaluations over the constraint-evaluation (CE) domain, divides them by the transition
+ * divisor, interpolates, and compares each quotient's degree with the one the AIR declares
+ * (TransitionConstraintDegree, air/src/lib.rs:69-90); a mismatch panics with
+ *   "transition constraint degrees didn't match\nexpected: [...]\nactual:   [...]"
+ * (winterfell is not part of this repository: these semantics are recollected, like every winterfell citation of
+ * DESIGN.md section 2; the anchor is that the reference's own example trace meets its declared degrees exactly under
+ * this reading).  The reference is built around the check: set_num_transition_exemptions(2) (lib.rs:92-94) and the
+ * thread_rng() last row of Processor::trace give every column polynomial degree n - 1.  A trace whose last row is not
+ * generic (zeros, a copy of row n - 2) proves and verifies here, yet stops a debug build of the reference.
+ * Semantics.  Base field; the CE domain is 3 <w_8n> (the AIR's CE blowup is 8, whatever the proof options say).
+ * C_k(x), k < 20: evaluate_transition on the LDE frame (x, x g) with the periodic column polynomials at x, no
+ * composition coefficients.  Q_k = C_k / D, D = (x^n - 1) / ((x - g^(n-2))(x - g^(n-1))), interpolated from its 8n
+ * values; actual[k] = the index of Q_k's highest non-zero coefficient, 0 for the zero polynomial (polynom::degree_of).
+ * expected[k] = base_k (n - 1) + cyc_k 15 n / 16 - (n - 2) with base = [1,5,2,6,6,6,7,7,6,6,6,6,4,7,4,4,2,2,2,2] and
+ * cyc = 1 for k >= 12 (the hash constraints' periodic column of cycle 16).  The trace passes iff actual == expected
+ * for all 20.  winterfell's second assertion, next_pow2(max(max actual, n + 1)) == 8n, is implied by a match; its left
+ * side is reported (ce_len_needed) and does not decide the status. */
+#define ZK_ERR_DEGREES -22   /* the transition constraint degrees differ from ProcessorAir's declared ones */
+typedef struct {
+    uint64_t trace_len, ce_len;               /* n, 8n */
+    uint64_t expected[ZK_MAX_TCONS], actual[ZK_MAX_TCONS];
+    uint32_t mismatch_mask, zero_mask, over_mask; /* bit k: actual != expected; Q_k == 0; actual > expected */
+    uint32_t _pad;
+    uint64_t max_actual, ce_len_needed;       /* next_pow2(max(max_actual, n + 1)) */
+} zk_degrees;
+/* validate_transition_degrees of a trace resident in this prover's device's HBM (28 x n column-major, n bounded as for
+ * zk_prove; of pub only lwe_size and delta are read).  ZK_OK or ZK_ERR_DEGREES; `out` is filled either way, and on
+ * failure zk_last_error() is winterfell's three-line message above with both vectors formatted as Rust's {:>3?}
+ * ("[  1, 509, 128, ...]").  quotients_out (optional): the 20 x 8n coefficients of the Q_k, coefficient j of Q_k at
+ * element k * 8n + j, 16 bytes little-endian each.  The check costs about a proof: a dense interpolation and 8-coset
+ * LDE of all 28 columns (none of zk_prove's column classes), 20 quotient planes, 160 size-n inverse transforms.  It
+ * runs in the prover's own buffers (trace polynomials, trace LDE, NTT scratch), so like a proof it ends the validity of
+ * any zk_trace_lde / zk_comp_commit handle of this prover.  Refused (ZK_ERR_INVALID_ARG) for a prover of
+ * zk_prover_create_shard. */
+int zk_degrees_device(zk_prover *p, const void *d_trace, size_t n, const zk_pub_inputs *pub, zk_degrees *out,
+                      uint8_t *quotients_out);
+/* The same for a host trace, one pointer per column (winterfell's ColMatrix): the 28 columns are copied whole into the
+ * prover's trace buffer and checked there. */
+int zk_degrees_columns(zk_prover *p, const uint8_t *const *columns, size_t n, const zk_pub_inputs *pub,
+                       zk_degrees *out, uint8_t *quotients_out);
+/* on = 1: zk_prove, zk_prove_columns(_ex), zk_prove_device and zk_vm_prove run validate_transition_degrees before they
+ * prove, after Trace::validate when zk_prover_set_validate is on as well (the order of a debug build: Prover::prove
+ * validates the trace, then the evaluator checks the degrees).  A mismatch returns ZK_ERR_DEGREES with *proof_len = 0:
+ * no proof is written and no column hint or snapshot is touched.  A pass goes on to the same proof bytes.  Default 0:
+ * nothing changes, and zk_prover_set_validate keeps its meaning.  The sharded entry points ignore the setting. */
+int zk_prover_set_validate_degrees(zk_prover *p, int on);
+/* The report of the last degree check that ran on p (by either call above or by a proof with the switch on);
+ * ZK_ERR_INVALID_ARG if none has run. */
+int zk_prover_degrees(const zk_prover *p, zk_degrees *out);
+
 /* ---- plug point 1: Prover::new_trace_lde (prover/src/lib.rs:55-62) -> DefaultTraceLde ---- */
 /* interpolate the trace, extend it over the blowup coset domain and commit to its rows.
  * The LDE lives in the prover's device memory until zk_lde_free. */
