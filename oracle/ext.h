@@ -13,10 +13,6 @@
 #define ORACLE_EXT_H
 #include "internal.h"
 
-typedef struct {
-    u128 a, b;
-} e2;
-
 static inline e2 e2_base(u128 v) {
     e2 r = {v, 0};
     return r;

@@ -114,8 +114,19 @@ uint8_t *merkle_build(const uint8_t *leaves, size_t num_leaves);
 void air_eval_u(const u128 *cur, const u128 *nxt, const u128 *per, uint32_t lwe, u128 delta, u128 *out);
 void air_periodic_u(unsigned step16, u128 *out9);
 
-
 /* winter-air AirContext::num_constraint_composition_columns for ProcessorAir (prover.c) */
 size_t or_num_comp_cols(size_t n);
+
+/* an element a + b*X of the quadratic extension (arithmetic in ext.h) */
+typedef struct {
+    u128 a, b;
+} e2;
+
+/* The AIR side of the out-of-domain identity (verifier.c): the transition constraints at the frame
+ * (oz, ozg) combined by ct[20] over the transition divisor at z, plus the two boundary groups
+ * combined by cb[22] over theirs.  The verifier compares it with sum_j z^(jn) H_j(z); the forging
+ * prover's FIT_OOD (prover.c) solves that sum for H_0(z). */
+e2 or_ood_air_side(const e2 *oz, const e2 *ozg, const e2 *ct, const e2 *cb, e2 z, size_t n,
+                   const or_pub_inputs *pub);
 
 #endif

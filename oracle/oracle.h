@@ -145,6 +145,32 @@ int or_prove(const void *trace /* 28 x n col-major */, size_t n, const or_option
              const or_pub_inputs *pub, uint8_t *proof_out, size_t *proof_len, or_record *rec,
              const or_dump *dump);
 
+/* ---- dishonest prover: the forged proofs the verifier tests need (tests/test_verifier_soundness.py).
+ * Each cheat departs from or_prove at one place and is otherwise consistent with its own
+ * transcript, so exactly one of the verifier's checks can object to it. */
+typedef enum {
+    OR_CHEAT_NONE = 0,       /* or_prove */
+    OR_CHEAT_IGNORE_DEGREE,  /* honest pipeline on an invalid statement: the composition's coefficients
+                                past c*n are dropped, the OOD constraint values are the truncated
+                                columns'.  Dies at the OOD identity. */
+    OR_CHEAT_FIT_OOD,        /* as above, then H_0(z) is set to what makes sum_j z^(jn) H_j(z) equal the
+                                AIR side at z: the DEEP quotient is not low degree.  Dies at the FRI
+                                remainder. */
+    OR_CHEAT_SHIFT_DEEP,     /* valid statement; 1 is added to every DEEP evaluation before FRI.  Dies at
+                                the layer-0 fold comparison (no layers: the remainder). */
+    OR_CHEAT_BAD_FOLD,       /* valid statement; arg = l in 1..num_fri_layers: 1 is added to every value
+                                folded into layer l (l = num_fri_layers: into the remainder).  Dies at the
+                                layer-l fold comparison (the remainder). */
+    OR_CHEAT_NO_GRIND,       /* grinding > 0: the smallest nonce >= 1 that fails the proof of work, query
+                                positions derived from it as usual.  Dies at the proof of work. */
+} or_cheat;
+
+/* or_prove with one cheat.  The proof bytes and the record are written whatever the statement:
+ * returns OR_OK, or OR_ERR_DEGREE when the honest degree check would have refused (both with the
+ * bytes), or an argument / buffer error. */
+int or_forge(const void *trace, size_t n, const or_options *opt, const or_pub_inputs *pub, uint32_t cheat,
+             uint32_t arg, uint8_t *proof_out, size_t *proof_len, or_record *rec);
+
 /* ---- verifier (winterfell verify restated for this AIR; checks our own proofs) ---- */
 int or_verify(const uint8_t *proof, size_t proof_len, const or_pub_inputs *pub, uint32_t min_security,
               char *msg, size_t msg_cap);

@@ -91,6 +91,8 @@ def lib():
         L.or_air_eval_transition.argtypes = [vp, vp, vp, u32, u32, vp]
         L.or_prove.argtypes = [vp, sz, C.POINTER(Options), C.POINTER(PubInputs), vp, C.POINTER(sz),
                                C.POINTER(Record), C.POINTER(Dump)]
+        L.or_forge.argtypes = [vp, sz, C.POINTER(Options), C.POINTER(PubInputs), u32, u32, vp, C.POINTER(sz),
+                               C.POINTER(Record)]
         L.or_verify.argtypes = [vp, sz, C.POINTER(PubInputs), u32, vp, sz]
         _lib = L
     return _lib
@@ -283,6 +285,26 @@ def prove_rc(trace: np.ndarray, pub: PubInputs, options: Options | None = None, 
     rc = lib().or_prove(trace.ctypes.data, n, C.byref(options), C.byref(pub), buf, C.byref(plen), C.byref(rec),
                         C.byref(dump))
     return rc, (buf.raw[:plen.value] if rc == 0 else b""), rec, held
+
+
+# or_cheat (oracle.h): where the dishonest prover departs from or_prove
+CHEAT_NONE, IGNORE_DEGREE, FIT_OOD, SHIFT_DEEP, BAD_FOLD, NO_GRIND = range(6)
+
+
+def forge(trace: np.ndarray, pub: PubInputs, options: Options | None, cheat: int, arg: int = 0):
+    """The dishonest prover (or_forge): (proof, record), the bytes written whatever the statement.
+    Only a wrong argument raises (a cheat the options leave no room for, e.g. BAD_FOLD past the layers)."""
+    options = options or default_options()
+    trace = np.ascontiguousarray(trace, dtype=np.uint64)
+    rec = Record()
+    cap = 4 << 20
+    buf = C.create_string_buffer(cap)
+    plen = C.c_size_t(cap)
+    rc = lib().or_forge(trace.ctypes.data, trace.shape[1], C.byref(options), C.byref(pub), cheat, arg, buf,
+                        C.byref(plen), C.byref(rec))
+    if rc not in (0, -20):
+        raise OracleError(rc, f"or_forge failed with status {rc}")
+    return buf.raw[:plen.value], rec
 
 
 def verify(proof: bytes, pub: PubInputs, min_security: int = 95):

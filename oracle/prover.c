@@ -193,8 +193,11 @@ static size_t sorted_assertions(size_t n, const or_pub_inputs *pub, assertion_t 
 }
 
 /* ----------------------------------------------------------------- prove */
-int or_prove(const void *trace_v, size_t n, const or_options *opt, const or_pub_inputs *pub, uint8_t *proof_out,
-             size_t *proof_len, or_record *rec, const or_dump *dump) {
+/* or_prove (cheat = OR_CHEAT_NONE) and or_forge: each cheat of oracle.h is a few lines at one stage,
+ * marked [cheat] */
+static int prove_body(const void *trace_v, size_t n, const or_options *opt, const or_pub_inputs *pub,
+                      uint8_t *proof_out, size_t *proof_len, or_record *rec, const or_dump *dump, uint32_t cheat,
+                      uint32_t arg) {
     if (n < 16 || (n & (n - 1)) || !opt || !pub || !proof_len) return OR_ERR_INVALID_ARG;
     if ((opt->field_extension != 1 && opt->field_extension != 2) || opt->blowup < CE_BLOWUP || (opt->blowup & (opt->blowup - 1)) ||
         (opt->fri_folding != 2 && opt->fri_folding != 4 && opt->fri_folding != 8 && opt->fri_folding != 16) ||
@@ -204,6 +207,12 @@ int or_prove(const void *trace_v, size_t n, const or_options *opt, const or_pub_
     const u128 *trace = (const u128 *)trace_v;
     const size_t B = opt->blowup, N = B * n, CE = CE_BLOWUP * n, fold = opt->fri_folding;
     if (opt->num_queries >= N) return OR_ERR_INVALID_ARG;
+    size_t nl = 0, last = N; /* FRI layers and the remainder's domain [P9]; refused before anything is allocated */
+    for (; last > (size_t)(opt->fri_rem_max_deg + 1) * B; last /= fold) nl++;
+    if (nl > OR_MAX_FRI_LAYERS || last / B > OR_MAX_REMAINDER) return OR_ERR_INVALID_ARG;
+    if (cheat > OR_CHEAT_NO_GRIND || (cheat == OR_CHEAT_NO_GRIND && opt->grinding == 0) ||
+        (cheat == OR_CHEAT_BAD_FOLD && (arg < 1 || arg > nl)))
+        return OR_ERR_INVALID_ARG;
     const size_t C = or_num_comp_cols(n);
     const int K = (int)opt->field_extension; /* 1: FieldExtension::None, 2: Quadratic */
     const u128 offset = F_GENERATOR; /* StarkDomain offset = GENERATOR [P1] */
@@ -379,8 +388,17 @@ int or_prove(const void *trace_v, size_t n, const or_options *opt, const or_pub_
     for (size_t c = 0; c < C; c++) {
         oodc[c] = poly_eval_e(cpolys + c * K * n, n, z);
         if (K == 2) oodc[c] = e2_add(oodc[c], e2_mulX(poly_eval_e(cpolys + (c * K + 1) * n, n, z)));
-        st(R.ood_constraints[c], oodc[c].a);
     }
+    if (cheat == OR_CHEAT_FIT_OOD) { /* [cheat] H_0(z) := AIR side - sum_{j >= 1} z^(jn) H_j(z) */
+        const e2 zn = e2_exp(z, n);
+        e2 h = or_ood_air_side(ood, ood + W, ct, cb, z, n, pub), zz = zn;
+        for (size_t c = 1; c < C; c++) {
+            h = e2_sub(h, e2_mul(zz, oodc[c]));
+            zz = e2_mul(zz, zn);
+        }
+        oodc[0] = h;
+    }
+    for (size_t c = 0; c < C; c++) st(R.ood_constraints[c], oodc[c].a);
     {
         uint8_t h[32];
         e2_hash(oodc, C, K, h);
@@ -434,11 +452,10 @@ int or_prove(const void *trace_v, size_t n, const or_options *opt, const or_pub_
     }
     if (dump && dump->deep)
         for (size_t i = 0; i < N; i++) st((uint8_t *)dump->deep + 16 * i, deep[i].a);
+    if (cheat == OR_CHEAT_SHIFT_DEEP) /* [cheat] FRI runs on DEEP + 1: low degree, but not the DEEP polynomial */
+        for (size_t i = 0; i < N; i++) deep[i] = e2_add(deep[i], e2_base(1));
 
     /* S6: FRI over E [P9, P10] */
-    size_t max_rem = (size_t)(opt->fri_rem_max_deg + 1) * B, nl = 0;
-    for (size_t s = N; s > max_rem; s /= fold) nl++;
-    if (nl > OR_MAX_FRI_LAYERS) return OR_ERR_INVALID_ARG;
     R.num_fri_layers = (uint32_t)nl;
     e2 *layer_vals[OR_MAX_FRI_LAYERS]; /* transposed: row r = [e[r + k*L/fold]] */
     uint8_t *layer_leaves[OR_MAX_FRI_LAYERS], *layer_nodes[OR_MAX_FRI_LAYERS];
@@ -478,6 +495,8 @@ int or_prove(const void *trace_v, size_t n, const or_options *opt, const or_pub_
             nx[r] = acc;
             xr_inv = f_mul(xr_inv, wl_inv);
         }
+        if (cheat == OR_CHEAT_BAD_FOLD && arg == l + 1) /* [cheat] layer l+1 (or the remainder) gets fold + 1 */
+            for (size_t r = 0; r < rows; r++) nx[r] = e2_add(nx[r], e2_base(1));
         layer_vals[l] = tv;
         layer_leaves[l] = lv;
         layer_nodes[l] = nodes;
@@ -492,7 +511,6 @@ int or_prove(const void *trace_v, size_t n, const or_options *opt, const or_pub_
     e2 rem[OR_MAX_REMAINDER];
     size_t rl = L / B;
     {
-        if (rl > OR_MAX_REMAINDER) return OR_ERR_INVALID_ARG;
         u128 *ra = (u128 *)malloc(L * 16), *rb = (u128 *)calloc(L, 16);
         for (size_t i = 0; i < L; i++) {
             ra[i] = ev[i].a;
@@ -522,7 +540,8 @@ int or_prove(const void *trace_v, size_t n, const or_options *opt, const or_pub_
         uint64_t head;
         memcpy(&head, d, 8);
         unsigned tz = head ? (unsigned)__builtin_ctzll(head) : 64;
-        if (tz >= opt->grinding) break;
+        /* [cheat] NO_GRIND stops at the first nonce that fails instead */
+        if (cheat == OR_CHEAT_NO_GRIND ? tz < opt->grinding : tz >= opt->grinding) break;
     }
     R.pow_nonce = nonce;
     {
@@ -685,4 +704,17 @@ int or_prove(const void *trace_v, size_t n, const or_options *opt, const or_pub_
     free(leaves);
     free(tnodes);
     return rc;
+}
+
+int or_prove(const void *trace, size_t n, const or_options *opt, const or_pub_inputs *pub, uint8_t *proof_out,
+             size_t *proof_len, or_record *rec, const or_dump *dump) {
+    return prove_body(trace, n, opt, pub, proof_out, proof_len, rec, dump, OR_CHEAT_NONE, 0);
+}
+
+int or_forge(const void *trace, size_t n, const or_options *opt, const or_pub_inputs *pub, uint32_t cheat, uint32_t arg,
+             uint8_t *proof_out, size_t *proof_len, or_record *rec) {
+    if (!proof_out || !proof_len) return OR_ERR_INVALID_ARG;
+    const size_t cap = *proof_len;
+    const int rc = prove_body(trace, n, opt, pub, proof_out, proof_len, rec, NULL, cheat, arg);
+    return (rc == OR_OK || rc == OR_ERR_DEGREE) && *proof_len > cap ? OR_ERR_BUFFER_TOO_SMALL : rc;
 }

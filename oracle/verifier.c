@@ -195,6 +195,39 @@ done:
     return rc;
 }
 
+/* H(z) from the AIR at z (internal.h) */
+e2 or_ood_air_side(const e2 *oz, const e2 *ozg, const e2 *ct, const e2 *cb, e2 z, size_t n,
+                   const or_pub_inputs *pub) {
+    const u128 g = f_root_of_unity(ilog2_sz(n));
+    e2 per[9], ev[NUM_TCONS];
+    u128 pc[9][16];
+    for (unsigned s = 0; s < 16; s++) {
+        u128 row[9];
+        air_periodic_u(s, row);
+        for (int j = 0; j < 9; j++) pc[j][s] = row[j];
+    }
+    const e2 zp = e2_exp(z, n / 16);
+    for (int j = 0; j < 9; j++) {
+        interp_coset_u(pc[j], 16, 1);
+        per[j] = poly_eval_e(pc[j], 16, zp);
+    }
+    air_eval_e(oz, ozg, per, pub->lwe_size, pub->delta, ev);
+    e2 t = e2_base(0);
+    for (int k = 0; k < NUM_TCONS; k++) t = e2_add(t, e2_mul(ct[k], ev[k]));
+    const e2 gl2 = e2_base(f_exp(g, n - 2)), gl1 = e2_base(f_exp(g, n - 1)), one = e2_base(1);
+    const e2 zn = e2_exp(z, n);
+    e2 h = e2_mul(e2_mul(t, e2_mul(e2_sub(z, gl2), e2_sub(z, gl1))), e2_inv(e2_sub(zn, one)));
+    const int fc[12] = {0, 7, 8, 11, 12, 13, 14, 15, 16, 17, 18, 19};
+    e2 b0 = e2_base(0), b1 = e2_base(0);
+    for (int i = 0; i < 12; i++) b0 = e2_add(b0, e2_mul(cb[i], oz[fc[i]]));
+    for (int i = 0; i < 2; i++)
+        b1 = e2_add(b1, e2_mul(cb[12 + i], e2_sub(oz[7 + i], e2_base(ld(pub->program_hash[i])))));
+    for (int i = 0; i < 8; i++)
+        b1 = e2_add(b1, e2_mul(cb[14 + i], e2_sub(oz[12 + i], e2_base(ld(pub->stack_outputs[i])))));
+    h = e2_add(h, e2_mul(b0, e2_inv(e2_sub(z, one))));
+    return e2_add(h, e2_mul(b1, e2_inv(e2_sub(z, gl2))));
+}
+
 int or_verify(const uint8_t *proof, size_t proof_len, const or_pub_inputs *pub, uint32_t min_security, char *msg,
               size_t msg_cap) {
     int rc = 0;
@@ -296,36 +329,9 @@ int or_verify(const uint8_t *proof, size_t proof_len, const or_pub_inputs *pub, 
     }
     /* ---- OOD consistency: H(z) from the AIR at z vs sum_j z^(jn) H_j(z) */
     {
-        const u128 g = f_root_of_unity(logn);
-        e2 per[9], ev[NUM_TCONS];
-        u128 pc[9][16];
-        for (unsigned s = 0; s < 16; s++) {
-            u128 row[9];
-            air_periodic_u(s, row);
-            for (int j = 0; j < 9; j++) pc[j][s] = row[j];
-        }
-        const e2 zp = e2_exp(z, n / 16);
-        for (int j = 0; j < 9; j++) {
-            interp_coset_u(pc[j], 16, 1);
-            per[j] = poly_eval_e(pc[j], 16, zp);
-        }
-        air_eval_e(oz, ozg, per, pub->lwe_size, pub->delta, ev);
-        e2 t = e2_base(0);
-        for (int k = 0; k < NUM_TCONS; k++) t = e2_add(t, e2_mul(ct[k], ev[k]));
-        const e2 gl2 = e2_base(f_exp(g, n - 2)), gl1 = e2_base(f_exp(g, n - 1)), one = e2_base(1);
-        const e2 zn = e2_exp(z, n);
-        e2 h = e2_mul(e2_mul(t, e2_mul(e2_sub(z, gl2), e2_sub(z, gl1))), e2_inv(e2_sub(zn, one)));
-        const int fc[12] = {0, 7, 8, 11, 12, 13, 14, 15, 16, 17, 18, 19};
-        e2 b0 = e2_base(0), b1 = e2_base(0);
-        for (int i = 0; i < 12; i++) b0 = e2_add(b0, e2_mul(cb[i], oz[fc[i]]));
-        for (int i = 0; i < 2; i++)
-            b1 = e2_add(b1, e2_mul(cb[12 + i], e2_sub(oz[7 + i], e2_base(ld(pub->program_hash[i])))));
-        for (int i = 0; i < 8; i++)
-            b1 = e2_add(b1, e2_mul(cb[14 + i], e2_sub(oz[12 + i], e2_base(ld(pub->stack_outputs[i])))));
-        h = e2_add(h, e2_mul(b0, e2_inv(e2_sub(z, one))));
-        h = e2_add(h, e2_mul(b1, e2_inv(e2_sub(z, gl2))));
+        const e2 h = or_ood_air_side(oz, ozg, ct, cb, z, n, pub), zn = e2_exp(z, n);
         /* H(z) = sum_j z^(jn) H_j(z); with k = 2, H_j(z) = oc[j] as the E-valued column */
-        e2 hc = e2_base(0), zz = one;
+        e2 hc = e2_base(0), zz = e2_base(1);
         for (size_t j = 0; j < C; j++) {
             hc = e2_add(hc, e2_mul(zz, oc[j]));
             zz = e2_mul(zz, zn);
