@@ -1,5 +1,5 @@
 // diag.hip -- the test entry points (C ABI: zk_diag_*), each a direct call into one piece of the prover on inputs of the
-// caller's choice.  Nothing on the prove path calls into this file.  (zk_diag_vm_states, the 30th, reads vm_gpu.hip's
+// caller's choice.  Nothing on the prove path calls into this file.  (zk_diag_vm_states, the 31st, reads vm_gpu.hip's
 // file-local VM state and lives there.)
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -961,23 +961,28 @@ extern "C" int zk_diag_coeff_sources(int device, const uint8_t *tplanes, const u
 // One FRI layer through commit_fri_layer and fri_fold_launch: `layer` holds L values as the
 // kernels read them (over E planar: L a components, then L b components; lb > 0: coset-major over 2^lb cosets,
 // FriLayout), folded by `fold` at `alpha` (16 bytes, 32 over E) with x_r = 3 w_L^r taken from the tables of a plan of
-// N = L wstride points.  root_out: the layer's Merkle root (32 bytes); next_out: the L / fold folded values (planar).
+// N = L wstride points.  root_out: the layer's Merkle root (32 bytes; of a one-row layer, L = fold, the zero digest:
+// commit_fri_layer); next_out: the L / fold folded values (planar).
 extern "C" int zk_diag_fri_layer(int device, const uint8_t *layer, size_t L, int ext, int fold, int lb, size_t wstride,
                                  const uint8_t *alpha, uint8_t *root_out, uint8_t *next_out) {
     fe2 av;
     const size_t N = L * wstride;
     const bool ok = layer && alpha && root_out && next_out && (ext == 1 || ext == 2) &&
                     (fold == 2 || fold == 4 || fold == 8 || fold == 16) && L && !(L & (L - 1)) && wstride &&
-                    !(wstride & (wstride - 1)) && L >= 4 * (size_t)fold && N >= 128 && N <= ((size_t)1 << 22) && lb >= 0 &&
-                    ((size_t)1 << lb) <= L / fold;
+                    !(wstride & (wstride - 1)) && (L >= 4 * (size_t)fold || L == (size_t)fold) && N >= 128 &&
+                    N <= ((size_t)1 << 22) && lb >= 0 && ((size_t)1 << lb) <= L / fold;
     if (!ok || !diag_read_fe(alpha, ext, &av))
         ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_fri_layer: L and wstride powers of two, 128 <= L wstride <= 2^22, fold 2 .. 16, "
-                                    "at least 4 rows, 2^lb <= L / fold, alpha canonical");
+                                    "at least 4 rows or the single row of an overfolded last layer, 2^lb <= L / fold, "
+                                    "alpha canonical");
     DiagProver p;
     ZK_TRY(p.open(device, N / 8, 8, true, ext));
     const Planes b = planes(p, ext);
     const size_t rows = L / fold;
     uint8_t *leaves = p->fri_dig, *nodes = leaves + 32 * rows;
+    // (the digests' area as a proof's later layers find it: not zero.  A one-row layer's root slot lies 32 bytes past
+    // its 64 rows bytes, as in fri_lead_layers)
+    ZK_CHECK_HIP(hipMemsetAsync(leaves, 0xA5, 64 * rows + 64, p->st));
     ZK_TRY(p.up(b.deep, layer, (size_t)ext * L));
     ZK_TRY(with_kx(ext, [&](auto kx) -> int {
         const auto F = fold_consts<decltype(kx)::value>(av, (uint32_t)fold);
@@ -988,6 +993,47 @@ extern "C" int zk_diag_fri_layer(int device, const uint8_t *layer, size_t L, int
     fri_fold_launch(p->st, ext, b.deep, L, fold, b.fold_consts, p.pl->TN, wstride, b.fri, lb);
     ZK_TRY(p.down(root_out, nodes + 32, 32));
     return p.down(next_out, b.fri, (size_t)ext * rows);
+}
+
+// ---- the Merkle tree builder on leaves of the caller's choice (tests/test_gpu_merkle.py; the reference is
+// tests/merkle_ref.py).  merkle_tree_cfg over nl 32-byte leaf digests (nl a power of two in [2, 2^24]) with the
+// launcher's constants given: levels of at least 2^l3_min_log nodes through k_merge_level3_pf on at most pf_blocks
+// blocks, the rest through k_merge_block with up to block_p threads (merkle_tree itself: 17, 2048, 512).  Checked here,
+// not in the launcher: l3_min_log in [2, 62] (a level of fewer than 4 nodes gives the three-level kernel no group),
+// pf_blocks in [1, 2^20], block_p a power of two in [1, 512].
+// The heap lies between two guard regions of ZK_DIAG_MERKLE_GUARD bytes, the leaves after the upper one; guards and heap
+// are filled with 0xA5 before the launches.  nodes_out: the heap, 32 nl bytes (slot 0, which no kernel writes, still
+// 0xA5; node i at 32 i); guard_out: the lower guard, then the upper; leaves_out: the leaf buffer after the launches.  A
+// store outside the heap's nodes thus comes back as a changed byte.
+// positions != NULL: also the batch opening of the k positions, as zk_lde_query forms it (query_positions,
+// batch_proof_bytes: the same refusals), into proof_out; *proof_len in: its capacity, out: the length.
+constexpr size_t ZK_DIAG_MERKLE_GUARD = 4096;
+extern "C" int zk_diag_merkle(int device, const uint8_t *leaves, size_t nl, int l3_min_log, uint32_t pf_blocks,
+                              uint32_t block_p, uint8_t *nodes_out, uint8_t *guard_out, uint8_t *leaves_out,
+                              const uint64_t *positions, size_t k, uint8_t *proof_out, size_t *proof_len) {
+    if (!leaves || !nodes_out || !guard_out || !leaves_out || nl < 2 || (nl & (nl - 1)) || nl > ((size_t)1 << 24))
+        ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_merkle: nl a power of two in [2, 2^24]");
+    if (l3_min_log < 2 || l3_min_log > 62 || pf_blocks < 1 || pf_blocks > (1u << 20) || block_p < 1 || block_p > 512 ||
+        (block_p & (block_p - 1)))
+        ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_merkle: l3_min_log in [2, 62], pf_blocks in [1, 2^20], block_p a power of two "
+                                    "in [1, 512]");
+    if (positions && !proof_len) ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_merkle: positions without proof_len");
+    std::vector<uint64_t> pos;
+    if (positions) ZK_TRY(query_positions(positions, k, nl, pos));
+    const size_t G = ZK_DIAG_MERKLE_GUARD, heap = 32 * nl;
+    DiagBuf buf;  // lower guard, heap, upper guard, leaves
+    ZK_TRY(buf.alloc(device, 2 * G + 2 * heap));
+    uint8_t *d_nodes = buf.d + G, *d_leaves = buf.d + 2 * G + heap;
+    ZK_CHECK_HIP(hipMemset(buf.d, 0xA5, 2 * G + heap));
+    ZK_CHECK_HIP(hipMemcpy(d_leaves, leaves, heap, hipMemcpyHostToDevice));
+    merkle_tree_cfg(nullptr, d_leaves, nl, d_nodes, MerkleCfg{l3_min_log, pf_blocks, block_p});
+    ZK_CHECK_HIP(hipGetLastError());
+    ZK_CHECK_HIP(hipMemcpy(nodes_out, d_nodes, heap, hipMemcpyDeviceToHost));
+    ZK_CHECK_HIP(hipMemcpy(guard_out, buf.d, G, hipMemcpyDeviceToHost));
+    ZK_CHECK_HIP(hipMemcpy(guard_out + G, d_nodes + heap, G, hipMemcpyDeviceToHost));
+    ZK_CHECK_HIP(hipMemcpy(leaves_out, d_leaves, heap, hipMemcpyDeviceToHost));
+    if (positions) ZK_TRY(batch_proof_bytes(nl, pos, d_leaves, d_nodes, proof_out, proof_len));
+    return ZK_OK;
 }
 
 // One grind_launch over the nonces [start, start + count) with the result preset to ~0: *best_out = the smallest

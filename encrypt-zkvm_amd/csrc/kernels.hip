@@ -1251,6 +1251,11 @@ void commit_fri_layer(hipStream_t st, int KX, const fe *layer, size_t L, int fol
         ZK_PROF(st, "hash_fri_rows", 16.0 * L + 32.0 * rows, hipLaunchKernelGGL(k_hash_fri_rows<1>, grid, dim3(256), 0, st, layer, L, fold, f, leaves));
     else
         ZK_PROF(st, "hash_fri_rows_ext", 32.0 * L + 32.0 * rows, hipLaunchKernelGGL(k_hash_fri_rows<2>, grid, dim3(256), 0, st, layer, L, fold, f, leaves));
+    // A layer of one row: fold 16 at blowup 8 with a remainder of one coefficient reaches L = 16 (trace lengths 32, 512,
+    // 8192 ...).  Such a proof ends in the degree error (its remainder is shorter than the blowup), but the layer's root
+    // is read on the way, and merkle_tree launches nothing for one leaf: the caller's nodes[1] would be whatever the
+    // buffer held.  A tree of one leaf has no merge, so the root is the zero digest the oracle's zeroed heap gives (merkle_build).
+    if (rows == 1) (void)hipMemsetAsync(nodes + 32, 0, 32, st);
     merkle_tree(st, leaves, rows, nodes);
 }
 
@@ -1357,13 +1362,16 @@ __global__ void __launch_bounds__(512) k_merge_block(const uint8_t *src, uint8_t
 #ifndef ZK_MERKLE_L3_MIN
 #define ZK_MERKLE_L3_MIN 17  // log2 of the smallest level the three-level kernel takes (A/B: 17 > 20 > 16 > 14)
 #endif
-void merkle_tree(hipStream_t st, const uint8_t *leaves, size_t nl, uint8_t *nodes) {
+// The launcher with its three constants as arguments (MerkleCfg, zk_internal.hpp): merkle_tree below passes the
+// production values; zk_diag_merkle passes small ones, so that trees of a few thousand leaves reach the three-level
+// kernel, its grid-stride rounds and the chained block passes.  The configuration is the caller's to validate.
+void merkle_tree_cfg(hipStream_t st, const uint8_t *leaves, size_t nl, uint8_t *nodes, MerkleCfg cfg) {
     // invariant: src holds 2*cnt digests whose parents go to nodes[cnt .. 2cnt)
     size_t cnt = nl / 2;
     const uint8_t *src = leaves;
     // wide levels: three per launch, seven compressions per thread (throughput)
-    while (cnt >= ((size_t)1 << ZK_MERKLE_L3_MIN)) {
-        const unsigned blocks = std::min<unsigned>(cdiv(cnt / 4, 256), MERKLE_PF_BLOCKS);
+    while (cnt >= ((size_t)1 << cfg.l3_min_log)) {
+        const unsigned blocks = std::min<unsigned>(cdiv(cnt / 4, 256), cfg.pf_blocks);
         ZK_PROF(st, "merkle_level", 64.0 * cnt + 32.0 * (cnt + cnt / 2 + cnt / 4),
                 hipLaunchKernelGGL(k_merge_level3_pf, dim3(blocks), dim3(256), 0, st, src, nodes, cnt));
         src = nodes + 32 * (cnt / 4);
@@ -1371,13 +1379,16 @@ void merkle_tree(hipStream_t st, const uint8_t *leaves, size_t nl, uint8_t *node
     }
     // upper part: up to 10 levels per launch, one compression per thread per level (latency)
     while (cnt >= 1) {
-        const size_t P = std::min<size_t>(512, cnt), roots = cnt / P;
+        const size_t P = std::min<size_t>(cfg.block_p, cnt), roots = cnt / P;
         ZK_PROF(st, roots > 1 ? "merkle_level" : "merkle_top", 96.0 * 2 * cnt,
                 hipLaunchKernelGGL(k_merge_block, dim3((unsigned)roots), dim3((unsigned)P), 0, st, src, nodes, cnt));
         if (roots == 1) break;
         src = nodes + 32 * roots;
         cnt = roots / 2;
     }
+}
+void merkle_tree(hipStream_t st, const uint8_t *leaves, size_t nl, uint8_t *nodes) {
+    merkle_tree_cfg(st, leaves, nl, nodes, MerkleCfg{ZK_MERKLE_L3_MIN, MERKLE_PF_BLOCKS, 512});
 }
 
 __global__ void k_gather_digests(const uint8_t *src, const uint64_t *idx, size_t k, uint8_t *out) {

@@ -2138,28 +2138,26 @@ int zk_lde_read_frame(zk_trace_lde *h, size_t step, uint8_t *cur, uint8_t *next)
     return ZK_OK;
 }
 
-// rows at `positions` of a committed coset-major LDE (ncols columns) + the batch Merkle proof bytes
-static int query_committed_rows(zk_prover *p, const fe *base, int ncols, size_t n, uint32_t B, const uint8_t *leaves,
-                                const uint8_t *nodes, const uint64_t *positions, size_t k, uint8_t *rows_out,
-                                uint8_t *proof_out, size_t *proof_len) {
-    if (!positions || !rows_out || !proof_len || k == 0 || k > ZK_MAX_QUERIES)
-        ZK_FAIL(ZK_ERR_INVALID_ARG, "invalid query arguments");
-    const size_t N = n * B;
-    std::vector<uint64_t> pos(positions, positions + k);
+// The two halves of a direct batch opening, shared by the plug points' queries below and zk_diag_merkle (diag.hip).
+// query_positions: the k positions of a query over N leaves into pos, refused unless 1 <= k <= ZK_MAX_QUERIES, each
+// below N and all distinct.
+int zk::query_positions(const uint64_t *positions, size_t k, size_t N, std::vector<uint64_t> &pos) {
+    if (!positions || k == 0 || k > ZK_MAX_QUERIES) ZK_FAIL(ZK_ERR_INVALID_ARG, "invalid query arguments");
+    pos.assign(positions, positions + k);
     for (uint64_t x : pos)
         if (x >= N) ZK_FAIL(ZK_ERR_INVALID_ARG, "query position out of range");
-    {
-        // MerkleTree::prove_batch refuses a repeated index (MerkleTreeError::DuplicateLeafIndex): the batch proof
-        // holds one path per distinct leaf pair, and a verifier rebuilds the root from distinct positions
-        std::vector<uint64_t> sorted(pos);
-        std::sort(sorted.begin(), sorted.end());
-        if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
-            ZK_FAIL(ZK_ERR_INVALID_ARG, "duplicate query position");
-    }
-    ZK_CHECK_HIP(hipMemcpyAsync(p->gather_idx, pos.data(), k * 8, hipMemcpyHostToDevice, p->st));
-    gather_rows(p->st, base, ncols, ilog2(n), ilog2(B), p->gather_idx, k, p->gather_out);
-    ZK_CHECK_HIP(hipMemcpyAsync(rows_out, p->gather_out, k * ncols * 16, hipMemcpyDeviceToHost, p->st));
-    ZK_CHECK_HIP(hipStreamSynchronize(p->st));
+    // MerkleTree::prove_batch refuses a repeated index (MerkleTreeError::DuplicateLeafIndex): the batch proof
+    // holds one path per distinct leaf pair, and a verifier rebuilds the root from distinct positions
+    std::vector<uint64_t> sorted(pos);
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+        ZK_FAIL(ZK_ERR_INVALID_ARG, "duplicate query position");
+    return ZK_OK;
+}
+// batch_proof_bytes: the serialized batch Merkle proof of pos over the N device leaves and their heap `nodes` (idle
+// stream: plain copies), plan_batch's digests in its order.  *proof_len: in the capacity of proof_out, out the length.
+int zk::batch_proof_bytes(size_t N, const std::vector<uint64_t> &pos, const uint8_t *leaves, const uint8_t *nodes,
+                          uint8_t *proof_out, size_t *proof_len) {
     BatchPlan bp;
     plan_batch(N, pos, bp);
     Bytes out;
@@ -2177,6 +2175,21 @@ static int query_committed_rows(zk_prover *p, const fe *base, int ncols, size_t 
     if (!proof_out || cap < out.v.size()) ZK_FAIL(ZK_ERR_BUFFER_TOO_SMALL, "proof buffer too small");
     memcpy(proof_out, out.v.data(), out.v.size());
     return ZK_OK;
+}
+
+// rows at `positions` of a committed coset-major LDE (ncols columns) + the batch Merkle proof bytes
+static int query_committed_rows(zk_prover *p, const fe *base, int ncols, size_t n, uint32_t B, const uint8_t *leaves,
+                                const uint8_t *nodes, const uint64_t *positions, size_t k, uint8_t *rows_out,
+                                uint8_t *proof_out, size_t *proof_len) {
+    if (!rows_out || !proof_len) ZK_FAIL(ZK_ERR_INVALID_ARG, "invalid query arguments");
+    const size_t N = n * B;
+    std::vector<uint64_t> pos;
+    ZK_TRY(query_positions(positions, k, N, pos));
+    ZK_CHECK_HIP(hipMemcpyAsync(p->gather_idx, pos.data(), k * 8, hipMemcpyHostToDevice, p->st));
+    gather_rows(p->st, base, ncols, ilog2(n), ilog2(B), p->gather_idx, k, p->gather_out);
+    ZK_CHECK_HIP(hipMemcpyAsync(rows_out, p->gather_out, k * ncols * 16, hipMemcpyDeviceToHost, p->st));
+    ZK_CHECK_HIP(hipStreamSynchronize(p->st));
+    return batch_proof_bytes(N, pos, leaves, nodes, proof_out, proof_len);
 }
 
 int zk_lde_query(zk_trace_lde *h, const uint64_t *positions, size_t k, uint8_t *rows_out, uint8_t *proof_out,

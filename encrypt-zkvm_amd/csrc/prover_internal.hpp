@@ -622,6 +622,11 @@ struct BatchPlan {
     }
 };
 void plan_batch(size_t nl, const std::vector<uint64_t> &idx, BatchPlan &out);  // reuses out's storage
+// A direct batch opening (zk_lde_query, zk_comp_query, zk_diag_merkle): the checked positions of a query over N leaves,
+// and the serialized batch proof read from the device leaves and heap (prover.hip)
+int query_positions(const uint64_t *positions, size_t k, size_t N, std::vector<uint64_t> &pos);
+int batch_proof_bytes(size_t N, const std::vector<uint64_t> &pos, const uint8_t *leaves, const uint8_t *nodes,
+                      uint8_t *proof_out, size_t *proof_len);
 
 // ---------------------------------------------------------------- protocol steps (host side)
 // argument checks shared by every prove entry point; returns ZK_OK or a status (g_err set)

@@ -488,7 +488,7 @@ int dist_commit(Ctx &X, DistTree &T, size_t M, HashFn hash, const char *digests_
     for (int l = 0; l < nl; l++) {
         zk_prover *p = X.P[l];
         ZK_CHECK_HIP(hipSetDevice(p->device));
-        merkle_tree(p->st, T.nodes[l] + 32 * (Q / 2), Q / 2, T.nodes[l]);  // (Q >= G >= 2)
+        merkle_tree(p->st, T.nodes[l] + 32 * (Q / 2), Q / 2, T.nodes[l]);  // (Q >= G >= 2; Q = 2: the one leaf is nodes[1])
         b.set(l, T.nodes[l] + 32, p->sh_roots);
     }
     ZK_TRY(xchg(X, roots_name, AG, b, 32));

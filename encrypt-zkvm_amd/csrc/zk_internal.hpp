@@ -245,7 +245,20 @@ struct FriLayout {
 };
 FriLayout fri_layout(size_t L, int lb);
 // nodes[1..nl) of a binary Merkle tree over nl leaves (nodes[nl/2..nl) = merges of leaf pairs)
+// nl a power of two.  With nl = 1 nothing is launched and no node is written.  Two callers can pass 1: the sharded
+// upper tree (dist_commit: Q / 2 leaves, Q >= G >= 2), whose one leaf sits at nodes + 32 and so is the root already;
+// and commit_fri_layer for a one-row layer, whose leaf does not, and which therefore sets the root itself.  The trace
+// and composition trees have n blowup >= 128 leaves.
 void merkle_tree(hipStream_t st, const uint8_t *leaves, size_t nl, uint8_t *nodes);
+// merkle_tree with its launch constants as arguments: levels of at least 2^l3_min_log nodes take the three-level kernel
+// on a grid of at most pf_blocks blocks, the rest blocks of up to block_p threads (production: 17, 2048, 512).  The
+// kernels need l3_min_log >= 2, pf_blocks >= 1 and block_p a power of two in [1, 512]; the caller sees to that.
+struct MerkleCfg {
+    int l3_min_log;
+    unsigned pf_blocks;
+    unsigned block_p;
+};
+void merkle_tree_cfg(hipStream_t st, const uint8_t *leaves, size_t nl, uint8_t *nodes, MerkleCfg cfg);
 // out[k] = src[idx[k]] for 32-byte digests
 // out[t] = the 16 bytes at device address addr[t] (query openings: LDE values and Merkle digests)
 constexpr size_t ZK_GATHER_CAP = 1 << 17;

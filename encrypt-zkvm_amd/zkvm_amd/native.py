@@ -346,6 +346,10 @@ def lib():
             # (op, col, aux, r0, r1, width, dst) -> the check's verdict / (r0, r1, R, ranges_out, cap, count_out)
             L.zk_diag_host_rows.argtypes = [i32, vp, vp, sz, sz, i32, vp]
             L.zk_diag_row_tasks.argtypes = [sz, sz, sz, vp, sz, C.POINTER(sz)]
+        if hasattr(L, "zk_diag_merkle"):
+            # (device, leaves, nl, l3_min_log, pf_blocks, block_p, nodes_out, guard_out[2 * 4096], leaves_out, positions,
+            #  k, proof_out, proof_len)
+            L.zk_diag_merkle.argtypes = [i32, vp, sz, i32, u32, u32, vp, vp, vp, vp, sz, vp, C.POINTER(sz)]
         _lib = L
     return _lib
 
