@@ -1,5 +1,5 @@
 // diag.hip -- the test entry points (C ABI: zk_diag_*), each a direct call into one piece of the prover on inputs of the
-// caller's choice.  Nothing on the prove path calls into this file.  (zk_diag_vm_states, the 31st, reads vm_gpu.hip's
+// caller's choice.  Nothing on the prove path calls into this file.  (zk_diag_vm_states, one more, reads vm_gpu.hip's
 // file-local VM state and lives there.)
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -1033,6 +1033,32 @@ extern "C" int zk_diag_merkle(int device, const uint8_t *leaves, size_t nl, int 
     ZK_CHECK_HIP(hipMemcpy(guard_out + G, d_nodes + heap, G, hipMemcpyDeviceToHost));
     ZK_CHECK_HIP(hipMemcpy(leaves_out, d_leaves, heap, hipMemcpyDeviceToHost));
     if (positions) ZK_TRY(batch_proof_bytes(nl, pos, d_leaves, d_nodes, proof_out, proof_len));
+    return ZK_OK;
+}
+
+// The CE layout conversion (ce_layout) on values of the caller's choice, with the launcher's grid cap given: `in` holds
+// 8 ext n elements, to_natural != 0: ext coset-major planes (plane[k][r n + q]) -> `out` in natural interleaved order
+// (component k of element r + 8 q at element (r + 8 q) ext + k); to_natural = 0: the inverse.  n in [1, 2^22], not
+// only the powers of two a proof has: a partial last tile is n mod 64 q-values.  max_blocks = 0: the launcher's own cap.
+// The destination lies between two guard regions of ZK_DIAG_CE_GUARD bytes, all three filled with 0xA5 before the
+// launch; guard_out: the lower guard, then the upper.
+constexpr size_t ZK_DIAG_CE_GUARD = 4096;
+extern "C" int zk_diag_ce_layout(int device, const uint8_t *in, size_t n, int ext, int to_natural, uint32_t max_blocks,
+                                 uint8_t *out, uint8_t *guard_out) {
+    if (!in || !out || !guard_out || n < 1 || n > ((size_t)1 << 22) || (ext != 1 && ext != 2) ||
+        max_blocks > (1u << 20))
+        ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_ce_layout: n in [1, 2^22], ext 1 or 2, max_blocks at most 2^20");
+    const size_t G = ZK_DIAG_CE_GUARD, bytes = (size_t)ext * 8 * n * sizeof(fe);
+    DiagBuf buf;  // source, lower guard, destination, upper guard
+    ZK_TRY(buf.alloc(device, 2 * bytes + 2 * G));
+    uint8_t *d_dst = buf.d + bytes + G;
+    ZK_CHECK_HIP(hipMemcpy(buf.d, in, bytes, hipMemcpyHostToDevice));
+    ZK_CHECK_HIP(hipMemset(buf.d + bytes, 0xA5, bytes + 2 * G));
+    ce_layout(nullptr, (const fe *)buf.d, n, ext, to_natural != 0, (fe *)d_dst, max_blocks);
+    ZK_CHECK_HIP(hipGetLastError());
+    ZK_CHECK_HIP(hipMemcpy(out, d_dst, bytes, hipMemcpyDeviceToHost));
+    ZK_CHECK_HIP(hipMemcpy(guard_out, d_dst - G, G, hipMemcpyDeviceToHost));
+    ZK_CHECK_HIP(hipMemcpy(guard_out + G, d_dst + bytes, G, hipMemcpyDeviceToHost));
     return ZK_OK;
 }
 

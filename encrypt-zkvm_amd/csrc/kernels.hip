@@ -3125,4 +3125,83 @@ void coset_major_to_natural(hipStream_t st, const fe *src, int log_n, int log_b,
     hipLaunchKernelGGL(k_coset_to_natural, dim3(blocks), dim3(256), 0, st, src, log_n, log_b, dst);
 }
 
+// ================================================================ CE layout conversion (the plug points' host order)
+// The library keeps the 8n composition values coset-major in EXT component planes, plane[k][r*n + q] (CE coset r < 8,
+// q < n); winterfell's CompositionPolyTrace is natural and interleaved: element i = r + 8q, component k, at fe index
+// i*EXT + k.  A direct gather has 16-byte segments strided by 16n on one side, so one block stages a tile of CE_TQ = 64
+// q-values x 8 cosets x EXT components (8 or 16 KiB) through LDS: on the plane side a wave moves one (k, r) row of 64
+// consecutive q (1 KiB contiguous), on the natural side the tile is one contiguous run of 512 EXT elements that the
+// 256 threads move in wave-contiguous pieces.
+// LDS image: element (q, c), c = r*EXT + k, at (q*CW + c) ^ swz(q), CW = 8 EXT, the XOR confined to the low four index
+// bits (one 256-B bank row).  Plane side: the lanes of a wave differ in q alone, and swz folds q's low four bits into
+// those index bits, so the 16 lanes of a ds_read_b128 group ({0-3,12-15,20-27}, ...: q distinct mod 16) take 16
+// different 16-B slots and the 8 lanes of a ds_write_b128 group 8 different slots mod 8.  Natural side: a group's lanes
+// are consecutive flat indices out of two bank rows, slots with bit 2 = bit 3 from one row and with bit 2 != bit 3
+// from the other; the XOR permutes within a row and keeps the two sets apart (EXT = 2: bit 2 ^ bit 3 of swz is q3,
+// shared by the rows q and q + 1; EXT = 1: slot bit 2 = r2 ^ q0 does not depend on q1, in which the rows differ), so
+// the group's 16 slots stay distinct.  Both sides conflict-free in both directions (the host model
+// in tests/plug_ext_ref.py enumerates every lane group).
+constexpr int CE_TQ = 64;
+template <int EXT>
+__device__ __forceinline__ int ce_lds(int q, int c) {
+    const int q0 = q & 1, q1 = (q >> 1) & 1, q2 = (q >> 2) & 1, q3 = (q >> 3) & 1;
+    const int swz = EXT == 1 ? (q3 << 3) | (q0 << 2) | (q1 << 1) | q2 : ((q0 ^ q3) << 3) | (q0 << 2) | (q2 << 1) | q1;
+    return (q * (8 * EXT) + c) ^ swz;
+}
+// TO_NAT: planes -> natural (src the planes, dst the interleaved values); else natural -> planes.  Grid-stride over the
+// tiles; a partial last tile (n < 64, or n no multiple of 64) moves its tq < 64 q-values only.
+template <int EXT, bool TO_NAT>
+__global__ void __launch_bounds__(256) k_ce_layout(const fe *src, size_t n, fe *dst) {
+    constexpr int CW = 8 * EXT;
+    __shared__ fe s[CE_TQ * CW];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const size_t tiles = (n + CE_TQ - 1) / CE_TQ;
+    for (size_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const size_t q0 = t * CE_TQ;
+        const int tq = (int)(n - q0 < (size_t)CE_TQ ? n - q0 : (size_t)CE_TQ);
+        if constexpr (TO_NAT) {
+            for (int c = wave; c < CW; c += 4)
+                if (lane < tq) s[ce_lds<EXT>(lane, c)] = ld_fe(src + ((size_t)(c % EXT) * 8 + c / EXT) * n + q0 + lane);
+            __syncthreads();
+            for (int f = tid; f < tq * CW; f += 256) st_fe(dst + q0 * CW + f, s[ce_lds<EXT>(f / CW, f % CW)]);
+        } else {
+            for (int f = tid; f < tq * CW; f += 256) s[ce_lds<EXT>(f / CW, f % CW)] = ld_fe(src + q0 * CW + f);
+            __syncthreads();
+            for (int c = wave; c < CW; c += 4)
+                if (lane < tq) st_fe(dst + ((size_t)(c % EXT) * 8 + c / EXT) * n + q0 + lane, s[ce_lds<EXT>(lane, c)]);
+        }
+        __syncthreads();  // the next round's tile overwrites the image
+    }
+}
+
+void ce_layout(hipStream_t st, const fe *src, size_t n, int ext, bool to_natural, fe *dst, unsigned max_blocks) {
+    const size_t tiles = (n + CE_TQ - 1) / CE_TQ;
+    const unsigned blocks = (unsigned)std::min<size_t>(tiles, max_blocks ? max_blocks : ZK_CE_LAYOUT_BLOCKS);
+    const double bytes = 2.0 * 16.0 * ext * 8.0 * (double)n;
+#define ZK_CE(E, D) ZK_PROF(st, D ? "ce_to_natural" : "ce_from_natural", bytes, hipLaunchKernelGGL((k_ce_layout<E, D>), dim3(blocks), dim3(256), 0, st, src, n, dst))
+    if (ext == 1) {
+        if (to_natural) ZK_CE(1, true);
+        else ZK_CE(1, false);
+    } else {
+        if (to_natural) ZK_CE(2, true);
+        else ZK_CE(2, false);
+    }
+#undef ZK_CE
+}
+
+// E column polynomials for the host: the composition stage leaves base column (c, k) of E column c at
+// (2c + k)*n; out element (c, i) holds (a, b) at fe index 2(c*n + i).  Even lanes read plane a, odd lanes plane b: a
+// wave's load is two contiguous 512-B runs, its store one contiguous KiB.
+__global__ void __launch_bounds__(256) k_interleave_columns(const fe *src, size_t n, size_t total, fe *dst) {
+    for (size_t t = blockIdx.x * (size_t)blockDim.x + threadIdx.x; t < total; t += (size_t)gridDim.x * blockDim.x) {
+        const size_t c = t / (2 * n), i = (t - c * 2 * n) >> 1;
+        st_fe(dst + t, ld_fe(src + (2 * c + (t & 1)) * n + i));
+    }
+}
+void interleave_columns(hipStream_t st, const fe *src, size_t n, int ncols, fe *dst) {
+    const size_t total = (size_t)2 * ncols * n;
+    const unsigned blocks = (unsigned)std::min<size_t>(cdiv(total, 256), 65536);
+    ZK_PROF(st, "interleave_columns", 32.0 * total, hipLaunchKernelGGL(k_interleave_columns, dim3(blocks), dim3(256), 0, st, src, n, total, dst));
+}
+
 }  // namespace zk

@@ -153,6 +153,7 @@ std::vector<fe> zk::periodic_table(size_t n) {
 }
 
 int zk::get_plan(zk_prover *p, size_t n, uint32_t B, Plan **out) {
+    p->kept_comp_ext = 0;  // whatever follows may overwrite composition values kept for the plug points
     auto key = std::make_pair(ilog2(n), ilog2(B));
     auto it = p->plans.find(key);
     if (it != p->plans.end()) {
@@ -2095,11 +2096,9 @@ int zk_host_unregister(void *ptr) {
 }
 
 // ---------------------------------------------------------------- plug point 1: trace LDE
-int zk_lde_new(zk_prover *p, const uint8_t *trace, size_t width, size_t n, uint32_t blowup, zk_trace_lde **out,
-               uint8_t root[32]) {
-    if (!p || !trace || !out) ZK_FAIL(ZK_ERR_INVALID_ARG, "null argument");
-    ZK_REQUIRE_FULL_PROVER(p);
-    if (width != (size_t)W) ZK_FAIL(ZK_ERR_INVALID_ARG, "ProcessorAir traces have 28 columns");
+// interpolate, extend and commit the 28 host columns; polys_out (optional): the 28 x n coefficients (TracePolyTable)
+static int lde_new_columns(zk_prover *p, const uint8_t *const *cols, size_t n, uint32_t blowup, zk_trace_lde **out,
+                           uint8_t root[32], uint8_t *polys_out) {
     if (n < 16 || (n & (n - 1)) || n > p->max_n || blowup < 8 || (blowup & (blowup - 1)) || blowup > p->max_b)
         ZK_FAIL(ZK_ERR_INVALID_ARG, "invalid trace length or blowup");
     ZK_CHECK_HIP(hipSetDevice(p->device));
@@ -2107,8 +2106,6 @@ int zk_lde_new(zk_prover *p, const uint8_t *trace, size_t width, size_t n, uint3
     Plan *pl;
     int rc = get_plan(p, n, blowup, &pl);
     if (rc) return rc;
-    const uint8_t *cols[W];
-    for (int c = 0; c < W; c++) cols[c] = trace + (size_t)c * n * sizeof(fe);
     TraceSrc src;
     src.cols = cols;
     src.hint_ok = false;  // no proof follows to verify a hint
@@ -2117,9 +2114,33 @@ int zk_lde_new(zk_prover *p, const uint8_t *trace, size_t width, size_t n, uint3
     if (!rc) rc = d2h_flush(p);
     upload_drain(p);  // the caller's trace is no longer read once this returns
     if (rc) return rc;
+    if (polys_out) {
+        // without hints no column is read at its source: every coefficient is in polys (the stream is idle: d2h_flush)
+        if (p->tc.coeff_src) ZK_FAIL(ZK_ERR_DEVICE, "trace coefficients were not written");
+        ZK_CHECK_HIP(hipMemcpy(polys_out, p->polys, (size_t)W * n * sizeof(fe), hipMemcpyDeviceToHost));
+    }
     if (root) memcpy(root, r, 32);
     *out = new zk_trace_lde{p, n, blowup, W};
     return ZK_OK;
+}
+
+int zk_lde_new(zk_prover *p, const uint8_t *trace, size_t width, size_t n, uint32_t blowup, zk_trace_lde **out,
+               uint8_t root[32]) {
+    if (!p || !trace || !out) ZK_FAIL(ZK_ERR_INVALID_ARG, "null argument");
+    ZK_REQUIRE_FULL_PROVER(p);
+    if (width != (size_t)W) ZK_FAIL(ZK_ERR_INVALID_ARG, "ProcessorAir traces have 28 columns");
+    const uint8_t *cols[W];
+    for (int c = 0; c < W; c++) cols[c] = trace + (size_t)c * n * sizeof(fe);
+    return lde_new_columns(p, cols, n, blowup, out, root, nullptr);
+}
+
+int zk_lde_new_columns(zk_prover *p, const uint8_t *const *columns, size_t n, uint32_t blowup, zk_trace_lde **out,
+                       uint8_t root[32], uint8_t *polys_out) {
+    if (!p || !columns || !out) ZK_FAIL(ZK_ERR_INVALID_ARG, "null argument");
+    ZK_REQUIRE_FULL_PROVER(p);
+    for (int c = 0; c < W; c++)
+        if (!columns[c]) ZK_FAIL(ZK_ERR_INVALID_ARG, "null trace column");
+    return lde_new_columns(p, columns, n, blowup, out, root, polys_out);
 }
 
 int zk_lde_read_frame(zk_trace_lde *h, size_t step, uint8_t *cur, uint8_t *next) {
@@ -2227,12 +2248,60 @@ int zk_eval_constraints(zk_trace_lde *h, const zk_pub_inputs *pub, const uint8_t
     return ZK_OK;
 }
 
+// The same over the challenge field: ext = 1 (the call above, byte for byte) or 2 (E coefficients and values as
+// (a, b) pairs of 16 bytes).  The evaluator leaves `ext` coset-major planes; ce_layout puts them in winterfell's order
+// on the device, so the host side is one contiguous copy.  out = NULL keeps the planes for zk_commit_composition_ext.
+int zk_eval_constraints_ext(zk_trace_lde *h, const zk_pub_inputs *pub, uint32_t ext, const uint8_t *coeff_t,
+                            const uint8_t *coeff_b, uint8_t *out) {
+    if (!h || !pub || !coeff_t || !coeff_b) ZK_FAIL(ZK_ERR_INVALID_ARG, "null argument");
+    if (ext != 1 && ext != 2) ZK_FAIL(ZK_ERR_INVALID_ARG, "ext must be 1 (base field) or 2 (quadratic extension)");
+    if (pub->lwe_size == 0 || pub->lwe_size > 5) ZK_FAIL(ZK_ERR_INVALID_ARG, "lwe_size must be in [1, 5]");
+    zk_prover *p = h->p;
+    const size_t n = h->n, CE = 8 * n;
+    const int KX = (int)ext;
+    ZK_CHECK_HIP(hipSetDevice(p->device));
+    if (KX == 2) ZK_TRY(ensure_ext(p));
+    Plan *pl;
+    ZK_TRY(get_plan(p, n, h->B, &pl));
+    const Planes b = planes(p, KX);
+    AirConsts K[2];
+    memset(K, 0, sizeof K);
+    for (int j = 0; j < KX; j++) {
+        for (int k = 0; k < NUM_TCONS; k++) K[j].coeff_t[k] = fe_from_bytes(coeff_t + 16 * (KX * k + j));
+        for (int k = 0; k < NUM_ASSERTS; k++) K[j].coeff_b[k] = fe_from_bytes(coeff_b + 16 * (KX * k + j));
+    }
+    const fe *per = air_static_consts(pub, n, K[0]);
+    if (KX == 2) {  // the b plane: the same constants around its own coefficients (draw_air_consts)
+        const AirConsts kb = K[1];
+        K[1] = K[0];
+        memcpy(K[1].coeff_t, kb.coeff_t, sizeof kb.coeff_t);
+        memcpy(K[1].coeff_b, kb.coeff_b, sizeof kb.coeff_b);
+        set_coeff_derived(K[1], per);
+    }
+    ZK_CHECK_HIP(hipMemcpyAsync(b.air_consts, K, KX * sizeof K[0], hipMemcpyHostToDevice, p->st));
+    const fe *binv = boundary_inverses(p, pl);
+    if (!binv) ZK_FAIL(ZK_ERR_OUT_OF_MEMORY, "boundary divisor table");
+    ZK_CHECK_HIP(eval_constraints(p->st, KX, p->lde, pl->log_n, eval_map_whole(pl->log_b, 8, true), pl->periodic, binv,
+                                  (const AirConsts *)b.air_consts, KX == 2 ? CE : 0, b.comp, true));
+    if (out) ce_layout(p->st, b.comp, n, KX, true, b.ctmp);
+    ZK_CHECK_HIP(hipStreamSynchronize(p->st));  // (K is read by the copy above until here)
+    collect_kernel_stats(p);  // (zk_prover_profile: a plug point's kernels are counted like a proof's)
+    if (out) {
+        ZK_CHECK_HIP(hipMemcpy(out, b.ctmp, (size_t)KX * CE * sizeof(fe), hipMemcpyDeviceToHost));
+    } else {
+        p->kept_comp_ext = KX;
+        p->kept_comp_lde = h;
+    }
+    return ZK_OK;
+}
+
 // ---------------------------------------------------------------- plug point 3: constraint commitment
 struct zk_comp_commit {
     zk_prover *p;
     size_t n;
     uint32_t B;
     int ncols;
+    int ext = 1;  // base elements per value: rows are ncols * ext elements of the plane set's composition LDE
 };
 
 int zk_commit_composition(zk_trace_lde *h, const uint8_t *composition, uint32_t num_cols, zk_comp_commit **out,
@@ -2263,12 +2332,55 @@ int zk_commit_composition(zk_trace_lde *h, const uint8_t *composition, uint32_t 
     return ZK_OK;
 }
 
+// The same over the challenge field.  composition: 8n values in winterfell's order, copied up whole and put into the
+// stage's coset-major planes by ce_layout; NULL: the planes zk_eval_constraints_ext(out = NULL) kept on this handle.
+int zk_commit_composition_ext(zk_trace_lde *h, const uint8_t *composition, uint32_t ext, uint32_t num_cols,
+                              zk_comp_commit **out, uint8_t root[32], uint8_t *polys_out) {
+    if (!h || !out) ZK_FAIL(ZK_ERR_INVALID_ARG, "null argument");
+    if (ext != 1 && ext != 2) ZK_FAIL(ZK_ERR_INVALID_ARG, "ext must be 1 (base field) or 2 (quadratic extension)");
+    if (num_cols < 1 || num_cols > 8) ZK_FAIL(ZK_ERR_INVALID_ARG, "num_cols must be in [1, 8]");
+    zk_prover *p = h->p;
+    const size_t n = h->n, CE = 8 * n;
+    const int KX = (int)ext, C = (int)num_cols;
+    if (!composition && (p->kept_comp_ext != KX || p->kept_comp_lde != h))
+        ZK_FAIL(ZK_ERR_INVALID_ARG, "no composition values of this ext are kept on the device for this trace LDE");
+    ZK_CHECK_HIP(hipSetDevice(p->device));
+    IoScope io_scope(p);
+    if (KX == 2) ZK_TRY(ensure_ext(p));
+    Plan *pl;
+    ZK_TRY(get_plan(p, n, h->B, &pl));  // (the kept values end here: the stage consumes them)
+    const Planes b = planes(p, KX);
+    if (composition) {
+        ZK_CHECK_HIP(hipMemcpyAsync(b.ctmp, composition, (size_t)KX * CE * sizeof(fe), hipMemcpyHostToDevice, p->st));
+        ce_layout(p->st, b.ctmp, n, KX, false, b.comp);
+    }
+    uint8_t r[32];
+    ZK_TRY(composition_stage(p, pl, KX, C, b.comp, b.ctmp, b.clde, r));
+    unsigned degree_flag = 0;
+    ZK_TRY(d2h_small(p, &degree_flag, p->flag, 4));
+    ZK_TRY(d2h_flush(p));  // root and flag
+    if (degree_flag) ZK_FAIL(ZK_ERR_DEGREE, "composition polynomial degree exceeds num_cols * trace_len");
+    if (polys_out) {
+        const fe *src = p->cpolys;
+        if (KX == 2) {  // the stage is done with the value planes: they stage the interleaved columns
+            interleave_columns(p->st, p->cpolys, n, C, b.comp);
+            ZK_CHECK_HIP(hipStreamSynchronize(p->st));
+            src = b.comp;
+        }
+        ZK_CHECK_HIP(hipMemcpy(polys_out, src, (size_t)KX * C * n * sizeof(fe), hipMemcpyDeviceToHost));
+    }
+    collect_kernel_stats(p);
+    if (root) memcpy(root, r, 32);
+    *out = new zk_comp_commit{p, n, h->B, C, KX};
+    return ZK_OK;
+}
+
 int zk_comp_query(zk_comp_commit *h, const uint64_t *positions, size_t k, uint8_t *rows_out, uint8_t *proof_out,
                   size_t *proof_len) {
     if (!h) ZK_FAIL(ZK_ERR_INVALID_ARG, "null argument");
     zk_prover *p = h->p;
-    return query_committed_rows(p, p->clde, h->ncols, h->n, h->B, p->cleaves, p->cnodes, positions, k, rows_out,
-                                proof_out, proof_len);
+    return query_committed_rows(p, planes(p, h->ext).clde, h->ncols * h->ext, h->n, h->B, p->cleaves, p->cnodes,
+                                positions, k, rows_out, proof_out, proof_len);
 }
 
 void zk_comp_free(zk_comp_commit *h) { delete h; }

@@ -308,6 +308,11 @@ struct zk_prover {
     fe *x_comp = nullptr, *x_ctmp = nullptr, *x_clde = nullptr, *x_deep = nullptr, *x_fri = nullptr,
        *x_partials = nullptr, *x_tab = nullptr;
     void *x_air = nullptr, *x_deep_consts = nullptr, *x_fold_consts = nullptr;
+    // Plug points: the composition values zk_eval_constraints_ext(out = NULL) left in comp / x_comp for the next
+    // zk_commit_composition_ext(composition = NULL) on the same trace LDE handle: the number of planes (0: none) and the
+    // handle.  Every entry point that computes in the prover's buffers looks its plan up first, and get_plan ends them.
+    int kept_comp_ext = 0;
+    const void *kept_comp_lde = nullptr;
     uint32_t *pow_seed = nullptr;            // grinding: the coin seed ...
     unsigned long long *pow_best = nullptr;  // ... and the smallest nonce found
     std::map<std::pair<int, int>, std::unique_ptr<zk::Plan>> plans;

@@ -522,6 +522,15 @@ void commit_fri_layer(hipStream_t st, int KX, const fe *layer, size_t L, int fol
 void fri_fold_launch(hipStream_t st, int KX, const fe *layer, size_t L, int fold, const void *fold_consts_dev,
                      const NttTables &TN, size_t wstride, fe *next, int lb = 0);
 void coset_major_to_natural(hipStream_t st, const fe *src, int log_n, int log_b, fe *dst);
+// The composition values between the library's layout and winterfell's (kernels.hip, CE layout conversion): `ext`
+// coset-major component planes of 8n values, plane[k][r*n + q], and the natural interleaved order, component k of
+// element i = r + 8q at fe index i*ext + k.  to_natural: src the planes, dst the natural values; else the inverse.
+// src and dst are distinct buffers of 8 ext n elements.  max_blocks = 0: the launcher's grid cap.
+constexpr unsigned ZK_CE_LAYOUT_BLOCKS = 2048;  // 8 blocks for each of 256 CUs; a block's LDS image is 8 ext KiB
+void ce_layout(hipStream_t st, const fe *src, size_t n, int ext, bool to_natural, fe *dst, unsigned max_blocks = 0);
+// The E column polynomials of a composition with two planes, base column (c, k) at src[(2c + k)*n], as ncols columns
+// of n interleaved (a, b) values in dst (2 ncols n elements, distinct from src)
+void interleave_columns(hipStream_t st, const fe *src, size_t n, int ncols, fe *dst);
 // FRI commit-phase coin on the device: seed = merge(seed, root_dev), alpha (k = 1 or 2 components) drawn
 // into alpha_dev (where the fold reads it) and alpha_log (the per-layer record the host replay is checked
 // against)

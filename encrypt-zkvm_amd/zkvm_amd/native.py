@@ -42,6 +42,7 @@ EXPORTED = (
     "zk_vm_prove_sharded",
     "zk_validate_device", "zk_validate_columns", "zk_prover_set_validate", "zk_prover_validation",
     "zk_degrees_device", "zk_degrees_columns", "zk_prover_set_validate_degrees", "zk_prover_degrees",
+    "zk_lde_new_columns", "zk_eval_constraints_ext", "zk_commit_composition_ext",
 )
 
 
@@ -252,6 +253,13 @@ def lib():
         L.zk_comp_query.argtypes = [vp, vp, sz, vp, vp, C.POINTER(sz)]
         L.zk_comp_free.argtypes = [vp]
         L.zk_comp_free.restype = None
+        if hasattr(L, "zk_lde_new_columns"):  # (an A/B library of an earlier commit, ZKVM_GPU_LIB, has none of the three)
+            # (p, columns[28], n, blowup, out, root, polys_out)
+            L.zk_lde_new_columns.argtypes = [vp, C.POINTER(vp), sz, u32, C.POINTER(vp), vp, vp]
+            # (lde, pub, ext, coeff_t, coeff_b, out)
+            L.zk_eval_constraints_ext.argtypes = [vp, C.POINTER(PubInputs), u32, vp, vp, vp]
+            # (lde, composition, ext, num_cols, out, root, polys_out)
+            L.zk_commit_composition_ext.argtypes = [vp, vp, u32, u32, C.POINTER(vp), vp, vp]
         L.zk_prover_stage_times.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), i32, C.POINTER(i32)]
         L.zk_prover_profile.argtypes = [vp, i32]
         L.zk_prover_set_upload_schedule.argtypes = [vp, i32]

@@ -321,6 +321,39 @@ int zk_comp_query(zk_comp_commit *comp, const uint64_t *positions, size_t k, uin
                   size_t *proof_len);
 void zk_comp_free(zk_comp_commit *comp);
 
+/* ---- the three plug points over the challenge field, with the polynomial tables ----
+ * winterfell's trait methods are generic over E: FieldElement<BaseField = f128>; with FieldExtension::Quadratic the
+ * composition coefficients, the CompositionPolyTrace<E> and the committed rows are E values.  Conventions of the calls
+ * below: ext = 1 (E = f128) or 2 (the quadratic extension); 3 is refused with ZK_ERR_INVALID_ARG, as in zk_options.
+ * An E element is 32 bytes: component a, then component b, 16 bytes little-endian each -- the form of the proof's own
+ * out-of-domain frame.  With ext = 1 every E buffer is the plain 16-byte layout of the calls above, and the results
+ * are theirs byte for byte.  Like them, the calls refuse a prover of zk_prover_create_shard. */
+/* Prover::new_trace_lde (prover/src/lib.rs:55-62) -> (DefaultTraceLde, TracePolyTable).  zk_lde_new with one pointer
+ * per column (n * 16 bytes each, winterfell's ColMatrix, as zk_prove_columns: no flattening copy) and the polynomial
+ * table: polys_out (optional) receives the 28 x n interpolation coefficients, column-major -- what winterfell builds
+ * the out-of-domain frame and the DEEP polynomial from.  The commitment runs without column hints, so every
+ * coefficient is written before it is copied out.  Same root and same LDE as zk_lde_new on the flattened trace. */
+int zk_lde_new_columns(zk_prover *p, const uint8_t *const *columns, size_t n, uint32_t blowup, zk_trace_lde **out,
+                       uint8_t root[32], uint8_t *polys_out);
+/* ConstraintEvaluator<E>::evaluate of DefaultConstraintEvaluator (Prover::new_evaluator, prover/src/lib.rs:65-72):
+ * coeff_t = 20 and coeff_b = 22 E elements (the ConstraintCompositionCoefficients<E> the channel draws), out = the 8n
+ * E values of the CompositionPolyTrace<E> in natural CE-domain order.  The trace and the constraints are base-field,
+ * so each component of out is zk_eval_constraints with that component of every coefficient.  out = NULL: the values
+ * stay in the prover's device memory for a zk_commit_composition_ext(composition = NULL) on this handle; any proof,
+ * commitment, evaluation or check on the prover in between ends their validity. */
+int zk_eval_constraints_ext(zk_trace_lde *lde, const zk_pub_inputs *pub, uint32_t ext, const uint8_t *coeff_t,
+                            const uint8_t *coeff_b, uint8_t *out);
+/* Prover::build_constraint_commitment over E (winterfell 0.9 provided method): composition = 8n E
+ * values in natural CE-domain order, or NULL for the values the last zk_eval_constraints_ext(out = NULL) on this handle
+ * left on the device with the same ext (ZK_ERR_INVALID_ARG if there are none, if ext differs, or if a proof or another
+ * commitment has run on the prover since: that ends the validity of the retained values).  num_cols in [1, 8];
+ * polys_out (optional): num_cols x n E elements, column-major -- the columns of CompositionPoly.  ZK_ERR_DEGREE (no
+ * handle) when either component has a non-zero coefficient at or beyond num_cols * n.  The handle records ext:
+ * zk_comp_query on it returns rows of num_cols E elements, and its batch Merkle proof is over leaves BLAKE3(row
+ * bytes), as the whole-proof path commits them. */
+int zk_commit_composition_ext(zk_trace_lde *lde, const uint8_t *composition, uint32_t ext, uint32_t num_cols,
+                              zk_comp_commit **out, uint8_t root[32], uint8_t *polys_out);
+
 /* ---- one proof sharded over several GPUs ----
  * The LDE domain is split by coset: rank g of `world` (1, 2, 4 or 8; blowup 8) owns the block of cosets
  * g * 8/world .. (g + 1) * 8/world - 1.  Exchanges (Merkle block nodes, composition coefficient slices, FRI layer 1,
