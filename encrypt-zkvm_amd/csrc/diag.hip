@@ -1062,6 +1062,41 @@ extern "C" int zk_diag_ce_layout(int device, const uint8_t *in, size_t n, int ex
     return ZK_OK;
 }
 
+// The bulk row read (rows_to_host: rows_layout chunk by chunk, then contiguous copies) on planes of the caller's
+// choice: `planes` holds ncols * blowup * n elements, element (c, i) at (c*blowup + i mod blowup)*n + i div blowup; out
+// takes rows (first + k) mod N, k < count, of ncols elements.  n in [1, 2^22], not only the powers of two an LDE has;
+// blowup 8, 16, 32 or 64; ncols in [1, 28]; first < N; 1 <= count <= N + blowup.  max_blocks = 0: the launcher's own
+// cap.  cap_rows: the rows the staging buffer holds, so small shapes cross chunk boundaries; 0: the 28 * 8 * n / ncols a
+// prover of this size gives.  The staging buffer lies between two guard regions of ZK_DIAG_ROWS_GUARD bytes, all three
+// filled with 0xA5 before the first launch; guard_out: the lower guard, then the upper.
+constexpr size_t ZK_DIAG_ROWS_GUARD = 4096;
+extern "C" int zk_diag_rows_layout(int device, const uint8_t *planes, size_t n, uint32_t blowup, int ncols, size_t first,
+                                   size_t count, uint32_t max_blocks, size_t cap_rows, uint8_t *out,
+                                   uint8_t *guard_out) {
+    if (!planes || !out || !guard_out || n < 1 || n > ((size_t)1 << 22) || blowup < 8 || blowup > 64 ||
+        (blowup & (blowup - 1)) || ncols < 1 || ncols > 28 || max_blocks > (1u << 20))
+        ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_rows_layout: n in [1, 2^22], blowup 8 .. 64, ncols in [1, 28], max_blocks at "
+                                    "most 2^20");
+    const size_t N = n * blowup;
+    if (first >= N || count == 0 || count > N + blowup)
+        ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_rows_layout: first below N and 1 <= count <= N + blowup");
+    if (!cap_rows) cap_rows = std::max<size_t>((size_t)W * 8 * n / ncols, 1);
+    cap_rows = std::min(cap_rows, N);
+    const size_t G = ZK_DIAG_ROWS_GUARD, src_bytes = (size_t)ncols * N * sizeof(fe),
+                 stage_bytes = cap_rows * ncols * sizeof(fe);
+    DiagBuf buf;  // source, lower guard, staging buffer, upper guard
+    ZK_TRY(buf.alloc(device, src_bytes + stage_bytes + 2 * G));
+    uint8_t *d_stage = buf.d + src_bytes + G;
+    ZK_CHECK_HIP(hipMemcpy(buf.d, planes, src_bytes, hipMemcpyHostToDevice));
+    ZK_CHECK_HIP(hipMemset(buf.d + src_bytes, 0xA5, stage_bytes + 2 * G));
+    ZK_TRY(rows_to_host(nullptr, (const fe *)buf.d, ncols, n, blowup, first, count, (fe *)d_stage, cap_rows, out,
+                        max_blocks));
+    ZK_CHECK_HIP(hipGetLastError());
+    ZK_CHECK_HIP(hipMemcpy(guard_out, d_stage - G, G, hipMemcpyDeviceToHost));
+    ZK_CHECK_HIP(hipMemcpy(guard_out + G, d_stage + stage_bytes, G, hipMemcpyDeviceToHost));
+    return ZK_OK;
+}
+
 // One grind_launch over the nonces [start, start + count) with the result preset to ~0: *best_out = the smallest
 // nonce whose BLAKE3(seed32 || nonce_le64) starts with >= bits trailing zero bits, ~0 when the window holds none.
 extern "C" int zk_diag_grind(int device, const uint8_t *seed32, uint64_t start, uint32_t count, int bits,

@@ -3189,6 +3189,57 @@ void ce_layout(hipStream_t st, const fe *src, size_t n, int ext, bool to_natural
 #undef ZK_CE
 }
 
+// ================================================================ committed LDEs as row matrices (the plug points' bulk reads)
+// A committed LDE lies coset-major: element (column c, LDE index i) at ((c*B + i mod B)*n + i div B).  winterfell's
+// RowMatrix is natural and row-major: row i at i*ncols + c.  One block stages a tile of ROWS_TR = 64 consecutive rows
+// (TQ = 64 / B values of i div B x B cosets) x ncols columns through LDS.  Plane side: a wave moves the 64 elements of
+// one column, lane u = (i mod B)*TQ + (i div B - q0): B runs of TQ consecutive elements (128 B at blowup 8, 16 B at
+// blowup 64).  Row side: the tile is one contiguous run of 64 ncols elements, which the 256 threads move in
+// wave-contiguous KiB pieces.
+// LDS image: element (c, u) at c*ROWS_LS + u, ROWS_LS = 65: a column's 64 elements and one of padding (28 columns:
+// 29120 bytes, five blocks to a CU).  Plane side: a wave writes 64 consecutive slots, conflict-free.  Row side: the lanes
+// of a group hold consecutive columns of one row, slots c*65 + u = c + u (mod 16): distinct until the row ends, where
+// the next row's u starts the count again (at most a two-way conflict in the groups that span two rows).
+constexpr int ROWS_TR = 64, ROWS_LS = ROWS_TR + 1;
+// Rows [first, first + count) of the domain, first + count <= n B (the launcher splits a window that wraps): row i of
+// them at dst + (i - first)*ncols.  Grid-stride over the tiles that meet the window; the first and the last tile store
+// their rows inside the window only, and a last tile past the domain's end (n no multiple of TQ) loads its n mod TQ
+// values of i div B alone.
+__global__ void __launch_bounds__(256) k_rows_layout(const fe *src, int ncols, size_t n, int log_b, size_t first, size_t count, fe *dst) {
+    extern __shared__ fe rows_s[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int log_tq = 6 - log_b, tq_mask = (1 << log_tq) - 1, b_mask = (1 << log_b) - 1;
+    const size_t B = (size_t)1 << log_b, end = first + count;
+    const size_t t0 = first / ROWS_TR, tiles = (end + ROWS_TR - 1) / ROWS_TR - t0;
+    const int dq = 256 / ncols, dc = 256 % ncols;  // the step of (row, column) between a thread's elements
+    for (size_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const size_t i0 = (t0 + t) * ROWS_TR, q = (i0 >> log_b) + (lane & tq_mask);
+        const int r = lane >> log_tq;
+        if (q < n)
+            for (int c = wave; c < ncols; c += 4) rows_s[c * ROWS_LS + lane] = ld_fe(src + ((size_t)c * B + r) * n + q);
+        __syncthreads();
+        int rl = tid / ncols, c = tid % ncols;
+        for (int f = tid; f < ROWS_TR * ncols; f += 256) {
+            const size_t i = i0 + rl;
+            if (i >= first && i < end)
+                st_fe(dst + (i - first) * ncols + c, rows_s[c * ROWS_LS + (((rl & b_mask) << log_tq) | (rl >> log_b))]);
+            rl += dq, c += dc;
+            if (c >= ncols) c -= ncols, rl++;
+        }
+        __syncthreads();  // the next round's tile overwrites the image
+    }
+}
+
+void rows_layout(hipStream_t st, const fe *base, int ncols, size_t n, int log_b, size_t first, size_t count, fe *dst,
+                 unsigned max_blocks) {
+    if (!count) return;
+    const size_t tiles = (first + count + ROWS_TR - 1) / ROWS_TR - first / ROWS_TR;
+    const unsigned blocks = (unsigned)std::min<size_t>(tiles, max_blocks ? max_blocks : ZK_ROWS_LAYOUT_BLOCKS);
+    const size_t lds = (size_t)ncols * ROWS_LS * sizeof(fe);
+    ZK_PROF(st, "rows_to_natural", 2.0 * 16.0 * ncols * (double)count,
+            hipLaunchKernelGGL(k_rows_layout, dim3(blocks), dim3(256), lds, st, base, ncols, n, log_b, first, count, dst));
+}
+
 // E column polynomials for the host: the composition stage leaves base column (c, k) of E column c at
 // (2c + k)*n; out element (c, i) holds (a, b) at fe index 2(c*n + i).  Even lanes read plane a, odd lanes plane b: a
 // wave's load is two contiguous 512-B runs, its store one contiguous KiB.

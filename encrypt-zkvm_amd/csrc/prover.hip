@@ -2221,6 +2221,46 @@ int zk_lde_query(zk_trace_lde *h, const uint64_t *positions, size_t k, uint8_t *
                                 proof_len);
 }
 
+// The plug points' bulk reads: rows (first + k) mod N, k < count, of a committed coset-major LDE as a row matrix in
+// `out`.  rows_layout forms up to cap_rows rows at a time in `stage` and a contiguous copy takes them to the host,
+// kernel and copy in order on st (the kernel is a few per cent of the copy), one synchronisation at the end.  A chunk
+// ends at the domain's end, where a window that wraps starts again at row 0, so no launch wraps.
+int zk::rows_to_host(hipStream_t st, const fe *base, int ncols, size_t n, uint32_t B, size_t first, size_t count,
+                     fe *stage, size_t cap_rows, uint8_t *out, unsigned max_blocks) {
+    const size_t N = n * B, row = (size_t)ncols * sizeof(fe);
+    const int log_b = ilog2(B);
+    for (size_t done = 0; done < count;) {
+        const size_t f = (first + done) % N, c = std::min({count - done, N - f, cap_rows});
+        rows_layout(st, base, ncols, n, log_b, f, c, stage, max_blocks);
+        ZK_CHECK_HIP(hipMemcpyAsync(out + done * row, stage, c * row, hipMemcpyDeviceToHost, st));
+        done += c;
+    }
+    ZK_CHECK_HIP(hipStreamSynchronize(st));
+    return ZK_OK;
+}
+
+// Both read calls stage in p->tmp (28 x 8 max_n elements: 8 max_n rows of 28, more of a narrower row).  It is the
+// scratch of the NTTs, the degree check and the VM's trace generation, written and read within one call each on p->st;
+// nothing a handle, the kept composition values, the hints or a snapshot hold lives there (the LDEs are in lde / clde
+// / x_clde, the kept values in comp / x_comp, the snapshots in buffers of their own), and no plan is fetched, so the
+// kept values stay valid.
+static int read_committed_rows(zk_prover *p, const fe *base, int ncols, size_t n, uint32_t B, size_t first,
+                               size_t count, uint8_t *rows_out) {
+    if (!rows_out) ZK_FAIL(ZK_ERR_INVALID_ARG, "null argument");
+    if (first >= n * B || count == 0 || count > n * B + B)
+        ZK_FAIL(ZK_ERR_INVALID_ARG, "first below N and 1 <= count <= N + blowup");
+    ZK_CHECK_HIP(hipSetDevice(p->device));
+    const size_t cap_rows = (size_t)W * 8 * p->max_n / ncols;
+    ZK_TRY(rows_to_host(p->st, base, ncols, n, B, first, count, p->tmp, cap_rows, rows_out, 0));
+    collect_kernel_stats(p);
+    return ZK_OK;
+}
+
+int zk_lde_read_rows(zk_trace_lde *h, size_t first, size_t count, uint8_t *rows_out) {
+    if (!h) ZK_FAIL(ZK_ERR_INVALID_ARG, "null argument");
+    return read_committed_rows(h->p, h->p->lde, W, h->n, h->B, first, count, rows_out);
+}
+
 void zk_lde_free(zk_trace_lde *h) { delete h; }
 
 // ---------------------------------------------------------------- plug point 2: constraint evaluation
@@ -2381,6 +2421,11 @@ int zk_comp_query(zk_comp_commit *h, const uint64_t *positions, size_t k, uint8_
     zk_prover *p = h->p;
     return query_committed_rows(p, planes(p, h->ext).clde, h->ncols * h->ext, h->n, h->B, p->cleaves, p->cnodes,
                                 positions, k, rows_out, proof_out, proof_len);
+}
+
+int zk_comp_read_rows(zk_comp_commit *h, size_t first, size_t count, uint8_t *rows_out) {
+    if (!h) ZK_FAIL(ZK_ERR_INVALID_ARG, "null argument");
+    return read_committed_rows(h->p, planes(h->p, h->ext).clde, h->ncols * h->ext, h->n, h->B, first, count, rows_out);
 }
 
 void zk_comp_free(zk_comp_commit *h) { delete h; }

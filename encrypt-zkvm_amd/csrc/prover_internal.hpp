@@ -632,6 +632,10 @@ void plan_batch(size_t nl, const std::vector<uint64_t> &idx, BatchPlan &out);  /
 int query_positions(const uint64_t *positions, size_t k, size_t N, std::vector<uint64_t> &pos);
 int batch_proof_bytes(size_t N, const std::vector<uint64_t> &pos, const uint8_t *leaves, const uint8_t *nodes,
                       uint8_t *proof_out, size_t *proof_len);
+// The bulk reads (zk_lde_read_rows, zk_comp_read_rows, zk_diag_rows_layout): rows (first + k) mod n B, k < count, of a
+// coset-major LDE into the host's `out`, formed cap_rows at a time in the device buffer `stage` (prover.hip)
+int rows_to_host(hipStream_t st, const fe *base, int ncols, size_t n, uint32_t B, size_t first, size_t count, fe *stage,
+                 size_t cap_rows, uint8_t *out, unsigned max_blocks);
 
 // ---------------------------------------------------------------- protocol steps (host side)
 // argument checks shared by every prove entry point; returns ZK_OK or a status (g_err set)

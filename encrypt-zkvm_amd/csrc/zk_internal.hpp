@@ -528,6 +528,12 @@ void coset_major_to_natural(hipStream_t st, const fe *src, int log_n, int log_b,
 // src and dst are distinct buffers of 8 ext n elements.  max_blocks = 0: the launcher's grid cap.
 constexpr unsigned ZK_CE_LAYOUT_BLOCKS = 2048;  // 8 blocks for each of 256 CUs; a block's LDS image is 8 ext KiB
 void ce_layout(hipStream_t st, const fe *src, size_t n, int ext, bool to_natural, fe *dst, unsigned max_blocks = 0);
+// Rows [first, first + count) of a coset-major LDE (element (c, i) at base[(c*B + i mod B)*n + i div B], B = 2^log_b,
+// log_b in [3, 6], ncols in [1, 28], any n >= 1) as a row matrix: row i at dst + (i - first)*ncols.  first + count
+// <= n B: the caller splits a window that wraps.  max_blocks = 0: the launcher's own cap.
+constexpr unsigned ZK_ROWS_LAYOUT_BLOCKS = 1280;  // 5 blocks for each of 256 CUs; a block's LDS image is 1040 ncols bytes
+void rows_layout(hipStream_t st, const fe *base, int ncols, size_t n, int log_b, size_t first, size_t count, fe *dst,
+                 unsigned max_blocks = 0);
 // The E column polynomials of a composition with two planes, base column (c, k) at src[(2c + k)*n], as ncols columns
 // of n interleaved (a, b) values in dst (2 ncols n elements, distinct from src)
 void interleave_columns(hipStream_t st, const fe *src, size_t n, int ncols, fe *dst);

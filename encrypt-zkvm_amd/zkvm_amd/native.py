@@ -43,6 +43,7 @@ EXPORTED = (
     "zk_validate_device", "zk_validate_columns", "zk_prover_set_validate", "zk_prover_validation",
     "zk_degrees_device", "zk_degrees_columns", "zk_prover_set_validate_degrees", "zk_prover_degrees",
     "zk_lde_new_columns", "zk_eval_constraints_ext", "zk_commit_composition_ext",
+    "zk_lde_read_rows", "zk_comp_read_rows",
 )
 
 
@@ -260,6 +261,10 @@ def lib():
             L.zk_eval_constraints_ext.argtypes = [vp, C.POINTER(PubInputs), u32, vp, vp, vp]
             # (lde, composition, ext, num_cols, out, root, polys_out)
             L.zk_commit_composition_ext.argtypes = [vp, vp, u32, u32, C.POINTER(vp), vp, vp]
+        if hasattr(L, "zk_lde_read_rows"):  # (likewise: the bulk reads came later)
+            # (handle, first, count, rows_out)
+            L.zk_lde_read_rows.argtypes = [vp, sz, sz, vp]
+            L.zk_comp_read_rows.argtypes = [vp, sz, sz, vp]
         L.zk_prover_stage_times.argtypes = [vp, C.POINTER(C.c_char_p), C.POINTER(C.c_float), i32, C.POINTER(i32)]
         L.zk_prover_profile.argtypes = [vp, i32]
         L.zk_prover_set_upload_schedule.argtypes = [vp, i32]

@@ -8,9 +8,11 @@ package.  An E value (ext = 2, FieldExtension::Quadratic) is two of them, compon
     lde, polys = TraceLde.new(gpu, trace, blowup=8, polys=True)   # new_trace_lde -> (TraceLde, TracePolyTable)
     cur, nxt = lde.read_frame(step)                               # TraceLde::read_main_trace_frame_into
     rows, proof = lde.query(positions)                            # TraceLde::query
+    matrix = lde.read_rows()                                      # DefaultTraceLde's RowMatrix, (N, 28, 2)
     comp = lde.evaluate(pub, coeff_t, coeff_b, ext=2)             # ConstraintEvaluator::evaluate
     cc, cpolys = ConstraintCommitment.commit(lde, comp, ext=2, num_cols=7, polys=True)
     rows, proof = cc.query(positions)                             # ConstraintCommitment::query
+    evaluations = cc.read_rows()                                  # its RowMatrix<E>, (N, num_cols, [2,] 2)
 """
 from __future__ import annotations
 
@@ -44,6 +46,17 @@ def _query(call, positions, row_shape):
     proof, plen = C.create_string_buffer(PROOF_CAP), C.c_size_t(PROOF_CAP)
     check(call(pos.ctypes.data, len(pos), rows.ctypes.data, proof, C.byref(plen)), "query")
     return rows, proof.raw[:plen.value]
+
+
+def _read_rows(call, what, N, first, count, out, row_shape):
+    count = N if count is None else count
+    if out is None:
+        out = np.empty((max(count, 0), *row_shape), dtype=np.uint64)
+    elif (not isinstance(out, np.ndarray) or out.dtype != np.uint64 or out.shape != (count, *row_shape)
+          or not out.flags.c_contiguous or not out.flags.writeable):
+        raise ValueError(f"out: expected a writeable C-contiguous uint64 array of shape {(count, *row_shape)}")
+    check(call(first, count, out.ctypes.data if out.size else None), what)
+    return out
 
 
 class TraceLde:
@@ -80,6 +93,14 @@ class TraceLde:
         """TraceLde::query: (rows (k, 28, 2), BatchMerkleProof bytes) at k distinct positions."""
         return _query(lambda *a: lib().zk_lde_query(self.handle, *a), positions, (WIDTH, 2))
 
+    def read_rows(self, first: int = 0, count: int | None = None, out: np.ndarray | None = None):
+        """A slice of DefaultTraceLde's main segment RowMatrix: rows (first + k) mod N, k < count (all N from `first` on
+        when count is None; at most N + blowup, so a window of frames may wrap), (count, 28, 2).  out: the caller's
+        array of that shape, for instance one over page-locked memory (zk_host_alloc), which the copies fill at the link
+        rate."""
+        return _read_rows(lambda *a: lib().zk_lde_read_rows(self.handle, *a), "zk_lde_read_rows", self.n * self.blowup,
+                          first, count, out, (WIDTH, 2))
+
     def evaluate(self, pub: PubInputs, coeff_t, coeff_b, ext: int = 1, keep_on_device: bool = False):
         """ConstraintEvaluator::evaluate: coeff_t (20, [2,] 2) and coeff_b (22, [2,] 2) -> the CompositionPolyTrace,
         (8n, [2,] 2) in natural CE-domain order.  keep_on_device: nothing comes back (None); the values stay on the GPU
@@ -107,8 +128,8 @@ class ConstraintCommitment:
     """ConstraintCommitment: the composition columns' LDE and its row commitment, valid until the next proof or
     commitment on the prover."""
 
-    def __init__(self, handle, n: int, ext: int, num_cols: int, root: bytes):
-        self.handle, self.n, self.ext, self.num_cols, self.root = handle, n, ext, num_cols, root
+    def __init__(self, handle, n: int, ext: int, num_cols: int, root: bytes, blowup: int = 8):
+        self.handle, self.n, self.ext, self.num_cols, self.root, self.blowup = handle, n, ext, num_cols, root, blowup
 
     @classmethod
     def commit(cls, lde: TraceLde, composition, ext: int = 1, num_cols: int = 8, polys: bool = False):
@@ -122,12 +143,18 @@ class ConstraintCommitment:
         check(lib().zk_commit_composition_ext(lde.handle, None if comp is None else comp.ctypes.data, ext, num_cols,
                                               C.byref(h), root, table.ctypes.data if polys else None),
               "zk_commit_composition_ext")
-        cc = cls(h, lde.n, ext, num_cols, root.raw)
+        cc = cls(h, lde.n, ext, num_cols, root.raw, lde.blowup)
         return (cc, table) if polys else cc
 
     def query(self, positions):
         """ConstraintCommitment::query: (rows (k, num_cols, [2,] 2), BatchMerkleProof bytes) at k distinct positions."""
         return _query(lambda *a: lib().zk_comp_query(self.handle, *a), positions, _eshape(self.ext, self.num_cols))
+
+    def read_rows(self, first: int = 0, count: int | None = None, out: np.ndarray | None = None):
+        """The evaluations ConstraintCommitment keeps as a RowMatrix<E>: rows (first + k) mod N, k < count (N when
+        count is None), (count, num_cols, [2,] 2), each as query returns it.  out: as in TraceLde.read_rows."""
+        return _read_rows(lambda *a: lib().zk_comp_read_rows(self.handle, *a), "zk_comp_read_rows",
+                          self.n * self.blowup, first, count, out, _eshape(self.ext, self.num_cols))
 
     def close(self):
         if self.handle:
@@ -163,3 +190,34 @@ def ce_natural_order(n: int, ext: int) -> np.ndarray:
     t = np.arange(8 * ext * n)
     i, k = t // ext, t % ext
     return (8 * k + i % 8) * n + i // 8
+
+
+# ---- the bulk row read called directly (csrc/diag.hip), for the tests
+ROWS_GUARD = 4096  # bytes on each side of the staging buffer
+ROWS_TILE = 64     # rows of one tile of the kernel
+
+
+def rows_layout_direct(planes: np.ndarray, n: int, blowup: int, ncols: int, first: int = 0, count: int | None = None,
+                       max_blocks: int = 0, cap_rows: int = 0, device: int = 0):
+    """The production launcher and chunk loop on planes of the caller's choice: planes holds ncols blowup n elements,
+    (…, 2) uint64, element (c, i) at (c blowup + i mod blowup) n + i div blowup.  cap_rows: the rows the staging buffer
+    holds (0: a prover's own), so that small shapes cross chunk boundaries.  Returns (rows (count, ncols, 2), guard
+    bytes around the staging buffer: the lower region, then the upper, 0xA5 each when untouched)."""
+    f = lib().zk_diag_rows_layout
+    f.argtypes = [C.c_int, C.c_void_p, C.c_size_t, C.c_uint32, C.c_int, C.c_size_t, C.c_size_t, C.c_uint32, C.c_size_t,
+                  C.c_void_p, C.c_void_p]
+    src = _elems(np.asarray(planes).reshape(-1, 2), (max(ncols, 0) * blowup * n, 2), "planes")
+    count = n * blowup if count is None else count
+    out, guard = np.empty((max(count, 0), max(ncols, 0), 2), dtype=np.uint64), C.create_string_buffer(2 * ROWS_GUARD)
+    check(f(device, src.ctypes.data, n, blowup, ncols, first, count, max_blocks, cap_rows, out.ctypes.data, guard),
+          "rows_layout_direct")
+    return out, guard.raw
+
+
+def rows_natural_order(n: int, blowup: int, ncols: int, first: int = 0, count: int | None = None) -> np.ndarray:
+    """The permutation the read applies: rows.reshape(-1)[k ncols + c] = planes.reshape(-1)[perm[k, c]] for row
+    i = (first + k) mod N of the window, perm[k, c] = (c blowup + i mod blowup) n + i div blowup; (count, ncols)."""
+    N = n * blowup
+    i = (first + np.arange(N if count is None else count, dtype=np.int64)) % N
+    c = np.arange(ncols, dtype=np.int64)
+    return (c[None, :] * blowup + (i % blowup)[:, None]) * n + (i // blowup)[:, None]

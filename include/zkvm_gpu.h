@@ -295,6 +295,17 @@ int zk_lde_read_frame(zk_trace_lde *lde, size_t lde_step, uint8_t *cur, uint8_t 
  * zk_comp_query takes the same. */
 int zk_lde_query(zk_trace_lde *lde, const uint64_t *positions, size_t k, uint8_t *rows_out, uint8_t *proof_out,
                  size_t *proof_len);
+/* A slice of DefaultTraceLde's main segment RowMatrix (Prover::new_trace_lde, prover/src/lib.rs:55-62): rows
+ * (first + k) mod N, k < count, of the trace LDE in natural order, row-major, 28 elements of 16 bytes each.  The
+ * frame TraceLde::read_main_trace_frame_into(s) reads is rows s and s + blowup of it.  first < N, 1 <= count <=
+ * N + blowup (a window of frames may run past the end of the domain: it wraps).  The layout change runs on the GPU;
+ * rows_out takes contiguous copies (page-locked memory, zk_host_alloc / zk_host_register: at the link rate).
+ * ZK_ERR_INVALID_ARG, before any launch and with rows_out untouched: a NULL handle or buffer, first >= N, count == 0,
+ * count > N + blowup.  The call reads the prover's device state and writes its NTT scratch only: both kinds of
+ * handle stay valid, so do the composition values a zk_eval_constraints_ext(out = NULL) left for
+ * zk_commit_composition_ext(NULL), and no hint, snapshot or proof state is touched -- a proof on the prover afterwards
+ * has the bytes it would have had.  zk_comp_read_rows keeps all of this too. */
+int zk_lde_read_rows(zk_trace_lde *lde, size_t first, size_t count, uint8_t *rows_out);
 void zk_lde_free(zk_trace_lde *lde);
 
 /* ---- plug point 2: Prover::new_evaluator (prover/src/lib.rs:65-72) + evaluate ----
@@ -319,6 +330,10 @@ int zk_commit_composition(zk_trace_lde *lde, const uint8_t *composition, uint32_
 /* ConstraintCommitment::query: rows (num_cols elements each) at positions + batch Merkle proof bytes */
 int zk_comp_query(zk_comp_commit *comp, const uint64_t *positions, size_t k, uint8_t *rows_out, uint8_t *proof_out,
                   size_t *proof_len);
+/* The same as zk_lde_read_rows for ConstraintCommitment's evaluations (winterfell keeps them as a RowMatrix<E>):
+ * rows (first + k) mod N, k < count, of num_cols E elements (ext = 2: 32 bytes each, a then b), as zk_comp_query
+ * returns them.  The same refusals and the same guarantees: nothing but the prover's NTT scratch is written. */
+int zk_comp_read_rows(zk_comp_commit *comp, size_t first, size_t count, uint8_t *rows_out);
 void zk_comp_free(zk_comp_commit *comp);
 
 /* ---- the three plug points over the challenge field, with the polynomial tables ----

@@ -13,6 +13,20 @@ on one warm prover in one process, old and new alternating.
     moves (each element read once and written once) over that time.
 
 Usage (GPU box): python3 tools/plug_time.py [log_n] [reps]    (profiles/plug_ext_time.txt keeps one run's output)
+
+`python3 tools/plug_time.py rows [log_n] [reps]` measures the bulk row reads instead (zk_lde_read_rows,
+zk_comp_read_rows; profiles/lde_rows_time.txt), on a random trace -- an LDE costs the same whatever it extends:
+
+  * the whole trace LDE (N x 28 x 16 B) into a page-locked buffer against a plain hipMemcpy of as many bytes from a
+    device buffer of that size into the same host buffer, alternating.  The library has no call that hands out the
+    address of its LDE, so the yardstick copies from an allocation of its own.  In order on one stream the read should
+    cost the copy plus the layout kernel: it passes if median(read) <= median(copy) (1 + s) + kernel time, s the copy's
+    own (max - min) / median, the kernel time from zk_prover_kernel_stats of profiled calls;
+  * the same read into a pageable buffer;
+  * 4096 consecutive frames through zk_lde_read_frame, scaled to the 8n calls an evaluator makes (extrapolated);
+  * zk_comp_read_rows of an ext = 2, 8-column commitment in the same manner;
+  * the layout kernel's rate (each element read once and written once, over the device time between HIP events), at
+    blowup 8 and, on a prover of the same size (half the trace length), at blowup 16.
 """
 import ctypes as C
 import statistics
@@ -59,7 +73,98 @@ def rand_elems(rng, *shape):
     return a
 
 
+def rows_main(log_n, reps):
+    from zkvm_amd.plug import ConstraintCommitment
+
+    L = native.lib()
+    hip = C.CDLL("libamdhip64.so")
+    hip.hipMalloc.argtypes = [C.POINTER(C.c_void_p), C.c_size_t]
+    hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    hip.hipFree.argtypes = [C.c_void_p]
+    D2H = 2
+    n = 1 << log_n
+    rng = np.random.default_rng(1)
+    pub = make_pub_inputs([1, 2], list(range(16)), 5, 16)
+    print(f"n = 2^{log_n}, blowup 8, {reps} calls each, read and plain copy alternating")
+
+    def pinned(nbytes):
+        p = C.c_void_p()
+        native.check(L.zk_host_alloc(nbytes, C.byref(p)))
+        C.memset(p, 0, nbytes)
+        return p
+
+    def measure(what, g, read, nbytes, kernel_calls=5):
+        """read(pointer) fills nbytes of host memory; -> median of the page-locked read"""
+        host, dev = pinned(nbytes), C.c_void_p()
+        assert hip.hipMalloc(C.byref(dev), nbytes) == 0
+        pageable = np.zeros(nbytes, dtype=np.uint8)
+
+        def copy():
+            assert hip.hipMemcpy(host, dev, nbytes, D2H) == 0
+
+        copy(), read(host.value), read(pageable.ctypes.data)  # warm
+        assert C.string_at(host.value + nbytes - 4096, 4096) == pageable[-4096:].tobytes()
+        tr, tc = alternate(reps, [lambda: read(host.value), copy])
+        a = line(f"{what} -> page-locked, {nbytes / 1e9:.3f} GB", tr)
+        b = line("plain hipMemcpy of as many bytes -> the same buffer", tc)
+        g.profile(True)
+        for _ in range(kernel_calls):
+            read(host.value)
+        ms, launches, moved = g.kernel_stats()["rows_to_natural"]
+        g.profile(False)
+        k = ms / kernel_calls
+        s = (max(tc) - min(tc)) / b
+        bound = b * (1 + s) + k
+        print(f"    read {nbytes / a / 1e6:.2f} GB/s, copy {nbytes / b / 1e6:.2f} GB/s; rows_to_natural {k:.4f} ms a call "
+              f"({launches // kernel_calls} launch(es)), {moved / ms / 1e9:.3f} TB/s (HBM copy rate {HBM_COPY_TBS} TB/s)")
+        print(f"    median(read) {a:.3f} ms {'<=' if a <= bound else '>'} median(copy) (1 + s) + kernel = "
+              f"{b:.3f} x (1 + {s:.4f}) + {k:.4f} = {bound:.3f} ms: {'passes' if a <= bound else 'DOES NOT PASS'}")
+        line(f"{what} -> pageable", alternate(reps, [lambda: read(pageable.ctypes.data)])[0])
+        hip.hipFree(dev)
+        L.zk_host_free(host)
+        return a
+
+    g = GpuProver(0, max_trace_len=n)
+    trace = rand_elems(rng, 28, n)
+    with TraceLde.new(g, trace, 8) as lde:
+        N = 8 * n
+        bulk = measure("zk_lde_read_rows, whole trace LDE", g,
+                       lambda p: native.check(L.zk_lde_read_rows(lde.handle, 0, N, p)), N * 28 * 16)
+        cur, nxt = C.create_string_buffer(28 * 16), C.create_string_buffer(28 * 16)
+        lde.read_frame(0)
+
+        def frames():
+            for step in range(4096):
+                native.check(L.zk_lde_read_frame(lde.handle, step, cur, nxt))
+
+        f = line("zk_lde_read_frame, 4096 consecutive frames", alternate(reps, [frames])[0])
+        print(f"    {f / 4096 * 1e3:.2f} us a frame; extrapolated to the 8n = {N} frames of an evaluator: {f / 4096 * N / 1e3:.1f} s, "
+              f"{f / 4096 * N / bulk:.0f} times the bulk read")
+        ct, cb = rand_elems(rng, 20, 2), rand_elems(rng, 22, 2)
+        lde.evaluate(pub, ct, cb, ext=2, keep_on_device=True)
+        with ConstraintCommitment.commit(lde, None, ext=2, num_cols=8) as cc:
+            measure("zk_comp_read_rows, ext = 2, 8 columns", g,
+                    lambda p: native.check(L.zk_comp_read_rows(cc.handle, 0, N, p)), N * 16 * 16)
+    g.close()
+
+    # blowup 16 at half the trace length: the same N, the plane-side runs half as long, two chunks through the staging
+    g = GpuProver(0, max_trace_len=n // 2, max_blowup=16)
+    with TraceLde.new(g, np.ascontiguousarray(trace[:, :n // 2]), 16) as lde:
+        host = pinned(N * 28 * 16)
+        g.profile(True)
+        for _ in range(5):
+            native.check(L.zk_lde_read_rows(lde.handle, 0, N, host))
+        ms, launches, moved = g.kernel_stats()["rows_to_natural"]
+        g.profile(False)
+        print(f"n = 2^{log_n - 1}, blowup 16: rows_to_natural {ms / 5:.4f} ms a call ({launches // 5} launches), "
+              f"{moved / ms / 1e9:.3f} TB/s")
+        L.zk_host_free(host)
+    g.close()
+
+
 def main():
+    if len(sys.argv) > 1 and sys.argv[1] == "rows":
+        return rows_main(int(sys.argv[2]) if len(sys.argv) > 2 else 20, int(sys.argv[3]) if len(sys.argv) > 3 else 11)
     log_n = int(sys.argv[1]) if len(sys.argv) > 1 else 20
     reps = int(sys.argv[2]) if len(sys.argv) > 2 else 11
     L = native.lib()
