@@ -11,6 +11,8 @@
 
 #include <vector>
 
+#include "../../include/zkvm_gpu.h"
+
 struct zk_prover;
 
 struct zk_comm {
@@ -27,6 +29,13 @@ struct zk_comm {
     // recv[l] = chunk of rank 0 || chunk of rank 1 || ... (each `bytes`); send[l] = this rank's chunk
     virtual int all_gather(const std::vector<zk_prover *> &P, const std::vector<const void *> &send,
                            const std::vector<void *> &recv, size_t bytes, hipStream_t is) = 0;
+    // The control channel: a small host-to-host all-gather that needs nothing from a prover (shard_agree.hpp: the
+    // agreement records, the validation partials).  send: the chunks of this process's ranks, `bytes` each, in local
+    // order (loopback: all `world` of them; else one); recv: `world` chunks in rank order.  Synchronous.
+    virtual int control_gather(const void *send, void *recv, size_t bytes) = 0;
+    // the last sharded call's outcome (zk_comm_agreement); have: records have been exchanged on this communicator
+    zk_agreement last = {};
+    bool have_last = false;
 };
 
 // defined in comm_rccl.cpp (links librccl)

@@ -14,8 +14,15 @@ namespace {
 
 struct RcclComm : zk_comm {
     ncclComm_t comm = nullptr;
+    // the control channel's staging (control_gather): CTL_CAP bytes to send, then world x CTL_CAP received
+    static constexpr size_t CTL_CAP = 2048;
+    int device = 0;
+    uint8_t *ctl = nullptr;
+    hipStream_t ctl_st = nullptr;
     ~RcclComm() override {
         if (comm) ncclCommDestroy(comm);
+        if (ctl) (void)hipFree(ctl);
+        if (ctl_st) (void)hipStreamDestroy(ctl_st);
     }
     bool loopback() const override { return false; }
     int all_to_all(const std::vector<zk_prover *> &P, const std::vector<const void *> &send,
@@ -30,6 +37,17 @@ struct RcclComm : zk_comm {
         if (P.size() != 1) ZK_FAIL(ZK_ERR_INVALID_ARG, "an RCCL communicator drives exactly one local rank");
         ncclResult_t r = ncclAllGather(send[0], recv[0], bytes, ncclUint8, comm, is);
         if (r != ncclSuccess) ZK_FAIL(ZK_ERR_DEVICE, std::string("ncclAllGather: ") + ncclGetErrorString(r));
+        return ZK_OK;
+    }
+    // (compiled, never run: no machine with two GPUs has built this project -- DESIGN.md section 7)
+    int control_gather(const void *send, void *recv, size_t bytes) override {
+        if (bytes > CTL_CAP) ZK_FAIL(ZK_ERR_INVALID_ARG, "control exchange larger than the communicator's staging");
+        ZK_CHECK_HIP(hipSetDevice(device));
+        ZK_CHECK_HIP(hipMemcpyAsync(ctl, send, bytes, hipMemcpyHostToDevice, ctl_st));
+        ncclResult_t r = ncclAllGather(ctl, ctl + CTL_CAP, bytes, ncclUint8, comm, ctl_st);
+        if (r != ncclSuccess) ZK_FAIL(ZK_ERR_DEVICE, std::string("ncclAllGather (control): ") + ncclGetErrorString(r));
+        ZK_CHECK_HIP(hipMemcpyAsync(recv, ctl + CTL_CAP, bytes * (size_t)world, hipMemcpyDeviceToHost, ctl_st));
+        ZK_CHECK_HIP(hipStreamSynchronize(ctl_st));
         return ZK_OK;
     }
 };
@@ -52,6 +70,12 @@ int zk_make_rccl_comm(const unsigned char id[128], int rank, int world, int devi
     auto *c = new RcclComm();
     c->world = world;
     c->rank = rank;
+    c->device = device;
+    if (hipMalloc(&c->ctl, RcclComm::CTL_CAP * (size_t)(world + 1)) != hipSuccess ||
+        hipStreamCreateWithFlags(&c->ctl_st, hipStreamNonBlocking) != hipSuccess) {
+        delete c;
+        ZK_FAIL(ZK_ERR_OUT_OF_MEMORY, "the control channel's staging buffer could not be allocated");
+    }
     ncclResult_t r = ncclCommInitRank(&c->comm, world, u, rank);
     if (r != ncclSuccess) {
         delete c;

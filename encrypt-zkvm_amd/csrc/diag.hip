@@ -1115,3 +1115,62 @@ extern "C" int zk_diag_grind(int device, const uint8_t *seed32, uint64_t start, 
     *best_out = best;
     return ZK_OK;
 }
+
+// ---------------------------------------------------------------- sharded proofs: agreement and validation windows
+// The pure rule of shard_agree.hpp on caller-built records (world x 256 bytes, AgreeRecord's layout): the outcome, its
+// text (empty when OK) and the outcome's code as the status.
+extern "C" int zk_diag_agree(const uint8_t *records, int world, zk_agreement *out, char *msg, size_t cap) {
+    if (!records || !out || world < 1 || world > 8) ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_agree: records of 1 .. 8 ranks");
+    std::vector<AgreeRecord> R((size_t)world);
+    memcpy(R.data(), records, R.size() * sizeof(AgreeRecord));
+    const Agreed A = agree(R.data(), world);
+    *out = A.a;
+    if (msg && cap) snprintf(msg, cap, "%s", A.msg.c_str());
+    g_err = A.msg;
+    return A.a.code;
+}
+// The window of rank g of G (val_window): out[3] = first, count, assertion mask
+extern "C" int zk_diag_val_window(uint64_t n, int g, int G, uint64_t *out) {
+    if (!out || G < 1 || g < 0 || g >= G || n < 16) ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_val_window: rank g < G, n >= 16");
+    const ValWindow w = val_window(n, g, G);
+    out[0] = w.first, out[1] = w.count, out[2] = w.amask;
+    return ZK_OK;
+}
+// The merge of `world` validation partials (world x sizeof(ValPartial) bytes) of a trace of n rows into the report and
+// status a sharded proof returns (validation_from_partials; the message in zk_last_error()).  No GPU.
+extern "C" int zk_diag_merge_validation(const uint8_t *partials, int world, size_t n, const zk_pub_inputs *pub,
+                                        zk_validation *out) {
+    if (!partials || !pub || !out || world < 1 || world > 8 || n < 16)
+        ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_merge_validation: partials of 1 .. 8 ranks, n >= 16");
+    std::vector<ValPartial> P((size_t)world);
+    memcpy(P.data(), partials, P.size() * sizeof(ValPartial));
+    return validation_from_partials(P.data(), world, n, pub, nullptr, 0, out);
+}
+// One window launch of the validator (validate_window_partial) on a prover of its own: steps first .. first + count - 1
+// of the trace (28 x n column-major host bytes) with the assertions of amask.  packed = 0: the whole trace goes up and
+// the window is read in place (ld = n), as a sharded proof reads a device trace; packed = 1: only rows first .. first +
+// count of each column go up (ld = count + 1), as it uploads a host trace.  partial_out: sizeof(ValPartial) bytes.
+extern "C" int zk_diag_validate_window(int device, const uint8_t *trace, size_t n, size_t first, size_t count,
+                                       uint32_t amask, const zk_pub_inputs *pub, int packed, uint8_t *partial_out) {
+    if (!trace || !pub || !partial_out) ZK_FAIL(ZK_ERR_INVALID_ARG, "null argument");
+    if (n < 16 || (n & (n - 1)) || !count || first > n - 2 || count > n - 2 - first)
+        ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_validate_window: steps first .. first + count - 1 within 0 .. n - 3");
+    if (((amask & ZK_ASSERT_ROW0) && first != 0) || ((amask & ZK_ASSERT_LAST) && first + count != n - 2) || (amask >> 22))
+        ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_validate_window: an assertion whose row the window does not hold");
+    if (pub->lwe_size == 0 || pub->lwe_size > 5) ZK_FAIL(ZK_ERR_INVALID_ARG, "lwe_size must be in [1, 5]");
+    DiagProver p;
+    ZK_TRY(p.open(device, n, 8));
+    const fe *win = p->d_trace + first;
+    size_t ld = n;
+    if (packed) {
+        ld = count + 1;
+        win = p->d_trace;
+        for (int c = 0; c < W; c++) ZK_TRY(p.up(p->d_trace + (size_t)c * ld, trace + ((size_t)c * n + first) * sizeof(fe), ld));
+    } else {
+        ZK_TRY(p.up(p->d_trace, trace, (size_t)W * n));
+    }
+    ValPartial P;
+    const int rc = validate_window_partial(p, win, ld, n, ValWindow{first, count, amask}, pub, 0, &P);
+    memcpy(partial_out, &P, sizeof P);
+    return rc;
+}

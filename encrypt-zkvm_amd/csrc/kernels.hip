@@ -1958,30 +1958,40 @@ hipError_t eval_constraints(hipStream_t st, int KX, const fe *lde, int log_n, Ev
 // ballot, its popcount and its lowest set lane (lanes are ascending steps) per wave, the four waves combined
 // through LDS, then one 64-bit atomicAdd and one atomicMin per failing constraint per block and one add for the
 // failing steps: device-scope integer atomics, so the report does not depend on the arrival order.
-__global__ void __launch_bounds__(256, ZK_EVAL_WAVES) k_validate_trace(const fe *trace, size_t n, const fe *per_tab,
-                                                                        fe delta, int L, ValReport *rep) {
+// The windowed form (WIN; sharded proofs, shard.hip: each rank checks a window of steps): steps first .. first +
+// count - 1 of a trace whose columns are `ld` elements apart, row `first` at index 0 of the window, which holds
+// count + 1 rows (the last step's frame reads one row past it).  Thread s of the launch checks global step first + s:
+// the periodic row is (first + s) mod 16 and the reported steps are global -- a wave's lowest failing step is
+// (first + s - lane) + ctz, and s - lane >= 0 is the wave's first LOCAL step, so a window that does not start on a wave
+// boundary of global steps needs nothing more.  amask: the assertions this launch checks (bit k; the row-0 cells at
+// window index 0 -- their rank's first is 0 -- and the row n - 2 cells at window index count -- their rank's window
+// ends at n - 2); a_found[k] of the others is left as the host wrote it.  The whole-trace form is the instantiation
+// WIN = false, whose window arguments are compile-time constants (ld = n, first = 0, count = n - 2, every assertion).
+template <bool WIN>
+__device__ __forceinline__ void validate_body(const fe *trace, size_t n, size_t ld_, size_t first_, size_t count_,
+                                              unsigned amask, const fe *per_tab, fe delta, int L, ValReport *rep) {
     __shared__ unsigned sh_cnt[4][20];
     __shared__ unsigned long long sh_min[4][20];
     __shared__ unsigned sh_steps[4];
     __shared__ fe vstash[6][256];  // 24 KiB: four blocks a CU (the register budget's 16 waves) fit its 160 KiB
     const int tid = threadIdx.x;
     const size_t s = blockIdx.x * (size_t)256 + tid;
-    const size_t steps = n - 2;
-    if (blockIdx.x == 0 && tid < 22) {
+    const size_t ld = WIN ? ld_ : n, first = WIN ? first_ : 0, steps = WIN ? count_ : n - 2;
+    if (blockIdx.x == 0 && tid < 22 && (!WIN || ((amask >> tid) & 1u))) {
         // assertion k: clk@0, depth@0, (7+i)@0 / (7+i)@n-2 for i < 2, (12+i)@0 / (12+i)@n-2 for i < 8.  The host wrote
         // the asserted value into a_found[k]; this thread alone reads it and replaces it with the cell's value
         const int k = tid;
         const int col = k == 0 ? 0 : k == 1 ? 11 : k < 6 ? 7 + ((k - 2) >> 1) : 12 + ((k - 6) >> 1);
         const size_t step = (k >= 2 && (k & 1)) ? steps : 0;
-        const fe want = rep->a_found[k], got = trace[(size_t)col * n + step];
+        const fe want = rep->a_found[k], got = trace[(size_t)col * ld + step];
         if (!fe_eq(want, got)) atomicOr(&rep->a_mask, 1u << k);
         rep->a_found[k] = got;
     }
     unsigned mask = 0;
     if (s < steps) {
         const fe *tb = trace;  // laundered by ZK_SEQ between the sections
-#define VCUR(c) tb[(size_t)(c)*n + s]
-#define VNXT(c) tb[(size_t)(c)*n + s + 1]
+#define VCUR(c) tb[(size_t)(c)*ld + s]
+#define VNXT(c) tb[(size_t)(c)*ld + s + 1]
 #define VSET(k, val) mask |= fe_is_zero(val) ? 0u : (1u << (k))
         const fe one = fe_one();
         // only the mask is live across the two sections: the five bits and s0' wait in a lane-private LDS slot (with
@@ -2007,7 +2017,7 @@ __global__ void __launch_bounds__(256, ZK_EVAL_WAVES) k_validate_trace(const fe 
             opc = fe_add(fe_add(opc, opc), b4);
             const fe push_term = fe_mul(s0n, is_push);
             ZK_SEQ(tb, push_term.lo);
-            const fe *per = per_tab + (s & 15) * 9;
+            const fe *per = per_tab + ((s + first) & 15) * 9;
             const fe c7 = VCUR(7), c8 = VCUR(8);
             fe x[4] = {cube(c7), cube(c8), cube(VCUR(9)), cube(VCUR(10))};
             fe m0[4];
@@ -2105,7 +2115,7 @@ __global__ void __launch_bounds__(256, ZK_EVAL_WAVES) k_validate_trace(const fe 
             const unsigned long long b = __ballot((mask >> k) & 1u);
             if (lane == k && b) {
                 my_cnt = (unsigned)__popcll(b);
-                my_min = (s - lane) + (unsigned)__builtin_ctzll(b);
+                my_min = (first + (s - lane)) + (unsigned)__builtin_ctzll(b);
             }
         }
     }
@@ -2128,6 +2138,25 @@ __global__ void __launch_bounds__(256, ZK_EVAL_WAVES) k_validate_trace(const fe 
     } else if (tid == 20) {
         atomicAdd(&rep->failing_steps, (unsigned long long)sh_steps[0] + sh_steps[1] + sh_steps[2] + sh_steps[3]);
     }
+}
+__global__ void __launch_bounds__(256, ZK_EVAL_WAVES) k_validate_trace(const fe *trace, size_t n, const fe *per_tab,
+                                                                        fe delta, int L, ValReport *rep) {
+    validate_body<false>(trace, n, 0, 0, 0, 0u, per_tab, delta, L, rep);
+}
+__global__ void __launch_bounds__(256, ZK_EVAL_WAVES) k_validate_window(const fe *win, size_t ld, size_t first,
+                                                                         size_t count, unsigned amask,
+                                                                         const fe *per_tab, fe delta, int L,
+                                                                         ValReport *rep) {
+    validate_body<true>(win, 0, ld, first, count, amask, per_tab, delta, L, rep);
+}
+
+hipError_t validate_window(hipStream_t st, const fe *win, size_t ld, size_t first, size_t count, unsigned amask,
+                           const fe *per_tab, fe delta, int lwe_size, ValReport *rep) {
+    // (count >= 1 and ld >= count + 1: checked by the callers)
+    ZK_PROF(st, "validate_window", 448.0 * count, hipLaunchKernelGGL(k_validate_window, dim3(cdiv(count, 256)), dim3(256),
+                                                                     0, st, win, ld, first, count, amask, per_tab, delta,
+                                                                     lwe_size, rep));
+    return hipGetLastError();
 }
 
 hipError_t validate_trace(hipStream_t st, const fe *trace, size_t n, const fe *per_tab, fe delta, int lwe_size,

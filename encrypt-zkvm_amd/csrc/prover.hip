@@ -610,8 +610,12 @@ int zk_prover_exchange_stats_ex(zk_prover *p, const char **names, float *ms, flo
     if (p->stage_done)
         for (const auto &r : p->xchg) {
             float x = 0, y = 0;
-            (void)hipEventElapsedTime(&x, p->xchg_pool[r.ev], p->xchg_pool[r.ev + 1]);
-            if (r.waited) (void)hipEventElapsedTime(&y, p->xchg_pool[r.ev + 2], p->xchg_pool[r.ev + 3]);
+            if (r.host_ms >= 0) {  // a control exchange: host wall time, all of it exposed
+                x = y = r.host_ms;
+            } else {
+                (void)hipEventElapsedTime(&x, p->xchg_pool[r.ev], p->xchg_pool[r.ev + 1]);
+                if (r.waited) (void)hipEventElapsedTime(&y, p->xchg_pool[r.ev + 2], p->xchg_pool[r.ev + 3]);
+            }
             size_t i = 0;
             while (i < nm.size() && strcmp(nm[i], r.name)) i++;
             if (i == nm.size()) {
@@ -1683,37 +1687,87 @@ static std::string u128_dec(fe v) {
     return s;
 }
 
+// an empty report of a trace of n rows with get_assertions (air/src/lib.rs:170-195) in its own order
+static void validation_begin(size_t n, const zk_pub_inputs *pub, zk_validation &V, fe expect[NUM_ASSERTS]) {
+    memset(&V, 0, sizeof V);
+    V.trace_len = n;
+    V.steps_checked = n - 2;
+    V.first_index = -1;
+    int k = 0;
+    auto put = [&](int col, size_t step, fe v) {
+        V.a_col[k] = (uint32_t)col;
+        V.a_step[k] = step;
+        expect[k] = v;
+        fe_to_bytes(v, V.a_expected[k]);
+        k++;
+    };
+    put(0, 0, fe_zero());
+    put(11, 0, fe_zero());
+    for (int i = 0; i < 2; i++) {
+        put(7 + i, 0, fe_zero());
+        put(7 + i, n - 2, fe_from_bytes(pub->program_hash[i]));
+    }
+    for (int i = 0; i < 8; i++) {
+        put(12 + i, 0, fe_zero());
+        put(12 + i, n - 2, fe_from_bytes(pub->stack_outputs[i]));
+    }
+}
+
+// the value of constraint k at global step s from the host evaluator, which must agree that it is not zero: the frame
+// (s, s + 1) is rows[c ld .. + 1] of the 28 columns on the device (one strided copy)
+static int validation_value(zk_prover *p, const fe *rows_dev, size_t ld, uint64_t s, int k, const zk_pub_inputs *pub,
+                            uint8_t out[16]) {
+    fe rows[W][2], cur[W], nxt[W], per[9], ev[NUM_TCONS];
+    ZK_CHECK_HIP(hipMemcpy2DAsync(rows, 2 * sizeof(fe), rows_dev, ld * sizeof(fe), 2 * sizeof(fe), W,
+                                  hipMemcpyDeviceToHost, p->st));
+    ZK_CHECK_HIP(hipStreamSynchronize(p->st));
+    for (int c = 0; c < W; c++) {
+        cur[c] = rows[c][0];
+        nxt[c] = rows[c][1];
+    }
+    air_periodic_row((size_t)s, per);
+    air_eval_base(cur, nxt, per, pub->lwe_size, pub->delta, ev);
+    if (fe_is_zero(ev[k]))
+        ZK_FAIL(ZK_ERR_DEVICE, "trace validation: device and host evaluators disagree at step " + std::to_string(s) +
+                                   " (transition constraint " + std::to_string(k) + ")");
+    fe_to_bytes(ev[k], out);
+    return ZK_OK;
+}
+
+// the first failure as winterfell's Trace::validate meets it (assertions first, then steps in order) into V, and the
+// status with its message: ZK_OK, or ZK_ERR_TRACE
+static int validation_verdict(zk_validation &V) {
+    std::string msg;
+    if (V.a_mask) {
+        const int k = __builtin_ctz(V.a_mask);
+        V.first_kind = 1;
+        V.first_index = k;
+        V.first_step = V.a_step[k];
+        msg = "trace does not satisfy assertion main_trace(" + std::to_string(V.a_col[k]) + ", " +
+              std::to_string(V.a_step[k]) + ") == " + u128_dec(fe_from_bytes(V.a_expected[k]));
+    } else if (V.failing_steps) {
+        int best = -1;
+        for (int k = 0; k < NUM_TCONS; k++)
+            if (V.t_count[k] && (best < 0 || V.t_first[k] < V.t_first[best])) best = k;
+        if (best < 0) ZK_FAIL(ZK_ERR_DEVICE, "trace validation: failing steps without a failing constraint");
+        V.first_kind = 2;
+        V.first_index = best;
+        V.first_step = V.t_first[best];
+        msg = "main transition constraint " + std::to_string(best) + " did not evaluate to ZERO at step " +
+              std::to_string(V.first_step);
+    }
+    if (V.first_kind == 0) return ZK_OK;
+    ZK_FAIL(ZK_ERR_TRACE, msg + "; " + std::to_string(V.failing_steps) + " failing steps, " + std::to_string(V.a_failed) +
+                              " failed assertions");
+}
+
 // the trace is on p's device at d_trace; arguments are checked
 static int validate_on_device(zk_prover *p, const fe *d_trace, size_t n, const zk_pub_inputs *pub, zk_validation *out) {
     ZK_CHECK_HIP(hipSetDevice(p->device));
     IoScope io_scope(p);
     zk_validation V;
-    memset(&V, 0, sizeof V);
-    V.trace_len = n;
-    V.steps_checked = n - 2;
-    V.first_index = -1;
-    // get_assertions (air/src/lib.rs:170-195), in its own order
     fe expect[NUM_ASSERTS];
-    {
-        int k = 0;
-        auto put = [&](int col, size_t step, fe v) {
-            V.a_col[k] = (uint32_t)col;
-            V.a_step[k] = step;
-            expect[k] = v;
-            fe_to_bytes(v, V.a_expected[k]);
-            k++;
-        };
-        put(0, 0, fe_zero());
-        put(11, 0, fe_zero());
-        for (int i = 0; i < 2; i++) {
-            put(7 + i, 0, fe_zero());
-            put(7 + i, n - 2, fe_from_bytes(pub->program_hash[i]));
-        }
-        for (int i = 0; i < 8; i++) {
-            put(12 + i, 0, fe_zero());
-            put(12 + i, n - 2, fe_from_bytes(pub->stack_outputs[i]));
-        }
-    }
+    validation_begin(n, pub, V, expect);
     ValReport R;
     memset(&R, 0, sizeof R);
     for (int k = 0; k < NUM_TCONS; k++) R.t_first[k] = ~0ull;
@@ -1735,47 +1789,92 @@ static int validate_on_device(zk_prover *p, const fe *d_trace, size_t n, const z
         const uint64_t s = R.t_first[k];
         if (s >= n - 2) ZK_FAIL(ZK_ERR_DEVICE, "trace validation: the device reported a step outside the trace");
         V.t_first[k] = s;
-        fe rows[W][2], cur[W], nxt[W], per[9], ev[NUM_TCONS];
-        ZK_CHECK_HIP(hipMemcpy2DAsync(rows, 2 * sizeof(fe), d_trace + s, n * sizeof(fe), 2 * sizeof(fe), W,
-                                      hipMemcpyDeviceToHost, p->st));
-        ZK_CHECK_HIP(hipStreamSynchronize(p->st));
-        for (int c = 0; c < W; c++) {
-            cur[c] = rows[c][0];
-            nxt[c] = rows[c][1];
-        }
-        air_periodic_row((size_t)s, per);
-        air_eval_base(cur, nxt, per, pub->lwe_size, pub->delta, ev);
-        if (fe_is_zero(ev[k]))
-            ZK_FAIL(ZK_ERR_DEVICE, "trace validation: device and host evaluators disagree at step " + std::to_string(s) +
-                                       " (transition constraint " + std::to_string(k) + ")");
-        fe_to_bytes(ev[k], V.t_value[k]);
+        ZK_TRY(validation_value(p, d_trace + s, n, s, k, pub, V.t_value[k]));
     }
-    // the first failure as winterfell's Trace::validate meets it: assertions first, then steps in order
-    std::string msg;
-    if (V.a_mask) {
-        const int k = __builtin_ctz(V.a_mask);
-        V.first_kind = 1;
-        V.first_index = k;
-        V.first_step = V.a_step[k];
-        msg = "trace does not satisfy assertion main_trace(" + std::to_string(V.a_col[k]) + ", " +
-              std::to_string(V.a_step[k]) + ") == " + u128_dec(expect[k]);
-    } else if (V.failing_steps) {
-        int best = -1;
-        for (int k = 0; k < NUM_TCONS; k++)
-            if (V.t_count[k] && (best < 0 || V.t_first[k] < V.t_first[best])) best = k;
-        if (best < 0) ZK_FAIL(ZK_ERR_DEVICE, "trace validation: failing steps without a failing constraint");
-        V.first_kind = 2;
-        V.first_index = best;
-        V.first_step = V.t_first[best];
-        msg = "main transition constraint " + std::to_string(best) + " did not evaluate to ZERO at step " +
-              std::to_string(V.first_step);
-    }
+    const int rc = validation_verdict(V);
+    if (rc != ZK_OK && rc != ZK_ERR_TRACE) return rc;
     p->val_last = V;
     p->val_have = true;
     *out = V;
-    if (V.first_kind == 0) return ZK_OK;
-    ZK_FAIL(ZK_ERR_TRACE, msg + "; " + std::to_string(V.failing_steps) + " failing steps, " + std::to_string(V.a_failed) +
-                              " failed assertions");
+    return rc;
+}
+
+// ---- a sharded proof's validation (shard.hip): one rank's window, and the merged report
+// Steps first .. first + count - 1 of a trace of n rows, whose rows first .. first + count are win[c ld + i] on p's
+// device; arguments are checked by the caller.  Fills *out (shard_agree.hpp) whatever happens: an error of this rank
+// (not a failing trace) goes into out->status / msg and is returned.
+int zk::validate_window_partial(zk_prover *p, const fe *win, size_t ld, size_t n, const ValWindow &w,
+                                const zk_pub_inputs *pub, int rank, ValPartial *out) {
+    memset(out, 0, sizeof *out);
+    out->version = ZK_AGREE_VERSION;
+    out->rank = (uint32_t)rank;
+    out->first = w.first;
+    out->count = w.count;
+    out->amask = w.amask;
+    for (int k = 0; k < NUM_TCONS; k++) out->t_first[k] = UINT64_MAX;
+    auto run = [&]() -> int {
+        if (!w.count || ld < w.count + 1 || w.first + w.count > n - 2)
+            ZK_FAIL(ZK_ERR_INVALID_ARG, "trace validation: a window outside the trace's steps");
+        ZK_CHECK_HIP(hipSetDevice(p->device));
+        IoScope io_scope(p);
+        zk_validation V;
+        fe expect[NUM_ASSERTS];
+        validation_begin(n, pub, V, expect);
+        ValReport R;
+        memset(&R, 0, sizeof R);
+        for (int k = 0; k < NUM_TCONS; k++) R.t_first[k] = ~0ull;
+        for (int k = 0; k < NUM_ASSERTS; k++) R.a_found[k] = expect[k];
+        ZK_TRY(h2d_small(p, p->val_rep, &R, sizeof R));
+        ZK_CHECK_HIP(validate_window(p->st, win, ld, w.first, w.count, w.amask, p->val_per, fe_make(pub->delta),
+                                     (int)pub->lwe_size, p->val_rep));
+        ZK_TRY(d2h_small(p, &R, p->val_rep, sizeof R));
+        ZK_TRY(d2h_flush(p));
+        out->failing_steps = R.failing_steps;
+        out->a_mask = R.a_mask & w.amask;
+        for (int k = 0; k < NUM_ASSERTS; k++) fe_to_bytes(R.a_found[k], out->a_found[k]);
+        for (int k = 0; k < NUM_TCONS; k++) {
+            out->t_count[k] = R.t_count[k];
+            if (!R.t_count[k]) continue;
+            const uint64_t s = R.t_first[k];
+            if (s < w.first || s >= w.first + w.count)
+                ZK_FAIL(ZK_ERR_DEVICE, "trace validation: the device reported a step outside the window");
+            out->t_first[k] = s;
+            ZK_TRY(validation_value(p, win + (s - w.first), ld, s, k, pub, out->t_value[k]));
+        }
+        return ZK_OK;
+    };
+    const int rc = run();
+    if (rc != ZK_OK) {
+        out->status = rc;
+        snprintf(out->msg, sizeof out->msg, "%s", g_err.c_str());
+    }
+    return rc;
+}
+
+// The merged report of `world` partials (merge_validation) of a trace of n rows, stored in each of the provers P
+// (zk_prover_validation).  ZK_OK, ZK_ERR_TRACE with zk_validate_device's message, or -- a rank's partial carries an
+// error -- ZK_ERR_PEER naming the lowest such rank (a local rank's own error: shard.hip returns it as it was met).
+int zk::validation_from_partials(const ValPartial *parts, int world, size_t n, const zk_pub_inputs *pub,
+                                 zk_prover *const *P, int np, zk_validation *out) {
+    zk_validation V;
+    fe expect[NUM_ASSERTS];
+    validation_begin(n, pub, V, expect);
+    int bad = -1;
+    if (merge_validation(parts, world, &V, &bad) != ZK_OK) {
+        char m[ZK_AGREE_MSG + 1];
+        memcpy(m, parts[bad].msg, ZK_AGREE_MSG);
+        m[ZK_AGREE_MSG] = 0;
+        ZK_FAIL(ZK_ERR_PEER, "rank " + std::to_string(bad) + " could not validate its rows: " +
+                                 std::to_string(parts[bad].status) + ": " + m);
+    }
+    const int rc = validation_verdict(V);
+    if (rc != ZK_OK && rc != ZK_ERR_TRACE) return rc;
+    for (int l = 0; l < np; l++) {
+        P[l]->val_last = V;
+        P[l]->val_have = true;
+    }
+    if (out) *out = V;
+    return rc;
 }
 
 static int check_validate_args(zk_prover *p, const void *trace, size_t n, const zk_pub_inputs *pub, zk_validation *out) {

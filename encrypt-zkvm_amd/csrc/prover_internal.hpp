@@ -17,6 +17,7 @@
 #include "host_field.hpp"
 #include "shard_plan.hpp"
 #include "upload_plan.hpp"
+#include "shard_agree.hpp"
 #include "zk_internal.hpp"
 
 namespace zk {
@@ -332,6 +333,7 @@ struct zk_prover {
         size_t ev;
         int op;       // 0 all-to-all, 1 all-gather
         bool waited;  // the compute streams have waited for it (xchg_wait)
+        float host_ms = -1.f;  // >= 0: a control exchange, run and timed on the host (no events: ev unused)
     };
     std::vector<hipEvent_t> xchg_pool;
     size_t xchg_next = 0;  // next free event of the pool (this proof)
@@ -504,6 +506,11 @@ int prove_sharded_entry(zk_comm *comm, zk_prover **provers, int nlocal, const ui
                         zk_record *rec, const FixedCols *fixed);
 // the rank of local prover l of a sharded proof over comm
 int shard_rank_of(const zk_comm *comm, int l);
+// a sharded proof's trace validation (prover.hip; shard_agree.hpp): one rank's window of steps, and the merged report
+int validate_window_partial(zk_prover *p, const fe *win, size_t ld, size_t n, const ValWindow &w,
+                            const zk_pub_inputs *pub, int rank, ValPartial *out);
+int validation_from_partials(const ValPartial *parts, int world, size_t n, const zk_pub_inputs *pub,
+                             zk_prover *const *P, int np, zk_validation *out);
 
 // the single-GPU prove path (prover.hip) for a sharded proof over one rank: trace = host column-major trace, or
 // NULL when it already sits in p->d_trace

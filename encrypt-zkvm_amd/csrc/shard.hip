@@ -24,6 +24,7 @@
 #include <algorithm>
 #include <array>
 #include <atomic>
+#include <chrono>
 #include <memory>
 #include <string>
 #include <type_traits>
@@ -34,6 +35,7 @@
 #include "fri_small.hpp"
 #include "host_pool.hpp"
 #include "prover_internal.hpp"
+#include "shard_agree.hpp"
 
 using namespace zk;
 
@@ -60,6 +62,10 @@ struct LoopbackComm : zk_comm {
             for (int s = 0; s < world; s++)
                 if ((uint8_t *)recv[d] + s * bytes != send[s])  // in place: a rank's own chunk is already there
                     ZK_CHECK_HIP(hipMemcpyAsync((uint8_t *)recv[d] + s * bytes, send[s], bytes, hipMemcpyDeviceToDevice, is));
+        return ZK_OK;
+    }
+    int control_gather(const void *send, void *recv, size_t bytes) override {
+        memcpy(recv, send, bytes * (size_t)world);
         return ZK_OK;
     }
 };
@@ -93,6 +99,11 @@ struct HostComm : zk_comm {
     int all_gather(const std::vector<zk_prover *> &P, const std::vector<const void *> &send,
                    const std::vector<void *> &recv, size_t bytes, hipStream_t is) override {
         return run(P, ZK_XCHG_ALL_GATHER, send.at(0), bytes, recv.at(0), bytes, is);
+    }
+    int control_gather(const void *send, void *recv, size_t bytes) override {  // host buffers: no device round trip
+        const int rc = fn(ctx, ZK_XCHG_ALL_GATHER, send, recv, bytes);
+        if (rc != 0) ZK_FAIL(ZK_ERR_DEVICE, "exchange callback failed (" + std::to_string(rc) + ")");
+        return ZK_OK;
     }
 };
 
@@ -307,6 +318,10 @@ struct Ctx {
     // ZK_SH_REDO, and prove_sharded_entry proves again without hints)
     bool hint_ok = true, sh_clock = false;
     uint32_t sh_refuted = 0;
+    // what the ranks agreed on before the proof (shard_agree.hpp; prove_sharded_entry): every rank detects the sparse
+    // columns / may derive the clock, and the hint set every rank uses for a host trace (none unless all sets were equal)
+    bool detect = false, clock = false;
+    HintSet hints;
     bool lead_seg = false;  // the schedule segment being enqueued runs on the lead rank only (lead_segment)
 };
 constexpr int ZK_SH_REDO = 1000;  // (internal) a refuted column hint voided the proof on every rank
@@ -604,8 +619,7 @@ struct ShardedProof : ProofRun {  // (ProofRun: the state and stages shared with
 
     int start() {
         for (zk_prover *p : X.P) ZK_TRY(io_rewind(p));  // the pinned staging areas start over
-        stage_begin(P0);
-        stage_mark(P0, "start");
+        stage_mark(P0, "start");  // (stage_begin: prove_sharded_entry, before the control exchange it lists)
         coin = seed_coin(n, opt, pub);
         return ZK_OK;
     }
@@ -634,23 +648,23 @@ struct ShardedProof : ProofRun {  // (ProofRun: the state and stages shared with
     // threads check its 1/G row range of them; the flags are all-gathered with the hints of the next proof, and a
     // refuted hint voids the proof on every rank (prove_sharded_entry redoes it without hints).
     int classify_host() {
-        // ZK_SHARD_HINTS=0: every column uploaded, interpolated and all-gathered
-        static const bool hints_on = env_switch("ZK_SHARD_HINTS");
-        // (keyed by length, world and program: column classes are a property of the program)
-        const zk_prover *H = P0;
-        const bool fresh = hints_on && X.hint_ok && sparse_on() && X.pl[0]->lagr && H->sh_hint_n == n && H->sh_hint_g == G &&
-                           !memcmp(H->sh_hint_key, pub->program_hash, 32);
-        S = fresh ? H->sh_sparse : 0u;
-        clk = fresh && H->sh_clock && clock_on() && H->sh_clock_off_n != n && !(S & 1u);
+        // the hint set the ranks agreed on (local_hints on every rank, equal on all of them, else none), unless this is
+        // the pass that redoes a proof whose hints were refuted
+        const HintSet hs = X.hint_ok && X.detect ? X.hints : HintSet{};
+        S = hs.S;
+        clk = hs.clk != 0;
         X.sh_clock = clk;
-        const uint32_t derived = S | (clk ? 1u : 0u);
-        const uint32_t N8 = fresh && narrow_on() ? H->sh_nw8 & ~derived : 0u;
-        const uint32_t N32 = fresh && narrow_on() ? H->sh_nw32 & ~derived & ~N8 : 0u;
+        const uint32_t N8 = hs.N8, N32 = hs.N32;
+        for (zk_prover *p : X.P) {  // (zk_prover_proof_info: what this proof took from its hints)
+            p->tc.sp_hinted = S;
+            p->tc.clk_used = clk;
+        }
         columns_left();
         static_assert((W + 1) / 2 <= ZK_UPLOAD_GROUPS_MAX, "one upload event per round at G = 2");
         for (int c = 0; c < W; c++) memcpy(&lastv[c], trace + (size_t)c * col + (n - 1) * sizeof(fe), sizeof(fe));
         ZK_TRY(each_rank(X, [this](int l, zk_prover *p, Plan *pl) -> int {
             ZK_TRY(sparse_begin(p, pl, &spc[l], &spp[l]));  // the flags the interpolation's pass 1 sets
+            if (!X.detect) spp[l] = nullptr;                // (agreed: a rank that cannot detect turns it off for all)
             if (spp[l]) spc[l].wstride = W;
             if (clk) ZK_TRY(clock_tables(p, pl));
             return ZK_OK;
@@ -732,6 +746,7 @@ struct ShardedProof : ProofRun {  // (ProofRun: the state and stages shared with
     int classify_device() {
         ZK_TRY(each_rank(X, [this](int l, zk_prover *p, Plan *pl) -> int {
             ZK_TRY(sparse_begin(p, pl, &spc[l], &spp[l]));
+            if (!X.detect) spp[l] = nullptr;
             if (!spp[l]) return ZK_OK;
             const size_t rr = n / (size_t)G;
             const bool row_split = rr % 4096 == 0;
@@ -739,12 +754,12 @@ struct ShardedProof : ProofRun {  // (ProofRun: the state and stages shared with
             sparse_detect_rows(p->st, p->d_trace, n, 0, W, spc[l], r0, r1);
             return ZK_OK;
         }));
-        if (std::find(spp.begin(), spp.end(), nullptr) == spp.end()) {  // every rank detects
+        if (X.detect) {  // every rank of the proof detects (agreed: the all-gather is issued by all ranks or by none)
             unsigned nz[4 * W];
             ZK_TRY(gather_flags(nz, true));
             for (int c = 0; c < W; c++)
                 if (nz[c] == 0) S |= 1u << c;
-            clk = clock_on() && !(S & 1u) && nz[3 * W] == 0 && spc[0].id_poly;
+            clk = X.clock && !(S & 1u) && nz[3 * W] == 0 && spc[0].id_poly;
         }
         columns_left();
         if (clk)
@@ -913,7 +928,7 @@ struct ShardedProof : ProofRun {  // (ProofRun: the state and stages shared with
     // host traces: the flags of the columns each rank interpolated (for the next proof's hints) and each rank's check
     // of the hinted ones, all-gathered: every rank then holds the same view.  ZK_SH_REDO: a hint was refuted.
     int learn_hints() {
-        if (!trace || !spp[0]) return ZK_OK;
+        if (!trace || !X.detect) return ZK_OK;
         checked.wait();
         ZK_TRY(each_rank(X, [this](int l, zk_prover *p, Plan *) -> int {
             const uint32_t b = bad[l].load();
@@ -1495,6 +1510,13 @@ int zk_comm_set_trace_split(zk_comm *c, int replicated) {
     return ZK_OK;
 }
 
+int zk_comm_agreement(const zk_comm *c, zk_agreement *out) {
+    if (!c || !out) ZK_FAIL(ZK_ERR_INVALID_ARG, "null argument");
+    if (!c->have_last) ZK_FAIL(ZK_ERR_INVALID_ARG, "no sharded call has exchanged control records on this communicator");
+    *out = c->last;
+    return ZK_OK;
+}
+
 int zk_comm_set_measure(zk_comm *c, int on) {
     if (!c) ZK_FAIL(ZK_ERR_INVALID_ARG, "null communicator");
     if (!c->loopback()) ZK_FAIL(ZK_ERR_INVALID_ARG, "the measurement mode needs a loopback communicator");
@@ -1578,18 +1600,186 @@ static int shard_context(Ctx &X, zk_comm *comm, zk_prover **provers, int nlocal,
     return ZK_OK;
 }
 
+// The hint set a rank would use for a host trace of this length, world and program (column classes are a property of
+// the program): what its last sharded proof learned, under this process's switches.  ZK_SHARD_HINTS=0: none.
+static HintSet local_hints(const zk_prover *H, const Plan *pl, size_t n, int G, const zk_pub_inputs *pub) {
+    static const bool hints_on = env_switch("ZK_SHARD_HINTS");
+    HintSet h;
+    const bool fresh = hints_on && sparse_on() && pl->lagr && H->sh_hint_n == n && H->sh_hint_g == G &&
+                       !memcmp(H->sh_hint_key, pub->program_hash, 32);
+    if (!fresh) return h;
+    h.fresh = 1;
+    h.S = H->sh_sparse;
+    h.clk = H->sh_clock && clock_on() && H->sh_clock_off_n != n && !(h.S & 1u) ? 1u : 0u;
+    const uint32_t derived = h.S | h.clk;
+    h.N8 = narrow_on() ? H->sh_nw8 & ~derived : 0u;
+    h.N32 = narrow_on() ? H->sh_nw32 & ~derived & ~h.N8 : 0u;
+    return h;
+}
+
+// one control exchange (comm.hpp control_gather), listed with the proof's collectives on local rank 0's prover
+static int control_exchange(zk_comm *comm, zk_prover *p0, const char *name, const void *send, void *recv, size_t bytes) {
+    const auto t0 = std::chrono::steady_clock::now();
+    ZK_TRY(comm->control_gather(send, recv, bytes));
+    const float ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    zk_prover::XchgRec r{name, (double)bytes * (comm->world - 1), 0, 1, true};
+    r.host_ms = ms;
+    p0->xchg.push_back(r);
+    comm->last.control_calls += 1;
+    comm->last.control_bytes += bytes * (size_t)(comm->world - 1);
+    return ZK_OK;
+}
+static bool rank_is_local(const zk_comm *comm, int r) { return comm->loopback() || r == comm->rank; }
+
+// Trace::validate of a sharded proof, split by rows (shard_agree.hpp val_window): each local rank checks its window
+// -- a device trace in place, a host trace from an upload of only its count + 1 rows of the 28 columns into its trace
+// buffer, which no stage has written yet (the proof's own uploads follow, after this has drained) -- the partial
+// reports are all-gathered over the control channel and every rank merges them.  No data collective, no hint state.
+static int validate_sharded(Ctx &X, const uint8_t *trace, const zk_pub_inputs *pub) {
+    const int nl = (int)X.P.size();
+    const size_t n = X.n;
+    std::vector<ValPartial> mine(nl), all(X.G);
+    for (int l = 0; l < nl; l++) {
+        zk_prover *p = X.P[l];
+        const ValWindow w = val_window(n, X.rank[l], X.G);
+        const fe *win = p->d_trace + w.first;
+        size_t ld = n;
+        auto upload = [&]() -> int {
+            ZK_CHECK_HIP(hipSetDevice(p->device));
+            ld = w.count + 1;
+            win = p->d_trace;
+            for (int c = 0; c < W; c++)
+                ZK_CHECK_HIP(hipMemcpyAsync(p->d_trace + (size_t)c * ld, trace + ((size_t)c * n + w.first) * sizeof(fe),
+                                            ld * sizeof(fe), hipMemcpyHostToDevice, p->st));
+            return ZK_OK;
+        };
+        const int rc = trace ? upload() : ZK_OK;
+        if (rc == ZK_OK) {
+            (void)validate_window_partial(p, win, ld, n, w, pub, X.rank[l], &mine[l]);  // (its status travels)
+        } else {
+            memset(&mine[l], 0, sizeof mine[l]);
+            mine[l].version = ZK_AGREE_VERSION;
+            mine[l].rank = (uint32_t)X.rank[l];
+            mine[l].status = rc;
+            snprintf(mine[l].msg, sizeof mine[l].msg, "%s", g_err.c_str());
+        }
+        if (trace) (void)hipStreamSynchronize(p->st);  // the caller's trace is free again on every way out
+    }
+    ZK_TRY(control_exchange(X.comm, X.P[0], "validate_report", mine.data(), all.data(), sizeof(ValPartial)));
+    for (int r = 0; r < X.G; r++)
+        if (all[r].status != ZK_OK && rank_is_local(X.comm, r)) {  // this rank's own error, as it met it
+            char m[ZK_AGREE_MSG + 1];
+            memcpy(m, all[r].msg, ZK_AGREE_MSG);
+            m[ZK_AGREE_MSG] = 0;
+            ZK_FAIL(all[r].status, std::string(m));
+        } else if (all[r].status != ZK_OK) {
+            break;  // (validation_from_partials names the lowest such rank)
+        }
+    return validation_from_partials(all.data(), X.G, n, pub, X.P.data(), nl, nullptr);
+}
+
 int zk::prove_sharded_entry(zk_comm *comm, zk_prover **provers, int nlocal, const uint8_t *trace, size_t n,
                             const zk_options *opt, const zk_pub_inputs *pub, uint8_t *proof_out, size_t *proof_len,
                             zk_record *rec, const FixedCols *fixed) {
+    // a null or wrong-shaped communicator or prover list: no exchange is possible, so these alone return at once
     if (!comm || !provers || !proof_len || nlocal <= 0) ZK_FAIL(ZK_ERR_INVALID_ARG, "null argument");
-    if (fixed && trace) ZK_FAIL(ZK_ERR_INVALID_ARG, "preprocessed columns go with a device trace");
+    if (comm->loopback() ? nlocal != comm->world : nlocal != 1)
+        ZK_FAIL(ZK_ERR_INVALID_ARG,
+                "a loopback communicator needs one prover per rank, an RCCL or host-exchange one exactly one");
+    for (int l = 0; l < nlocal; l++)
+        if (!provers[l]) ZK_FAIL(ZK_ERR_INVALID_ARG, "null prover");
     Ctx X;
-    ZK_TRY(shard_context(X, comm, provers, nlocal, n, opt, pub));
     // one rank: nothing to shard or exchange, so the single-GPU path proves it (the same proof bytes; its
     // seven-coset evaluation only pays off without ranks to balance: DESIGN.md section 7, round 4)
-    if (X.G == 1)
+    if (comm->world == 1) {
+        if (fixed && trace) ZK_FAIL(ZK_ERR_INVALID_ARG, "preprocessed columns go with a device trace");
+        ZK_TRY(shard_context(X, comm, provers, nlocal, n, opt, pub));
         return fixed ? prove_fixed(X.P[0], n, opt, pub, fixed, proof_out, proof_len)
                      : prove_single(X.P[0], trace, n, opt, pub, proof_out, proof_len, rec);
+    }
+    // This rank's own checks, into a status: a rank that returned here would strand the peers whose arguments passed
+    // in their first collective.  Every rank goes on to the control exchange and learns the same outcome from it.
+    const int G = comm->world;
+    int status = ZK_OK;
+    if (!opt || !pub) {
+        g_err = "null argument";
+        status = ZK_ERR_INVALID_ARG;
+    } else if (fixed && trace) {
+        g_err = "preprocessed columns go with a device trace";
+        status = ZK_ERR_INVALID_ARG;
+    } else {
+        status = shard_context(X, comm, provers, nlocal, n, opt, pub);
+    }
+    const std::string status_msg = status != ZK_OK ? g_err : std::string();
+    std::vector<AgreeRecord> mine(nlocal), all(G);
+    for (int l = 0; l < nlocal; l++) {
+        AgreeRecord &r = mine[l];
+        memset(&r, 0, sizeof r);
+        r.version = ZK_AGREE_VERSION;
+        r.world = (uint32_t)G;
+        r.rank = (uint32_t)shard_rank_of(comm, l);
+        r.status = status;
+        snprintf(r.msg, sizeof r.msg, "%s", status_msg.c_str());
+        r.n = n;
+        if (opt) {
+            const uint32_t o[6] = {opt->num_queries,     opt->blowup,      opt->grinding,
+                                   opt->field_extension, opt->fri_folding, opt->fri_rem_max_deg};
+            memcpy(r.opt, o, sizeof o);
+        }
+        if (pub) b3::hash_bytes(reinterpret_cast<const uint8_t *>(pub), sizeof *pub, r.pub_hash);
+        r.source = fixed ? ZK_SRC_FIXED : trace ? ZK_SRC_HOST : ZK_SRC_DEVICE;
+        r.split_rep = comm->split_rep;
+        r.measure = comm->measure ? 1u : 0u;
+        r.validate = provers[l]->validate ? 1u : 0u;
+        if (status != ZK_OK) continue;
+        const Plan *pl = X.pl[l];
+        r.detect = (sparse_on() && pl->lagr && pl->lagr_lde ? 1u : 0u) | (clock_on() ? 2u : 0u);
+        if (trace) {
+            const HintSet h = local_hints(provers[l], pl, n, G, pub);
+            r.hint_fresh = h.fresh, r.hint_S = h.S, r.hint_clk = h.clk, r.hint_N8 = h.N8, r.hint_N32 = h.N32;
+        }
+    }
+    zk_prover *const p0 = provers[0];
+    stage_begin(p0);  // the record of this call's exchanges starts with the control exchange
+    comm->last = zk_agreement{};
+    comm->have_last = false;
+    ZK_TRY(control_exchange(comm, p0, "control", mine.data(), all.data(), sizeof(AgreeRecord)));
+    const Agreed A = agree(all.data(), G);
+    {
+        const uint64_t calls = comm->last.control_calls, bytes = comm->last.control_bytes;
+        comm->last = A.a;
+        comm->last.control_calls = calls;
+        comm->last.control_bytes = bytes;
+        comm->have_last = true;
+    }
+    if (A.a.code != ZK_OK) {
+        p0->stage_done = true;  // (zk_prover_exchange_stats: the control exchange is all that ran)
+        if (A.a.code == ZK_ERR_PEER && rank_is_local(comm, A.a.rank_a)) ZK_FAIL(status, status_msg);
+        ZK_FAIL(A.a.code, A.msg);
+    }
+    X.detect = A.a.detect != 0;
+    X.clock = A.a.clock != 0;
+    X.hints = A.hints;
+    if (!A.a.hints_equal)  // stale on some rank: every rank proves from every column and learns the set anew
+        for (zk_prover *p : X.P) {
+            p->sh_hint_n = 0;
+            p->sh_sparse = p->sh_nw8 = p->sh_nw32 = 0;
+            p->sh_clock = false;
+        }
+    if (A.a.validate) {
+        int rc = ZK_OK;
+        if (fixed) {
+            g_err = "sharded validation needs every trace column in HBM, not the preprocessed ones";
+            rc = ZK_ERR_INVALID_ARG;
+        } else {
+            rc = validate_sharded(X, trace, pub);
+        }
+        if (rc != ZK_OK) {
+            *proof_len = 0;
+            p0->stage_done = true;
+            return rc;
+        }
+    }
     X.fixed = fixed;
     // measurement mode (loopback): every rank's kernels on rank 0's stream, in program order (restored on the way out)
     struct SharedStream {
@@ -1628,5 +1818,11 @@ int zk::prove_sharded_entry(zk_comm *comm, zk_prover **provers, int nlocal, cons
     if (rc != ZK_SH_REDO) return rc;
     *proof_len = cap;
     forget_hints(X);
+    for (zk_prover *p : X.P) p->hint_redos++;
+    {  // the redone proof's record starts over, the control exchanges kept at its head
+        const std::vector<zk_prover::XchgRec> ctl(p0->xchg.begin(), p0->xchg.begin() + (long)comm->last.control_calls);
+        stage_begin(p0);
+        p0->xchg = ctl;
+    }
     return prove_sharded(X, trace, opt, pub, proof_out, proof_len, rec);
 }

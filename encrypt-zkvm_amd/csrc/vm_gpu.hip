@@ -601,7 +601,12 @@ int zk_vm_prove_sharded(zk_comm *comm, zk_prover **provers, int nlocal, zk_progr
     size_t n = 0;
     const int G = comm->world;
     // ZK_VM_PREPROCESS=0: every column from the device trace, as zk_vm_prove
-    const bool pre = env_switch("ZK_VM_PREPROCESS") && opt->blowup == 8 && (G == 1 || G == 2 || G == 4 || G == 8);
+    // zk_prover_set_validate on a local prover: Trace::validate needs every column of the written trace in HBM, so the
+    // call takes the all-columns path, as zk_vm_prove (the trace source is one of the fields the ranks must agree on)
+    bool validates = false;
+    for (int l = 0; l < nlocal; l++) validates = validates || (G > 1 && provers[l]->validate);
+    const bool pre = env_switch("ZK_VM_PREPROCESS") && opt->blowup == 8 && (G == 1 || G == 2 || G == 4 || G == 8) &&
+                     !validates;
     std::vector<FixedCols> fx(pre ? nlocal : 0);
     // Processor::run + trace on every local rank, each into its own trace buffer (the loopback communicator drives
     // several ranks from one process; one RCCL process holds one); with the preprocessed columns (built once per

@@ -374,6 +374,11 @@ static_assert(sizeof(ValReport) < 1024, "the validation report stays a small tra
 // 28 x n column-major, n >= 16
 hipError_t validate_trace(hipStream_t st, const fe *trace, size_t n, const fe *per_tab, fe delta, int lwe_size,
                           ValReport *rep);
+// The windowed form: steps first .. first + count - 1 (global) of a trace whose columns are ld elements apart, win[c ld +
+// i] = row first + i of column c, i <= count (count + 1 rows; ld >= count + 1, count >= 1).  amask: the assertions
+// checked (bit k; row-0 cells at window index 0, row n - 2 cells at window index count).  Reported steps are global.
+hipError_t validate_window(hipStream_t st, const fe *win, size_t ld, size_t first, size_t count, unsigned amask,
+                           const fe *per_tab, fe delta, int lwe_size, ValReport *rep);
 // Transition constraint degrees (kernels.hip k_transition_quotients, k_poly_degrees; zk_degrees_device).
 // transition_quotients: quot[k 8n + jl n + q] = C_k / D at CE row (jl, q) of `map` for the 20 constraints k of
 // evaluate_transition, no coefficients; lde, periodic and divs (plane 0 of divisor_tables) as eval_constraints.

@@ -18,6 +18,7 @@ ZK_ERR_INVALID_ARG = -1
 ZK_ERR_BUFFER_TOO_SMALL = -2
 ZK_ERR_DEVICE = -3
 ZK_ERR_OUT_OF_MEMORY = -4
+ZK_ERR_PEER = -5
 ZK_ERR_PROGRAM = -10
 ZK_ERR_STACK = -11
 ZK_ERR_CHIPLETS = -12
@@ -44,6 +45,7 @@ EXPORTED = (
     "zk_degrees_device", "zk_degrees_columns", "zk_prover_set_validate_degrees", "zk_prover_degrees",
     "zk_lde_new_columns", "zk_eval_constraints_ext", "zk_commit_composition_ext",
     "zk_lde_read_rows", "zk_comp_read_rows",
+    "zk_comm_agreement",
 )
 
 
@@ -103,6 +105,53 @@ class Validation(C.Structure):
             "a_found": [el(self.a_found, k) for k in range(a)],
             "first_kind": self.first_kind, "first_index": self.first_index, "first_step": self.first_step,
         }
+
+
+class Agreement(C.Structure):
+    """zk_agreement (include/zkvm_gpu.h): what the ranks of the last sharded call agreed on."""
+    _fields_ = [
+        ("code", C.c_int32), ("rank_a", C.c_int32), ("rank_b", C.c_int32),
+        ("detect", C.c_int32), ("clock", C.c_int32), ("hints", C.c_int32), ("hints_equal", C.c_int32),
+        ("validate", C.c_int32), ("world", C.c_uint32), ("_pad", C.c_uint32),
+        ("control_calls", C.c_uint64), ("control_bytes", C.c_uint64), ("field", C.c_char * 32),
+    ]
+
+    def to_dict(self) -> dict:
+        d = {f: getattr(self, f) for f, _ in self._fields_ if f != "_pad"}
+        d["field"] = self.field.decode()
+        return d
+
+
+# The control record and the validation partial of csrc/shard_agree.hpp (AgreeRecord: 256 bytes, ValPartial: 1160), for
+# the test entry points bound in zkvm_amd/shard_diag.py
+AGREE_VERSION, AGREE_MSG = 1, 120
+SRC_HOST, SRC_DEVICE, SRC_FIXED = 0, 1, 2
+ASSERT_ROW0, ASSERT_LAST = 0x155557, 0x2AAAA8
+
+
+class AgreeRecord(C.Structure):
+    _fields_ = [
+        ("version", C.c_uint32), ("world", C.c_uint32), ("rank", C.c_uint32), ("status", C.c_int32),
+        ("n", C.c_uint64), ("opt", C.c_uint32 * 6), ("pub_hash", C.c_uint8 * 32),
+        ("source", C.c_uint32), ("split_rep", C.c_int32), ("measure", C.c_uint32), ("validate", C.c_uint32),
+        ("detect", C.c_uint32),
+        ("hint_fresh", C.c_uint32), ("hint_S", C.c_uint32), ("hint_clk", C.c_uint32), ("hint_N8", C.c_uint32),
+        ("hint_N32", C.c_uint32),
+        ("msg", C.c_char * AGREE_MSG), ("reserved", C.c_uint8 * 16),
+    ]
+
+
+class ValPartial(C.Structure):
+    _fields_ = [
+        ("version", C.c_uint32), ("rank", C.c_uint32), ("status", C.c_int32), ("amask", C.c_uint32),
+        ("first", C.c_uint64), ("count", C.c_uint64), ("failing_steps", C.c_uint64),
+        ("t_count", C.c_uint64 * 20), ("t_first", C.c_uint64 * 20), ("t_value", C.c_uint8 * (16 * 20)),
+        ("a_mask", C.c_uint32), ("_pad", C.c_uint32), ("a_found", C.c_uint8 * (16 * 22)),
+        ("msg", C.c_char * AGREE_MSG),
+    ]
+
+
+assert C.sizeof(AgreeRecord) == 256 and C.sizeof(ValPartial) == 1160
 
 
 class Degrees(C.Structure):
@@ -359,6 +408,8 @@ def lib():
             # (op, col, aux, r0, r1, width, dst) -> the check's verdict / (r0, r1, R, ranges_out, cap, count_out)
             L.zk_diag_host_rows.argtypes = [i32, vp, vp, sz, sz, i32, vp]
             L.zk_diag_row_tasks.argtypes = [sz, sz, sz, vp, sz, C.POINTER(sz)]
+        if hasattr(L, "zk_comm_agreement"):  # (an A/B library of an earlier commit has none)
+            L.zk_comm_agreement.argtypes = [vp, C.POINTER(Agreement)]
         if hasattr(L, "zk_diag_merkle"):
             # (device, leaves, nl, l3_min_log, pf_blocks, block_p, nodes_out, guard_out[2 * 4096], leaves_out, positions,
             #  k, proof_out, proof_len)

@@ -114,6 +114,26 @@ class ShardedProver:
         check(rc, "zk_vm_prove_sharded")
         return bytes_elems(h.raw), bytes_elems(outputs.raw), C.string_at(buf, plen.value)
 
+    def agreement(self) -> dict:
+        """zk_comm_agreement: what the ranks of the last sharded call on this communicator agreed on before anything
+        touched the GPU -- the outcome's code and the field or rank it names, the decisions (detect, clock, hints,
+        validate) and the count and bytes of the control exchanges."""
+        a = native.Agreement()
+        check(lib().zk_comm_agreement(self.comm, C.byref(a)), "zk_comm_agreement")
+        return a.to_dict()
+
+    def set_validate(self, on: bool):
+        """zk_prover_set_validate on every local rank's prover: the sharded proof validates the trace first, split by
+        rows over the ranks, when any rank of the proof has the switch on."""
+        for p in self.provers:
+            check(lib().zk_prover_set_validate(p, 1 if on else 0), "zk_prover_set_validate")
+
+    def validation(self, local: int = 0) -> dict:
+        """zk_prover_validation of a local rank's prover: the merged report of the last sharded validation."""
+        v = native.Validation()
+        check(lib().zk_prover_validation(self.provers[local], C.byref(v)), "zk_prover_validation")
+        return v.to_dict()
+
     def stage_times(self) -> dict:
         names = (C.c_char_p * 32)()
         ms = (C.c_float * 32)()

@@ -32,6 +32,7 @@ extern "C" {
 #define ZK_ERR_BUFFER_TOO_SMALL -2
 #define ZK_ERR_DEVICE -3
 #define ZK_ERR_OUT_OF_MEMORY -4
+#define ZK_ERR_PEER -5      /* sharded proof: another rank refused it (that rank and its reason in the message) */
 #define ZK_ERR_PROGRAM -10  /* ProgramError (vm/src/program/errors.rs) */
 #define ZK_ERR_STACK -11    /* StackError (vm/src/processor/errors.rs:4-42) */
 #define ZK_ERR_CHIPLETS -12 /* ChipletsError (vm/src/processor/errors.rs:44-71) */
@@ -222,7 +223,8 @@ int zk_validate_columns(zk_prover *p, const uint8_t *const *columns, size_t n, c
  * zk_vm_prove validates the trace it has written.  A failing trace returns ZK_ERR_TRACE with *proof_len = 0: no
  * proof is written and no column hint or snapshot is touched.  A valid trace goes on to the same proof bytes.
  * Default 0: nothing is validated, and a bad trace ends in ZK_ERR_DEGREE after the whole proof, as before.
- * The sharded entry points (zk_prove_sharded, zk_vm_prove_sharded) ignore the setting. */
+ * The setting applies to rank-sized provers (zk_prover_create_shard) too: zk_prove_sharded and zk_vm_prove_sharded
+ * validate first, split by rows over the ranks, when ANY rank's prover has it on ("what the ranks agree on" below). */
 int zk_prover_set_validate(zk_prover *p, int on);
 /* The report of the last validation that ran on p (by either call above or by a proof with the switch on);
  * ZK_ERR_INVALID_ARG if none has run. */
@@ -274,7 +276,8 @@ int zk_degrees_columns(zk_prover *p, const uint8_t *const *columns, size_t n, co
  * prove, after Trace::validate when zk_prover_set_validate is on as well (the order of a debug build: Prover::prove
  * validates the trace, then the evaluator checks the degrees).  A mismatch returns ZK_ERR_DEGREES with *proof_len = 0:
  * no proof is written and no column hint or snapshot is touched.  A pass goes on to the same proof bytes.  Default 0:
- * nothing changes, and zk_prover_set_validate keeps its meaning.  The sharded entry points ignore the setting. */
+ * nothing changes, and zk_prover_set_validate keeps its meaning.  The sharded entry points (zk_prove_sharded,
+ * zk_vm_prove_sharded) ignore THIS setting: they validate the trace (zk_prover_set_validate), never the degrees. */
 int zk_prover_set_validate_degrees(zk_prover *p, int on);
 /* The report of the last degree check that ran on p (by either call above or by a proof with the switch on);
  * ZK_ERR_INVALID_ARG if none has run. */
@@ -409,11 +412,55 @@ int zk_comm_set_trace_split(zk_comm *comm, int replicated);
 int zk_prove_sharded(zk_comm *comm, zk_prover **provers, int nlocal, const uint8_t *trace, size_t n,
                      const zk_options *opt, const zk_pub_inputs *pub, uint8_t *proof_out, size_t *proof_len,
                      zk_record *rec);
-/* The collectives of the last sharded proof on this (local rank 0) prover, aggregated by name (trace_coeffs,
+/* ---- what the ranks agree on before a sharded proof touches the GPU ----
+ * Every sharded entry point (world > 1) first runs its own argument checks into a status instead of returning, then
+ * exchanges one 256-byte control record per rank over the communicator's control channel -- a host-to-host all-gather
+ * (loopback: a memcpy; host exchange: the caller's callback with ZK_XCHG_ALL_GATHER on host buffers, no device round
+ * trip; RCCL: a small device staging buffer the communicator owns) that needs nothing from a prover -- and every rank
+ * maps the same records to the same outcome.  The one exception: a null or wrong-shaped communicator or prover list is
+ * refused at once (no exchange is possible).  The record holds a layout version, world, rank, n, every member of
+ * zk_options, a BLAKE3 of zk_pub_inputs, the trace source (host / device / preprocessed), the communicator's
+ * zk_comm_set_trace_split and zk_comm_set_measure settings, the prover's zk_prover_set_validate switch, what this
+ * process can detect (ZK_SPARSE, ZK_CLOCK and its tables), the column-hint set it would use, and its status.
+ *  1. A rank whose own checks failed returns its own code and message, as before; every other rank returns ZK_ERR_PEER
+ *     with "rank r refused the proof: <code>: <message>" (the lowest such rank).
+ *  2. A field that must match differs -- world, n, options, public inputs, trace source, the two communicator
+ *     settings: every rank returns ZK_ERR_INVALID_ARG with "sharded proof: ranks disagree on <field> (rank a: x, rank
+ *     b: y)", the first differing field in that order, options by member (options.num_queries), the two lowest ranks
+ *     holding different values.
+ *  3. Otherwise: column detection and the derived clock run iff every rank can (AND); the column hints of a host trace
+ *     are used iff every rank holds the same set (else every rank proves without and drops its set: no redo pass); the
+ *     trace is validated first iff any rank's switch is on (OR).
+ * So the ZK_* switches and the provers' histories no longer have to match across ranks for the collectives to pair
+ * up: every rank issues the same collectives in the same order.  After 1 or 2 nothing else has run: communicator and
+ * provers stay usable, and the next call with matching inputs proves as always.  zk_vm_prove_sharded takes the
+ * preprocessed trace source only when no local prover validates, so there the switches must match (else: case 2,
+ * "trace source").  Deadlines on a peer that never arrives are the transport's (the caller's callback, RCCL).
+ * Sharded validation: rank g checks steps [g n / world, min((g + 1) n / world, n - 2)) of the trace -- in place for a
+ * device trace, for a host trace from an upload of only its rows -- the partial reports are all-gathered over the
+ * control channel and merged, every local prover stores the merged report, read with zk_prover_validation, and a failing
+ * trace returns ZK_ERR_TRACE on every rank with *proof_len = 0 and zk_validate_device's message, before any data
+ * collective.  zk_prover_exchange_stats lists the control exchanges as "control" and "validate_report". */
+typedef struct {
+    int32_t code;           /* ZK_OK; ZK_ERR_PEER (case 1); ZK_ERR_INVALID_ARG (case 2); the same on every rank */
+    int32_t rank_a, rank_b; /* case 1: the rank that refused, -1; case 2: the two ranks named; else -1, -1 */
+    int32_t detect, clock;  /* case 3: every rank detects sparse columns / may derive the clock */
+    int32_t hints;          /* case 3: the ranks' hint sets are equal and fresh: this proof uses them */
+    int32_t hints_equal;    /* case 3: the ranks' hint sets are equal (an equal empty set is no disagreement) */
+    int32_t validate;       /* case 3: the trace is validated first */
+    uint32_t world, _pad;
+    uint64_t control_calls, control_bytes; /* control exchanges of the call, and the bytes each rank received in them */
+    char field[32];         /* case 2: the field named; case 1: "status" */
+} zk_agreement;
+/* The outcome of the last sharded call on this communicator (ZK_ERR_INVALID_ARG if none has exchanged records). */
+int zk_comm_agreement(const zk_comm *comm, zk_agreement *out);
+/* The collectives of the last sharded proof on this (local rank 0) prover, aggregated by name (control,
+ * validate_report, trace_coeffs,
  * trace_digests, trace_roots, comp_slices, comp_columns, degree_flags, comp_digests, comp_roots, ood_parts,
  * deep_totals, deep_slices, fri0_digests, fri0_roots, fri_layer1, openings): ms between HIP events recorded on the
  * stream the collective runs on around each call (waiting for slower ranks included), bytes this rank received from
- * the other ranks, and the number of calls.  Valid once the proof has returned, until the next proof. */
+ * the other ranks, and the number of calls.  Valid once the proof has returned, until the next proof.  The two control
+ * exchanges run on the host: their ms is host wall time, and they are all a refused or invalid proof lists. */
 int zk_prover_exchange_stats(zk_prover *p, const char **names, float *ms, double *bytes, int *calls, int cap,
                              int *count);
 /* The same with each collective's exposed time beside its total: exposed_ms is how long the compute stream waited
@@ -468,7 +515,9 @@ int zk_prover_set_upload_schedule(zk_prover *p, int schedule);
  * hint_redos: proofs this prover voided and redid because a column hint was refuted (cumulative).  hint_sets: the
  * (trace length, program hash) column-hint sets it holds (at most 8, least recently used evicted).  hinted_sparse /
  * derived: the sparse columns (bit c) and derived columns (bit 0, the clock) the last proof took from its hints.
- * fixed_sets: the fixed-column snapshots it holds (zk_prover_upload_fixed; at most 2). */
+ * fixed_sets: the fixed-column snapshots it holds (zk_prover_upload_fixed; at most 2).  After a sharded host-trace
+ * proof hinted_sparse / derived are what it took from the hint set the ranks agreed on (zero without one), and
+ * hint_redos counts the sharded proofs redone as well. */
 typedef struct {
     int32_t schedule;
     uint32_t hint_redos;
