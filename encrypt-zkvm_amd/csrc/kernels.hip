@@ -1564,6 +1564,153 @@ __device__ __forceinline__ fe adj_row(int r, const fe y[4]) {
 // 3^-72 mod p: the adjugate path's cubes carry 3^72, folded into the coefficients (ct3 = ct 3^-72)
 static constexpr fe ZK_INV3_72 = fe{0x8092deb1ab776293ull, 0xf0185d00eca40a3bull};
 
+// ---- the plain reading of ProcessorAir::evaluate_transition (air/src/lib.rs:104-168, constrains.rs:95-216,
+// flags.rs:37-91): the 20 constraint values of one frame, one by one and unmerged -- no coefficient, no divisor, no
+// extension plane, no folding of constraints into each other.  The body of the project's own soundness checks: the
+// trace validator (k_validate_trace / k_validate_window) hands each value to a zero test, the degree check
+// (k_transition_quotients) to a store.  k_eval_constraints below is the tuned statement of the same AIR and shares
+// only the small helpers above.
+// The frame: column c of the current row is base[c cs + cur], of the next row base[c cs + nxt].  `base` is what ZK_SEQ
+// launders between the sections; the body takes the frame by value and launders its own copy (by reference the
+// quotient kernel needs 114 VGPRs, by value the 112 it had with a body of its own).
+// Registers at ZK_EVAL_WAVES = 4 (profiles/plain_body_resources.txt), with two pasted bodies -> with this one:
+// k_validate_trace 106 -> 106 VGPRs, 38 -> 48 SGPRs; k_validate_window 106 -> 106, 44 -> 50; k_transition_quotients
+// 112 -> 112, 46 -> 44.  No scratch, no spills, LDS and four waves per SIMD as before.
+struct FrameRows {
+    const fe *base;
+    size_t cs, cur, nxt;
+    __device__ __forceinline__ fe at(int c) const { return base[(size_t)c * cs + cur]; }
+    __device__ __forceinline__ fe next(int c) const { return base[(size_t)c * cs + nxt]; }
+};
+// The two sinks.  set(k, v) takes constraint k's value; wait() / wait(sel) is the value the row loads of the last two
+// sections are sequenced after (ZK_SEQ; sel: the last selector formed before the limb loops).
+struct ZeroMaskSink {  // bit k: constraint k is not zero (every operation returns the canonical representative)
+    unsigned mask = 0;
+    __device__ __forceinline__ void set(int k, fe v) { mask |= fe_is_zero(v) ? 0u : (1u << k); }
+    __device__ __forceinline__ unsigned wait() const { return mask; }
+    __device__ __forceinline__ unsigned wait(fe) const { return mask; }
+};
+struct QuotientSink {  // out[k stride] = value x divisor inverse, stored as soon as it is formed
+    fe *out;
+    size_t stride;
+    fe dinv;
+    __device__ __forceinline__ void set(int k, fe v) const { out[(size_t)k * stride] = fe_mul(v, dinv); }
+    __device__ __forceinline__ uint64_t wait() const { return dinv.lo; }
+    __device__ __forceinline__ uint64_t wait(fe sel) const { return sel.lo; }
+};
+// per: the 9 periodic values of this row (CYCLE_MASK, then the 8 round constants); L: lwe_size; vstash: the block's LDS
+// stash, slot tid this lane's alone -- so no barrier in here, and a block's lanes may enter it or not as they like.
+template <class Sink>
+__device__ __forceinline__ void transition_constraints(FrameRows f, const fe *per, fe delta, int L, fe (*vstash)[256],
+                                                       int tid, Sink &sink) {
+    const fe one = fe_one();
+    // only the sink's state is live across the two sections: the five bits and s0' wait in a lane-private LDS slot (with
+    // them in registers the Rescue section spilled 22 VGPRs at this occupancy), and the complements and the
+    // selectors are formed where they are used
+    {
+        const fe b0 = f.at(5), b1 = f.at(4), b2 = f.at(3), b3 = f.at(2), b4 = f.at(1);
+        const fe s0n = f.next(12);
+        vstash[0][tid] = b0;
+        vstash[1][tid] = b1;
+        vstash[2][tid] = b2;
+        vstash[3][tid] = b3;
+        vstash[4][tid] = b4;
+        vstash[5][tid] = s0n;
+        // 12..15 Rescue round, 16..19 copy (constrains.rs:182-216)
+        // flags.rs: is_push = b0 (1 - b1)(1 - b2)(1 - b3)(1 - b4)
+        const fe is_push = fe_mul(fe_mul(fe_mul(fe_mul(b0, fe_sub(one, b1)), fe_sub(one, b2)), fe_sub(one, b3)),
+                                  fe_sub(one, b4));
+        fe opc = b0;  // 16 b0 + 8 b1 + 4 b2 + 2 b3 + b4
+        opc = fe_add(fe_add(opc, opc), b1);
+        opc = fe_add(fe_add(opc, opc), b2);
+        opc = fe_add(fe_add(opc, opc), b3);
+        opc = fe_add(fe_add(opc, opc), b4);
+        const fe push_term = fe_mul(s0n, is_push);
+        ZK_SEQ(f.base, push_term.lo);
+        const fe c7 = f.at(7), c8 = f.at(8);
+        fe x[4] = {cube(c7), cube(c8), cube(f.at(9)), cube(f.at(10))};
+        fe m0[4];
+#pragma unroll
+        for (int r = 0; r < 4; r++) m0[r] = fe_add(mds_row(r, x), per[1 + r]);
+        m0[0] = fe_add(m0[0], opc);
+        m0[1] = fe_add(m0[1], push_term);
+        ZK_SEQ(f.base, m0[3].lo);
+        const fe hf = per[0], h0 = f.at(6);
+        fe y[4];
+        {
+            // 16..19 first: the next-row sponge words are consumed as they arrive
+            const fe nf = fe_sub(one, hf);
+            const fe n7 = f.next(7), n8 = f.next(8), n9 = f.next(9), n10 = f.next(10);
+            sink.set(16, fe_mul(fe_mul(fe_sub(n7, c7), nf), h0));
+            sink.set(17, fe_mul(fe_mul(fe_sub(n8, c8), nf), h0));
+            sink.set(18, fe_mul(fe_mul(n9, nf), h0));
+            sink.set(19, fe_mul(fe_mul(n10, nf), h0));
+            y[0] = fe_sub(n7, per[5]);
+            y[1] = fe_sub(n8, per[6]);
+            y[2] = fe_sub(n9, per[7]);
+            y[3] = fe_sub(n10, per[8]);
+        }
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            // (INV_MDS y)_r^3 = (adj_r y)^3 3^-72
+            const fe v3 = fe_mul(cube(adj_row(r, y)), ZK_INV3_72);
+            sink.set(12 + r, fe_mul(fe_mul(fe_sub(v3, m0[r]), hf), h0));
+        }
+    }
+    ZK_SEQ(f.base, sink.wait());
+    {
+        // 0 clock, 2 shift, 8..11 the selectors that move one value
+        const fe b0 = vstash[0][tid], b1 = vstash[1][tid], b2 = vstash[2][tid], b3 = vstash[3][tid],
+                 b4 = vstash[4][tid], s0n = vstash[5][tid];
+        const fe s0 = f.at(12), s1 = f.at(13);
+        sink.set(0, fe_sub(f.next(0), fe_add(f.at(0), one)));
+        sink.set(2, fe_mul(b0, b1));
+        const fe nb0 = fe_sub(one, b0), nb1 = fe_sub(one, b1), nb2 = fe_sub(one, b2), nb3 = fe_sub(one, b3),
+                 nb4 = fe_sub(one, b4);
+        fe is_read2;
+        {
+            // flags.rs: the three selectors that start b0 (1 - b1)(1 - b2)
+            const fe pp = fe_mul(fe_mul(b0, nb1), nb2), pn3 = fe_mul(pp, nb3);
+            const fe d1 = fe_sub(f.next(13), s0);
+            sink.set(8, fe_mul(fe_mul(pn3, nb4), d1));
+            sink.set(9, fe_mul(fe_mul(pn3, b4), d1));
+            is_read2 = fe_mul(fe_mul(pp, b3), nb4);
+            sink.set(10, fe_mul(is_read2, fe_sub(f.next(17), s0)));
+        }
+        const fe is_noop = fe_mul(fe_mul(fe_mul(fe_mul(nb0, nb1), nb2), nb3), nb4);
+        sink.set(11, fe_mul(is_noop, fe_sub(s0n, s0)));
+        // the selectors that start (1 - b0) b1: add, sadd, add2, mul over (1 - b2), smul over b2
+        const fe q = fe_mul(nb0, b1), qa = fe_mul(q, nb2);
+        const fe is_add = fe_mul(fe_mul(qa, nb3), nb4), is_sadd = fe_mul(fe_mul(qa, b3), nb4),
+                 is_add2 = fe_mul(fe_mul(qa, b3), b4), is_mul = fe_mul(fe_mul(qa, nb3), b4),
+                 is_smul = fe_mul(fe_mul(fe_mul(q, b2), nb3), nb4);
+        sink.set(3, fe_mul(is_add, fe_sub(s0n, fe_add(s0, s1))));
+        sink.set(6, fe_mul(is_mul, fe_sub(s0n, fe_mul(s0, s1))));
+        // 1 depth: d' - d - b0 + b1 - 4 read2 + 4 add2
+        {
+            fe v = fe_add(fe_sub(fe_sub(f.next(11), f.at(11)), b0), b1);
+            fe r4 = fe_add(is_read2, is_read2), a4 = fe_add(is_add2, is_add2);
+            r4 = fe_add(r4, r4);
+            a4 = fe_add(a4, a4);
+            sink.set(1, fe_add(fe_sub(v, r4), a4));
+        }
+        ZK_SEQ(f.base, sink.wait(is_smul));
+        // 4 sadd / 5 add2 / 7 smul over the lwe_size ciphertext limbs (fhe/src/server_key.rs:89-124), limb by
+        // limb as the reference sums them
+        fe a4 = fe_zero(), a5 = fe_zero(), a7 = fe_zero();
+        for (int i = 0; i < L; i++) {
+            const fe sn = f.next(12 + i), si1 = f.at(13 + i);
+            const fe triv = i == L - 1 ? fe_mul(s0, delta) : fe_zero();  // encrypt_trivial: delta s0 in the body
+            a4 = fe_add(a4, fe_sub(sn, fe_add(si1, triv)));
+            a5 = fe_add(a5, fe_sub(sn, fe_add(f.at(12 + i), f.at(12 + L + i))));
+            a7 = fe_add(a7, fe_sub(sn, fe_mul(si1, s0)));
+        }
+        sink.set(4, fe_mul(is_sadd, a4));
+        sink.set(5, fe_mul(is_add2, a5));
+        sink.set(7, fe_mul(is_smul, a7));
+    }
+}
+
 // The launch-uniform multipliers of one evaluation (composition coefficients and what the host folds from them, delta)
 // are never held in registers or LDS: each product reads its W set from AirConsts::ws by scalar loads at the point of
 // use (fe_mul_uniform and the lazy acc192 / acc288_madd_uniform sums, f128.hpp), 16 SGPRs for the length of one
@@ -1949,8 +2096,9 @@ hipError_t eval_constraints(hipStream_t st, int KX, const fe *lde, int log_n, Ev
 // evaluate_transition (air/src/lib.rs:104-168, constrains.rs:95-216, flags.rs:37-91) at the n - 2 trace-domain
 // steps with the raw periodic values (row s mod 16 of CYCLE_MASK || round constants, lib.rs:201-225), each of the
 // 20 values tested against zero on its own, and the 22 assertions of get_assertions (lib.rs:170-195) in that
-// method's order.  An evaluator body of its own: no coefficient, no divisor, no extension plane, nothing shared
-// with k_eval_constraints but the small helpers (cube, mds_row, adj_row with the 3^-72 correction, ZK_SEQ).
+// method's order.  The 20 values are transition_constraints' (the plain body above, shared with k_transition_quotients;
+// with k_eval_constraints only the small helpers are shared), collected by ZeroMaskSink.  Everything else is here: the
+// assertion threads, the early exit, the reduction and the window arguments.
 // One thread per step s < n - 2; lane l of a wave reads trace[c n + s] and trace[c n + s + 1], consecutive 16-B
 // elements across the lanes.  Every operation returns the canonical representative, so "value != 0" is the exact
 // test on canonical trace cells.
@@ -1987,123 +2135,12 @@ __device__ __forceinline__ void validate_body(const fe *trace, size_t n, size_t 
         if (!fe_eq(want, got)) atomicOr(&rep->a_mask, 1u << k);
         rep->a_found[k] = got;
     }
-    unsigned mask = 0;
+    ZeroMaskSink sink;
     if (s < steps) {
-        const fe *tb = trace;  // laundered by ZK_SEQ between the sections
-#define VCUR(c) tb[(size_t)(c)*ld + s]
-#define VNXT(c) tb[(size_t)(c)*ld + s + 1]
-#define VSET(k, val) mask |= fe_is_zero(val) ? 0u : (1u << (k))
-        const fe one = fe_one();
-        // only the mask is live across the two sections: the five bits and s0' wait in a lane-private LDS slot (with
-        // them in registers the Rescue section spilled 22 VGPRs at this occupancy), and the complements and the
-        // selectors are formed where they are used
-        {
-            const fe b0 = VCUR(5), b1 = VCUR(4), b2 = VCUR(3), b3 = VCUR(2), b4 = VCUR(1);
-            const fe s0n = VNXT(12);
-            vstash[0][tid] = b0;
-            vstash[1][tid] = b1;
-            vstash[2][tid] = b2;
-            vstash[3][tid] = b3;
-            vstash[4][tid] = b4;
-            vstash[5][tid] = s0n;
-            // 12..15 Rescue round, 16..19 copy (constrains.rs:182-216)
-            // flags.rs: is_push = b0 (1 - b1)(1 - b2)(1 - b3)(1 - b4)
-            const fe is_push = fe_mul(fe_mul(fe_mul(fe_mul(b0, fe_sub(one, b1)), fe_sub(one, b2)), fe_sub(one, b3)),
-                                      fe_sub(one, b4));
-            fe opc = b0;  // 16 b0 + 8 b1 + 4 b2 + 2 b3 + b4
-            opc = fe_add(fe_add(opc, opc), b1);
-            opc = fe_add(fe_add(opc, opc), b2);
-            opc = fe_add(fe_add(opc, opc), b3);
-            opc = fe_add(fe_add(opc, opc), b4);
-            const fe push_term = fe_mul(s0n, is_push);
-            ZK_SEQ(tb, push_term.lo);
-            const fe *per = per_tab + ((s + first) & 15) * 9;
-            const fe c7 = VCUR(7), c8 = VCUR(8);
-            fe x[4] = {cube(c7), cube(c8), cube(VCUR(9)), cube(VCUR(10))};
-            fe m0[4];
-#pragma unroll
-            for (int r = 0; r < 4; r++) m0[r] = fe_add(mds_row(r, x), per[1 + r]);
-            m0[0] = fe_add(m0[0], opc);
-            m0[1] = fe_add(m0[1], push_term);
-            ZK_SEQ(tb, m0[3].lo);
-            const fe hf = per[0], h0 = VCUR(6);
-            fe y[4];
-            {
-                // 16..19 first: the next-row sponge words are consumed as they arrive
-                const fe nf = fe_sub(one, hf);
-                const fe n7 = VNXT(7), n8 = VNXT(8), n9 = VNXT(9), n10 = VNXT(10);
-                VSET(16, fe_mul(fe_mul(fe_sub(n7, c7), nf), h0));
-                VSET(17, fe_mul(fe_mul(fe_sub(n8, c8), nf), h0));
-                VSET(18, fe_mul(fe_mul(n9, nf), h0));
-                VSET(19, fe_mul(fe_mul(n10, nf), h0));
-                y[0] = fe_sub(n7, per[5]);
-                y[1] = fe_sub(n8, per[6]);
-                y[2] = fe_sub(n9, per[7]);
-                y[3] = fe_sub(n10, per[8]);
-            }
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                // (INV_MDS y)_r^3 = (adj_r y)^3 3^-72
-                const fe v3 = fe_mul(cube(adj_row(r, y)), ZK_INV3_72);
-                VSET(12 + r, fe_mul(fe_mul(fe_sub(v3, m0[r]), hf), h0));
-            }
-        }
-        ZK_SEQ(tb, mask);
-        {
-            // 0 clock, 2 shift, 8..11 the selectors that move one value
-            const fe b0 = vstash[0][tid], b1 = vstash[1][tid], b2 = vstash[2][tid], b3 = vstash[3][tid],
-                     b4 = vstash[4][tid], s0n = vstash[5][tid];
-            const fe s0 = VCUR(12), s1 = VCUR(13);
-            VSET(0, fe_sub(VNXT(0), fe_add(VCUR(0), one)));
-            VSET(2, fe_mul(b0, b1));
-            const fe nb0 = fe_sub(one, b0), nb1 = fe_sub(one, b1), nb2 = fe_sub(one, b2), nb3 = fe_sub(one, b3),
-                     nb4 = fe_sub(one, b4);
-            fe is_read2;
-            {
-                // flags.rs: the three selectors that start b0 (1 - b1)(1 - b2)
-                const fe pp = fe_mul(fe_mul(b0, nb1), nb2), pn3 = fe_mul(pp, nb3);
-                const fe d1 = fe_sub(VNXT(13), s0);
-                VSET(8, fe_mul(fe_mul(pn3, nb4), d1));
-                VSET(9, fe_mul(fe_mul(pn3, b4), d1));
-                is_read2 = fe_mul(fe_mul(pp, b3), nb4);
-                VSET(10, fe_mul(is_read2, fe_sub(VNXT(17), s0)));
-            }
-            const fe is_noop = fe_mul(fe_mul(fe_mul(fe_mul(nb0, nb1), nb2), nb3), nb4);
-            VSET(11, fe_mul(is_noop, fe_sub(s0n, s0)));
-            // the selectors that start (1 - b0) b1: add, sadd, add2, mul over (1 - b2), smul over b2
-            const fe q = fe_mul(nb0, b1), qa = fe_mul(q, nb2);
-            const fe is_add = fe_mul(fe_mul(qa, nb3), nb4), is_sadd = fe_mul(fe_mul(qa, b3), nb4),
-                     is_add2 = fe_mul(fe_mul(qa, b3), b4), is_mul = fe_mul(fe_mul(qa, nb3), b4),
-                     is_smul = fe_mul(fe_mul(fe_mul(q, b2), nb3), nb4);
-            VSET(3, fe_mul(is_add, fe_sub(s0n, fe_add(s0, s1))));
-            VSET(6, fe_mul(is_mul, fe_sub(s0n, fe_mul(s0, s1))));
-            // 1 depth: d' - d - b0 + b1 - 4 read2 + 4 add2
-            {
-                fe v = fe_add(fe_sub(fe_sub(VNXT(11), VCUR(11)), b0), b1);
-                fe r4 = fe_add(is_read2, is_read2), a4 = fe_add(is_add2, is_add2);
-                r4 = fe_add(r4, r4);
-                a4 = fe_add(a4, a4);
-                VSET(1, fe_add(fe_sub(v, r4), a4));
-            }
-            ZK_SEQ(tb, mask);
-            // 4 sadd / 5 add2 / 7 smul over the lwe_size ciphertext limbs (fhe/src/server_key.rs:89-124), limb by
-            // limb as the reference sums them
-            fe a4 = fe_zero(), a5 = fe_zero(), a7 = fe_zero();
-            for (int i = 0; i < L; i++) {
-                const fe sn = VNXT(12 + i), si1 = VCUR(13 + i);
-                const fe triv = i == L - 1 ? fe_mul(s0, delta) : fe_zero();  // encrypt_trivial: delta s0 in the body
-                a4 = fe_add(a4, fe_sub(sn, fe_add(si1, triv)));
-                a5 = fe_add(a5, fe_sub(sn, fe_add(VCUR(12 + i), VCUR(12 + L + i))));
-                a7 = fe_add(a7, fe_sub(sn, fe_mul(si1, s0)));
-            }
-            VSET(4, fe_mul(is_sadd, a4));
-            VSET(5, fe_mul(is_add2, a5));
-            VSET(7, fe_mul(is_smul, a7));
-        }
-#undef VCUR
-#undef VNXT
-#undef VSET
+        FrameRows f{trace, ld, s, s + 1};
+        transition_constraints(f, per_tab + ((s + first) & 15) * 9, delta, L, vstash, tid, sink);
     }
+    const unsigned mask = sink.mask;
     // block-uniform: a block without a failing step is done
     if (!__syncthreads_or(mask != 0)) return;
     const int wave = tid >> 6, lane = tid & 63;
@@ -2175,10 +2212,11 @@ hipError_t validate_trace(hipStream_t st, const fe *trace, size_t n, const fe *p
 // transition divisor; the host interpolates the 20 x 8 coset planes with the composition's interpolation (ntt inverse
 // per coset, then k_comp_cross) and k_poly_degrees finds each quotient's degree.
 // One thread per CE row with k_eval_constraints' row mapping (coset-major LDE, EvalMap, frame partner q + 1), the
-// periodic values from the evaluator's CE-domain table and the divisor inverse from plane 0 of divisor_tables.  The
-// body is k_validate_trace's, constraint by constraint, with a store where that kernel tests for zero: no coefficient,
-// no folding of constraints into each other.  quot[k 8n + jl n + q] = C_k(x) / D(x), CE-coset-major per constraint,
-// each value stored as soon as it is formed: beside the validate body's state only the divisor inverse is live.
+// periodic values from the evaluator's CE-domain table (row i mod 128: the same 9 values per row as the validator's raw
+// table) and the divisor inverse from plane 0 of divisor_tables.  The constraint values are transition_constraints',
+// the body the validator runs, with QuotientSink's store where ZeroMaskSink tests for zero.  quot[k 8n + jl n + q] =
+// C_k(x) / D(x), CE-coset-major per constraint, each value stored as soon as it is formed: beside the body's state only
+// the divisor inverse is live.  Threads past the CE domain return before the body, which has no barrier.
 __global__ void __launch_bounds__(256, ZK_EVAL_WAVES) k_transition_quotients(const fe *lde, int log_n, EvalMap map,
                                                                               const fe *periodic, const fe *divs,
                                                                               fe delta, int L, fe *quot) {
@@ -2190,120 +2228,9 @@ __global__ void __launch_bounds__(256, ZK_EVAL_WAVES) k_transition_quotients(con
     if (t_id >= CE) return;
     const size_t jl = t_id >> log_n, q = t_id & (n - 1), qn = (q + 1) & (n - 1);
     const size_t i = map.ce0 + map.cestep * jl + 8 * q;  // the CE step
-    const fe *tb = lde + (jl << map.lshift) * n;          // laundered by ZK_SEQ between the sections
-    const size_t cs = (size_t)map.lde_cosets * n;
-    const fe dT = divs[t_id];
-    fe *qo = quot + t_id;
-#define VCUR(c) tb[(size_t)(c)*cs + q]
-#define VNXT(c) tb[(size_t)(c)*cs + qn]
-#define VSET(k, val) qo[(size_t)(k)*CE] = fe_mul((val), dT)
-    const fe one = fe_one();
-    {
-        const fe b0 = VCUR(5), b1 = VCUR(4), b2 = VCUR(3), b3 = VCUR(2), b4 = VCUR(1);
-        const fe s0n = VNXT(12);
-        vstash[0][tid] = b0;
-        vstash[1][tid] = b1;
-        vstash[2][tid] = b2;
-        vstash[3][tid] = b3;
-        vstash[4][tid] = b4;
-        vstash[5][tid] = s0n;
-        // 12..15 Rescue round, 16..19 copy (constrains.rs:182-216)
-        // flags.rs: is_push = b0 (1 - b1)(1 - b2)(1 - b3)(1 - b4)
-        const fe is_push = fe_mul(fe_mul(fe_mul(fe_mul(b0, fe_sub(one, b1)), fe_sub(one, b2)), fe_sub(one, b3)),
-                                  fe_sub(one, b4));
-        fe opc = b0;  // 16 b0 + 8 b1 + 4 b2 + 2 b3 + b4
-        opc = fe_add(fe_add(opc, opc), b1);
-        opc = fe_add(fe_add(opc, opc), b2);
-        opc = fe_add(fe_add(opc, opc), b3);
-        opc = fe_add(fe_add(opc, opc), b4);
-        const fe push_term = fe_mul(s0n, is_push);
-        ZK_SEQ(tb, push_term.lo);
-        const fe *per = periodic + (i & 127) * 9;
-        const fe c7 = VCUR(7), c8 = VCUR(8);
-        fe x[4] = {cube(c7), cube(c8), cube(VCUR(9)), cube(VCUR(10))};
-        fe m0[4];
-#pragma unroll
-        for (int r = 0; r < 4; r++) m0[r] = fe_add(mds_row(r, x), per[1 + r]);
-        m0[0] = fe_add(m0[0], opc);
-        m0[1] = fe_add(m0[1], push_term);
-        ZK_SEQ(tb, m0[3].lo);
-        const fe hf = per[0], h0 = VCUR(6);
-        fe y[4];
-        {
-            // 16..19 first: the next-row sponge words are consumed as they arrive
-            const fe nf = fe_sub(one, hf);
-            const fe n7 = VNXT(7), n8 = VNXT(8), n9 = VNXT(9), n10 = VNXT(10);
-            VSET(16, fe_mul(fe_mul(fe_sub(n7, c7), nf), h0));
-            VSET(17, fe_mul(fe_mul(fe_sub(n8, c8), nf), h0));
-            VSET(18, fe_mul(fe_mul(n9, nf), h0));
-            VSET(19, fe_mul(fe_mul(n10, nf), h0));
-            y[0] = fe_sub(n7, per[5]);
-            y[1] = fe_sub(n8, per[6]);
-            y[2] = fe_sub(n9, per[7]);
-            y[3] = fe_sub(n10, per[8]);
-        }
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            // (INV_MDS y)_r^3 = (adj_r y)^3 3^-72
-            const fe v3 = fe_mul(cube(adj_row(r, y)), ZK_INV3_72);
-            VSET(12 + r, fe_mul(fe_mul(fe_sub(v3, m0[r]), hf), h0));
-        }
-    }
-    ZK_SEQ(tb, dT.lo);
-    {
-        // 0 clock, 2 shift, 8..11 the selectors that move one value
-        const fe b0 = vstash[0][tid], b1 = vstash[1][tid], b2 = vstash[2][tid], b3 = vstash[3][tid],
-                 b4 = vstash[4][tid], s0n = vstash[5][tid];
-        const fe s0 = VCUR(12), s1 = VCUR(13);
-        VSET(0, fe_sub(VNXT(0), fe_add(VCUR(0), one)));
-        VSET(2, fe_mul(b0, b1));
-        const fe nb0 = fe_sub(one, b0), nb1 = fe_sub(one, b1), nb2 = fe_sub(one, b2), nb3 = fe_sub(one, b3),
-                 nb4 = fe_sub(one, b4);
-        fe is_read2;
-        {
-            // flags.rs: the three selectors that start b0 (1 - b1)(1 - b2)
-            const fe pp = fe_mul(fe_mul(b0, nb1), nb2), pn3 = fe_mul(pp, nb3);
-            const fe d1 = fe_sub(VNXT(13), s0);
-            VSET(8, fe_mul(fe_mul(pn3, nb4), d1));
-            VSET(9, fe_mul(fe_mul(pn3, b4), d1));
-            is_read2 = fe_mul(fe_mul(pp, b3), nb4);
-            VSET(10, fe_mul(is_read2, fe_sub(VNXT(17), s0)));
-        }
-        const fe is_noop = fe_mul(fe_mul(fe_mul(fe_mul(nb0, nb1), nb2), nb3), nb4);
-        VSET(11, fe_mul(is_noop, fe_sub(s0n, s0)));
-        // the selectors that start (1 - b0) b1: add, sadd, add2, mul over (1 - b2), smul over b2
-        const fe qq = fe_mul(nb0, b1), qa = fe_mul(qq, nb2);
-        const fe is_add = fe_mul(fe_mul(qa, nb3), nb4), is_sadd = fe_mul(fe_mul(qa, b3), nb4),
-                 is_add2 = fe_mul(fe_mul(qa, b3), b4), is_mul = fe_mul(fe_mul(qa, nb3), b4),
-                 is_smul = fe_mul(fe_mul(fe_mul(qq, b2), nb3), nb4);
-        VSET(3, fe_mul(is_add, fe_sub(s0n, fe_add(s0, s1))));
-        VSET(6, fe_mul(is_mul, fe_sub(s0n, fe_mul(s0, s1))));
-        // 1 depth: d' - d - b0 + b1 - 4 read2 + 4 add2
-        {
-            fe v = fe_add(fe_sub(fe_sub(VNXT(11), VCUR(11)), b0), b1);
-            fe r4 = fe_add(is_read2, is_read2), a4 = fe_add(is_add2, is_add2);
-            r4 = fe_add(r4, r4);
-            a4 = fe_add(a4, a4);
-            VSET(1, fe_add(fe_sub(v, r4), a4));
-        }
-        ZK_SEQ(tb, is_smul.lo);
-        // 4 sadd / 5 add2 / 7 smul over the lwe_size ciphertext limbs (fhe/src/server_key.rs:89-124), limb by
-        // limb as the reference sums them
-        fe a4 = fe_zero(), a5 = fe_zero(), a7 = fe_zero();
-        for (int l = 0; l < L; l++) {
-            const fe sn = VNXT(12 + l), si1 = VCUR(13 + l);
-            const fe triv = l == L - 1 ? fe_mul(s0, delta) : fe_zero();  // encrypt_trivial: delta s0 in the body
-            a4 = fe_add(a4, fe_sub(sn, fe_add(si1, triv)));
-            a5 = fe_add(a5, fe_sub(sn, fe_add(VCUR(12 + l), VCUR(12 + L + l))));
-            a7 = fe_add(a7, fe_sub(sn, fe_mul(si1, s0)));
-        }
-        VSET(4, fe_mul(is_sadd, a4));
-        VSET(5, fe_mul(is_add2, a5));
-        VSET(7, fe_mul(is_smul, a7));
-    }
-#undef VCUR
-#undef VNXT
-#undef VSET
+    FrameRows f{lde + (jl << map.lshift) * n, (size_t)map.lde_cosets * n, q, qn};
+    QuotientSink sink{quot + t_id, CE, divs[t_id]};
+    transition_constraints(f, periodic + (i & 127) * 9, delta, L, vstash, tid, sink);
 }
 
 hipError_t transition_quotients(hipStream_t st, const fe *lde, int log_n, EvalMap map, const fe *periodic,

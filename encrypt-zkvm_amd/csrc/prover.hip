@@ -1877,30 +1877,49 @@ int zk::validation_from_partials(const ValPartial *parts, int world, size_t n, c
     return rc;
 }
 
-static int check_validate_args(zk_prover *p, const void *trace, size_t n, const zk_pub_inputs *pub, zk_validation *out) {
+// ---- the scaffold of the two stand-alone checks (trace validation above, constraint degrees below)
+// the arguments of their four entry points; trace: the device pointer or the column table, out: the report
+static int check_standalone_args(zk_prover *p, const void *trace, size_t n, const zk_pub_inputs *pub, const void *out) {
     if (!p || !trace || !pub || !out) ZK_FAIL(ZK_ERR_INVALID_ARG, "null argument");
     ZK_REQUIRE_FULL_PROVER(p);
     ZK_TRY(check_trace_len(n, p->max_n));
     return check_lwe_size(pub);
 }
 
+// check(p->d_trace) on the 28 host columns: one full upload, every column whole (a debugging aid: none of the prove
+// path's column classes).  The caller's columns are free again on every way out, a failed copy included.
+template <class Check>
+static int with_uploaded_columns(zk_prover *p, const uint8_t *const *columns, size_t n, Check check) {
+    for (int c = 0; c < W; c++)
+        if (!columns[c]) ZK_FAIL(ZK_ERR_INVALID_ARG, "null trace column");
+    ZK_CHECK_HIP(hipSetDevice(p->device));
+    const int rc = [&]() -> int {
+        for (int c = 0; c < W; c++)
+            ZK_CHECK_HIP(hipMemcpyAsync(p->d_trace + (size_t)c * n, columns[c], n * sizeof(fe), hipMemcpyHostToDevice, p->st));
+        return check(p->d_trace);
+    }();
+    (void)hipStreamSynchronize(p->st);
+    return rc;
+}
+
+// The gate of a check the prove entry points run first (zk_prover_set_validate / _validate_degrees): its switch is on,
+// and the call is one prove_impl would enter on a full prover.  Arguments the prove path would refuse are left for it
+// to report.
+static bool check_runs_first(const zk_prover *p, bool zk_prover::*on, size_t n, const zk_options *opt,
+                             const zk_pub_inputs *pub, const size_t *proof_len) {
+    if (!p || !(p->*on) || !proof_len || p->shard_world > 1) return false;
+    return check_prove_args(n, p->max_n, p->max_b, opt, pub) == ZK_OK;
+}
+
 int zk_validate_device(zk_prover *p, const void *d_trace, size_t n, const zk_pub_inputs *pub, zk_validation *out) {
-    ZK_TRY(check_validate_args(p, d_trace, n, pub, out));
+    ZK_TRY(check_standalone_args(p, d_trace, n, pub, out));
     return validate_on_device(p, (const fe *)d_trace, n, pub, out);
 }
 
 int zk_validate_columns(zk_prover *p, const uint8_t *const *columns, size_t n, const zk_pub_inputs *pub,
                         zk_validation *out) {
-    ZK_TRY(check_validate_args(p, columns, n, pub, out));
-    for (int c = 0; c < W; c++)
-        if (!columns[c]) ZK_FAIL(ZK_ERR_INVALID_ARG, "null trace column");
-    ZK_CHECK_HIP(hipSetDevice(p->device));
-    // one full upload, every column whole (a debugging aid: none of the prove path's column classes)
-    for (int c = 0; c < W; c++)
-        ZK_CHECK_HIP(hipMemcpyAsync(p->d_trace + (size_t)c * n, columns[c], n * sizeof(fe), hipMemcpyHostToDevice, p->st));
-    const int rc = validate_on_device(p, p->d_trace, n, pub, out);
-    (void)hipStreamSynchronize(p->st);  // the caller's columns are free again on every way out
-    return rc;
+    ZK_TRY(check_standalone_args(p, columns, n, pub, out));
+    return with_uploaded_columns(p, columns, n, [&](const fe *t) { return validate_on_device(p, t, n, pub, out); });
 }
 
 int zk_prover_set_validate(zk_prover *p, int on) {
@@ -1916,13 +1935,11 @@ int zk_prover_validation(const zk_prover *p, zk_validation *out) {
     return ZK_OK;
 }
 
-// zk_prover_set_validate(p, 1): Trace::validate before the proof.  Arguments the prove path would refuse are left
-// for it to report; a failing trace ends the call with ZK_ERR_TRACE and an empty proof before prove_impl is entered,
-// so no hint or snapshot state moves.
+// zk_prover_set_validate(p, 1): Trace::validate before the proof (check_runs_first).  A failing trace ends the call
+// with ZK_ERR_TRACE and an empty proof before prove_impl is entered, so no hint or snapshot state moves.
 static int validate_first(zk_prover *p, const void *d_trace, const uint8_t *const *cols, size_t n, const zk_options *opt,
                           const zk_pub_inputs *pub, size_t *proof_len) {
-    if (!p || !p->validate || !proof_len || p->shard_world > 1) return ZK_OK;
-    if (check_prove_args(n, p->max_n, p->max_b, opt, pub) != ZK_OK) return ZK_OK;
+    if (!check_runs_first(p, &zk_prover::validate, n, opt, pub, proof_len)) return ZK_OK;
     zk_validation v;
     const int rc = cols ? zk_validate_columns(p, cols, n, pub, &v) : zk_validate_device(p, d_trace, n, pub, &v);
     if (rc != ZK_OK) *proof_len = 0;
@@ -2021,35 +2038,21 @@ static int degrees_on_device(zk_prover *p, const fe *d_trace, size_t n, const zk
                                 "\nactual:   " + rust_vec3(D.actual, NUM_TCONS));
 }
 
-static int check_degrees_args(zk_prover *p, const void *trace, size_t n, const zk_pub_inputs *pub, zk_degrees *out) {
-    if (!p || !trace || !pub || !out) ZK_FAIL(ZK_ERR_INVALID_ARG, "null argument");
-    ZK_REQUIRE_FULL_PROVER(p);
-    ZK_TRY(check_trace_len(n, p->max_n));
-    return check_lwe_size(pub);
-}
-
 static int degrees_columns(zk_prover *p, const uint8_t *const *columns, size_t n, const zk_pub_inputs *pub, uint32_t B,
                            zk_degrees *out, uint8_t *quotients_out) {
-    for (int c = 0; c < W; c++)
-        if (!columns[c]) ZK_FAIL(ZK_ERR_INVALID_ARG, "null trace column");
-    ZK_CHECK_HIP(hipSetDevice(p->device));
-    // one full upload, every column whole (a debugging aid: none of the prove path's column classes)
-    for (int c = 0; c < W; c++)
-        ZK_CHECK_HIP(hipMemcpyAsync(p->d_trace + (size_t)c * n, columns[c], n * sizeof(fe), hipMemcpyHostToDevice, p->st));
-    const int rc = degrees_on_device(p, p->d_trace, n, pub, B, out, quotients_out);
-    (void)hipStreamSynchronize(p->st);  // the caller's columns are free again on every way out
-    return rc;
+    return with_uploaded_columns(p, columns, n,
+                                 [&](const fe *t) { return degrees_on_device(p, t, n, pub, B, out, quotients_out); });
 }
 
 int zk_degrees_device(zk_prover *p, const void *d_trace, size_t n, const zk_pub_inputs *pub, zk_degrees *out,
                       uint8_t *quotients_out) {
-    ZK_TRY(check_degrees_args(p, d_trace, n, pub, out));
+    ZK_TRY(check_standalone_args(p, d_trace, n, pub, out));
     return degrees_on_device(p, (const fe *)d_trace, n, pub, 8, out, quotients_out);
 }
 
 int zk_degrees_columns(zk_prover *p, const uint8_t *const *columns, size_t n, const zk_pub_inputs *pub,
                        zk_degrees *out, uint8_t *quotients_out) {
-    ZK_TRY(check_degrees_args(p, columns, n, pub, out));
+    ZK_TRY(check_standalone_args(p, columns, n, pub, out));
     return degrees_columns(p, columns, n, pub, 8, out, quotients_out);
 }
 
@@ -2067,13 +2070,12 @@ int zk_prover_degrees(const zk_prover *p, zk_degrees *out) {
 }
 
 // zk_prover_set_validate_degrees(p, 1): validate_transition_degrees before the proof, after validate_first (the order
-// of a debug build).  As there, arguments the prove path would refuse are left for it to report, and a mismatch ends
-// the call before prove_impl is entered.  The CE cosets come from the tables of the proof's own blowup (cosets
-// 0, B/8, ... of its LDE domain are the CE domain), so no plan is built that the proof does not need.
+// of a debug build; check_runs_first).  As there, a mismatch ends the call before prove_impl is entered.  The CE cosets
+// come from the tables of the proof's own blowup (cosets 0, B/8, ... of its LDE domain are the CE domain), so no plan
+// is built that the proof does not need.
 static int degrees_first(zk_prover *p, const void *d_trace, const uint8_t *const *cols, size_t n, const zk_options *opt,
                          const zk_pub_inputs *pub, size_t *proof_len) {
-    if (!p || !p->validate_degrees || !proof_len || p->shard_world > 1) return ZK_OK;
-    if (check_prove_args(n, p->max_n, p->max_b, opt, pub) != ZK_OK) return ZK_OK;
+    if (!check_runs_first(p, &zk_prover::validate_degrees, n, opt, pub, proof_len)) return ZK_OK;
     zk_degrees d;
     const int rc = cols ? degrees_columns(p, cols, n, pub, opt->blowup, &d, nullptr)
                         : degrees_on_device(p, (const fe *)d_trace, n, pub, opt->blowup, &d, nullptr);

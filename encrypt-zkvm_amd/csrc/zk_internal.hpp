@@ -359,6 +359,8 @@ EvalMap eval_map_whole(int log_b, int nce, bool bnd);
 // bnd: the boundary (assertion) terms are evaluated per row (else: boundary_poly_add after interpolation)
 hipError_t eval_constraints(hipStream_t st, int KX, const fe *lde, int log_n, EvalMap map, const fe *periodic,
                             const fe *divs, const AirConsts *consts, size_t plane, fe *comp, bool bnd);
+// The project's own soundness checks, trace validation and transition constraint degrees: three kernels over one plain
+// reading of the 20 transition constraints (kernels.hip transition_constraints), apart from eval_constraints' tuned one.
 // Trace validation (kernels.hip k_validate_trace; zk_validate_device): the device report of one launch.  The host
 // initialises it in-stream: counts 0, firsts UINT64_MAX, a_mask 0 and a_found[k] = the value assertion k asserts
 // (get_assertions order, air/src/lib.rs:170-195), which the kernel replaces with the asserted cell's value.
@@ -381,7 +383,8 @@ hipError_t validate_window(hipStream_t st, const fe *win, size_t ld, size_t firs
                            const fe *per_tab, fe delta, int lwe_size, ValReport *rep);
 // Transition constraint degrees (kernels.hip k_transition_quotients, k_poly_degrees; zk_degrees_device).
 // transition_quotients: quot[k 8n + jl n + q] = C_k / D at CE row (jl, q) of `map` for the 20 constraints k of
-// evaluate_transition, no coefficients; lde, periodic and divs (plane 0 of divisor_tables) as eval_constraints.
+// evaluate_transition, the values validate_trace tests for zero, no coefficients; lde, periodic and divs (plane 0 of
+// divisor_tables) as eval_constraints.
 hipError_t transition_quotients(hipStream_t st, const fe *lde, int log_n, EvalMap map, const fe *periodic,
                                 const fe *divs, fe delta, int lwe_size, fe *quot);
 // top[k]: the highest non-zero coefficient index of polynomial k; nonzero bit k: it has one.  Zeroed in-stream.
