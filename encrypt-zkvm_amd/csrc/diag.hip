@@ -1174,3 +1174,90 @@ extern "C" int zk_diag_validate_window(int device, const uint8_t *trace, size_t 
     memcpy(partial_out, &P, sizeof P);
     return rc;
 }
+
+// ---------------------------------------------------------------- sharded proofs: the degree check's merge and ranges
+// The merge of `world` degree partials (world x sizeof(DegPartial) bytes) of a trace of n rows into the report and
+// status a sharded degree check returns (degrees_from_partials; the message in zk_last_error()).  No GPU.
+extern "C" int zk_diag_merge_degrees(const uint8_t *partials, int world, size_t n, zk_degrees *out) {
+    if (!partials || !out || world < 1 || world > 8 || n < 16 || (n & (n - 1)))
+        ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_merge_degrees: partials of 1 .. 8 ranks, n a power of two >= 16");
+    std::vector<DegPartial> P((size_t)world);
+    memcpy(P.data(), partials, P.size() * sizeof(DegPartial));
+    return degrees_from_partials(P.data(), world, n, nullptr, 0, out);
+}
+
+// Steps 3 to 6 of a sharded degree check (shard.hip DegreesSharded) on quotient VALUES of the caller's choice, on one
+// device in rank order, split into G = 2, 4 or 8 ranges exactly as G ranks split them.  quot: count <= 20 planes of 8n
+// canonical values over the CE domain in transition_quotients' layout, quot[k 8n + r n + q] = Q_k(3 w_8n^r w_n^q).
+// Rank s's planes (k, j) are cosets s Bl + j: its per-coset inverse transforms go to its own area [k Bl + j][n], the
+// production pack kernel (k_sh_pack_coset, count Bl planes) fills its send area, the all-to-all is device copies
+// (send area of s, chunk g -> receive area of g, chunk s), and per range g the production fused kernel
+// (cross_degrees, max_blocks as given) fills a report of its own, which becomes partial g.  partials_out: G x
+// sizeof(DegPartial); merged_out: the production merge's report (polynomials >= count read as zero); coeffs_out
+// (optional: the fused kernel then writes coefficients): count x 8n elements, coefficient i of polynomial k at
+// k 8n + i, assembled from the ranges' slices [k][k2][kl].  The status is the merge's (ZK_OK or ZK_ERR_DEGREES).
+extern "C" int zk_diag_degrees_parts(int device, const uint8_t *quot, size_t n, int count, int G, uint32_t max_blocks,
+                                     uint8_t *partials_out, zk_degrees *merged_out, uint8_t *coeffs_out) {
+    bool ok = quot && partials_out && merged_out && n >= 16 && !(n & (n - 1)) && n <= ((size_t)1 << 20) && count >= 1 &&
+              count <= NUM_TCONS && (G == 2 || G == 4 || G == 8) && n / (size_t)(G ? G : 1) >= 8;
+    for (size_t i = 0; ok && i < (size_t)count * 8 * n; i++) ok = fe_canonical(fe_from_bytes(quot + 16 * i));
+    if (!ok)
+        ZK_FAIL(ZK_ERR_INVALID_ARG, "zk_diag_degrees_parts: 1 .. 20 planes of 8n canonical values, n a power of two in "
+                                    "[16, 2^20], 2, 4 or 8 ranges of at least 8 coefficients");
+    DiagProver p;
+    ZK_TRY(p.open(device, n, 8, true));
+    Plan *pl = p.pl;
+    const int log_n = pl->log_n, Bl = 8 / G, planes = count * Bl;
+    const size_t CE = 8 * n, kg = n / (size_t)G, area = (size_t)planes * n;  // area: one rank's planes, = count 8 kg
+    fe *vals = p->tmp, *scratch = p->tmp + (size_t)NUM_TCONS * CE, *per = p->lde, *send = p->tmp, *recv = p->lde,
+       *coeffs = p->tmp;
+    ZK_TRY(p.up(vals, quot, (size_t)count * CE));
+    for (int s = 0; s < G; s++)
+        for (int k = 0; k < count; k++)
+            ntt(p->st, pl->Tn, vals + (size_t)k * CE + (size_t)s * Bl * n, n, per + s * area + (size_t)k * Bl * n, n, Bl,
+                true, nullptr, nullptr, scratch);
+    for (int s = 0; s < G; s++) diag_pack_coset(p->st, per + s * area, n, log_n, planes, ilog2(kg), send + s * area);
+    for (int g = 0; g < G; g++)
+        for (int s = 0; s < G; s++)
+            ZK_CHECK_HIP(hipMemcpyAsync(recv + g * area + (size_t)s * planes * kg, send + s * area + (size_t)g * planes * kg,
+                                        (size_t)planes * kg * sizeof(fe), hipMemcpyDeviceToDevice, p->st));
+    std::vector<DegPartial> parts((size_t)G);
+    const fe scale = h_inv(fe_make(CE)), w8inv = h_inv(h_root_of_unity(3)), inv3n = h_inv(h_pow(fe_make(3), n));
+    for (int g = 0; g < G; g++) {
+        DegCrossMap m;
+        m.c = recv + g * area;
+        for (int r = 0; r < 8; r++) m.off[r] = ((size_t)(r / Bl) * planes + (size_t)(r % Bl)) * kg;
+        m.cstride = (size_t)Bl * kg;
+        m.k0 = (size_t)g * kg;
+        m.kcount = kg;
+        m.log_n = log_n;
+        m.first = 0;
+        m.count = count;
+        m.coeffs = coeffs_out ? coeffs + g * area : nullptr;
+        ZK_CHECK_HIP(hipMemsetAsync(p->deg_rep, 0, sizeof(DegReport), p->st));
+        cross_degrees(p->st, m, pl->Tce, pl->inv3, scale, w8inv, inv3n, p->deg_rep, max_blocks);
+        ZK_CHECK_HIP(hipGetLastError());
+        DegReport R;
+        ZK_TRY(d2h_small(p, &R, p->deg_rep, sizeof R));
+        ZK_TRY(d2h_flush(p));
+        DegPartial &P = parts[g];
+        memset(&P, 0, sizeof P);
+        P.version = ZK_AGREE_VERSION;
+        P.rank = (uint32_t)g;
+        P.first = (uint64_t)g * kg;
+        P.count = kg;
+        P.nonzero = R.nonzero;
+        for (int k = 0; k < NUM_TCONS; k++) P.top[k] = R.top[k];
+    }
+    memcpy(partials_out, parts.data(), parts.size() * sizeof(DegPartial));
+    if (coeffs_out) {
+        std::vector<uint8_t> sl((size_t)count * CE * sizeof(fe));
+        ZK_TRY(p.down(sl.data(), coeffs, (size_t)count * CE));
+        for (int g = 0; g < G; g++)
+            for (int k = 0; k < count; k++)
+                for (int k2 = 0; k2 < 8; k2++)
+                    memcpy(coeffs_out + 16 * ((size_t)k * CE + (size_t)k2 * n + (size_t)g * kg),
+                           sl.data() + 16 * ((size_t)g * area + ((size_t)k * 8 + k2) * kg), 16 * kg);
+    }
+    return degrees_from_partials(parts.data(), G, n, nullptr, 0, merged_out);
+}

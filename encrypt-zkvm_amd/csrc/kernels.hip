@@ -2349,6 +2349,101 @@ void comp_cross_mapped(hipStream_t st, const CrossMap &m, const NttTables &T8n, 
                                                  nonzero_flag));
 }
 
+// The cross-coset step fused with the degree scan (a sharded degree check's coefficient range, DegCrossMap): one
+// thread per k1 of the range and constraint (blockIdx.y), the 8 per-coset coefficients in registers, k_comp_cross's
+// twiddle products and radix-2 DFT in its order, then per block k2 the test for zero.  COEFFS: the 8 coefficients
+// a[k1 + n k2] = b_k2 scale 3^-(k1 + n k2) are formed as k_comp_cross forms them, stored, and tested; else nothing is
+// stored and b_k2 itself is tested -- the factor is non-zero, so the 9 products it costs per thread decide nothing.  A
+// thread keeps the highest global index + 1 it met (not ascending: a higher block k2 beats any k1), the block reduces
+// by wave shuffles and LDS as k_poly_degrees does, then one atomicMax and one atomicOr per block and constraint.  Every
+// thread reaches the shuffles and the barrier: a thread past the range only skips the loop body.
+template <bool COEFFS>
+__global__ void __launch_bounds__(256) k_cross_degrees(DegCrossMap m, const fe *wi_lo, const fe *wi_hi,
+                                                       const fe *i3_lo, const fe *i3_hi, fe scale, CrossWs cw,
+                                                       DegReport *rep) {
+    __shared__ unsigned long long sh_top[4];
+    const int k = blockIdx.y;
+    const fe *c = m.c + (size_t)k * m.cstride;
+    unsigned long long top = 0;  // highest non-zero global index + 1
+    for (size_t kl = blockIdx.x * (size_t)blockDim.x + threadIdx.x; kl < m.kcount; kl += (size_t)gridDim.x * blockDim.x) {
+        const size_t k1 = m.k0 + kl;
+        fe w = pow_split(wi_lo, wi_hi, k1);  // w_8n^-k1
+        fe d[8];
+        fe wr = fe_one();
+#pragma unroll
+        for (int r = 0; r < 8; r++) {
+            fe v = c[m.off[r] + kl];
+            d[r] = r ? fe_mul(v, wr) : v;
+            wr = fe_mul(wr, w);
+        }
+        fe e0 = d[0], e1 = d[4], e2 = d[2], e3 = d[6], e4 = d[1], e5 = d[5], e6 = d[3], e7 = d[7];
+        fe t0 = fe_add(e0, e1), t1 = fe_sub(e0, e1), t2 = fe_add(e2, e3), t3 = fe_sub(e2, e3);
+        fe t4 = fe_add(e4, e5), t5 = fe_sub(e4, e5), t6 = fe_add(e6, e7), t7 = fe_sub(e6, e7);
+        t3 = fe_mul_uniform(t3, cw.w2);
+        t7 = fe_mul_uniform(t7, cw.w2);
+        fe u0 = fe_add(t0, t2), u2 = fe_sub(t0, t2), u1 = fe_add(t1, t3), u3 = fe_sub(t1, t3);
+        fe u4 = fe_add(t4, t6), u6 = fe_sub(t4, t6), u5 = fe_add(t5, t7), u7 = fe_sub(t5, t7);
+        u5 = fe_mul_uniform(u5, cw.w1);
+        u6 = fe_mul_uniform(u6, cw.w2);
+        u7 = fe_mul_uniform(u7, cw.w3);
+        fe bk[8] = {fe_add(u0, u4), fe_add(u1, u5), fe_add(u2, u6), fe_add(u3, u7),
+                    fe_sub(u0, u4), fe_sub(u1, u5), fe_sub(u2, u6), fe_sub(u3, u7)};
+        int hi = -1;  // the highest block with a non-zero coefficient at this k1
+        if constexpr (COEFFS) {
+            fe *out = m.coeffs + (size_t)(m.first + k) * 8 * m.kcount + kl;
+            fe s = fe_mul(scale, pow_split(i3_lo, i3_hi, k1));
+#pragma unroll
+            for (int k2 = 0; k2 < 8; k2++) {
+                const fe a = fe_mul(bk[k2], s);
+                out[(size_t)k2 * m.kcount] = a;
+                if (!fe_is_zero(a)) hi = k2;
+                s = fe_mul_uniform(s, cw.inv3n);
+            }
+        } else {
+#pragma unroll
+            for (int k2 = 0; k2 < 8; k2++)
+                if (!fe_is_zero(bk[k2])) hi = k2;
+        }
+        if (hi >= 0) {
+            const unsigned long long g = k1 + ((unsigned long long)hi << m.log_n) + 1;
+            top = g > top ? g : top;
+        }
+    }
+    for (int dd = 32; dd > 0; dd >>= 1) {
+        const unsigned long long o = __shfl_xor(top, dd, 64);
+        top = o > top ? o : top;
+    }
+    if ((threadIdx.x & 63) == 0) sh_top[threadIdx.x >> 6] = top;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int wv = 1; wv < 4; wv++) top = sh_top[wv] > top ? sh_top[wv] : top;
+        if (top) {
+            atomicMax(&rep->top[m.first + k], top - 1);
+            atomicOr(&rep->nonzero, 1u << (m.first + k));
+        }
+    }
+}
+
+void cross_degrees(hipStream_t st, const DegCrossMap &m, const NttTables &T8n, const PowTable &inv3, fe scale, fe w8inv,
+                   fe inv3n, DegReport *rep, unsigned max_blocks) {
+    unsigned blocks = cdiv(m.kcount, 256);
+    if (!max_blocks) max_blocks = 4096;
+    if (blocks > max_blocks) blocks = max_blocks;
+    CrossWs cw = {};
+    const fe w2 = fe_mul(w8inv, w8inv);
+    cw.w1 = make_fe_ws(w8inv), cw.w2 = make_fe_ws(w2), cw.w3 = make_fe_ws(fe_mul(w2, w8inv));
+    cw.inv3n = make_fe_ws(inv3n);
+    const dim3 grid(blocks, m.count);
+    if (m.coeffs)
+        ZK_PROF(st, "cross_degrees", 256.0 * m.count * (double)m.kcount,
+                hipLaunchKernelGGL(k_cross_degrees<true>, grid, dim3(256), 0, st, m, T8n.inv_lo, T8n.inv_hi, inv3.lo,
+                                   inv3.hi, scale, cw, rep));
+    else
+        ZK_PROF(st, "cross_degrees", 128.0 * m.count * (double)m.kcount,
+                hipLaunchKernelGGL(k_cross_degrees<false>, grid, dim3(256), 0, st, m, T8n.inv_lo, T8n.inv_hi, inv3.lo,
+                                   inv3.hi, scale, cw, rep));
+}
+
 // ================================================================ OOD evaluation
 // One pass over every polynomial of the OOD frame: T_c(z), T_c(zg) for the trace columns and
 // H_j(z) for the composition columns.  A wave owns the coefficient chunk [base, base + 64E):

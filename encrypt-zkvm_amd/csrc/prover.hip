@@ -1957,17 +1957,8 @@ static int validate_first(zk_prover *p, const void *d_trace, const uint8_t *cons
 //   p->tmp    (28 x 8n) the four-step scratch of the front, then the 20 x 8n quotient values with the 8 x 8n behind them
 //             as the four-step scratch of their inverse transforms (groups of 8 constraints), and last, the values
 //             consumed, the 20 x 8n coefficients the cross-coset step writes (read by k_poly_degrees and quotients_out).
-// Rust's {:>3?} of a Vec<usize>: every element right-aligned in 3 columns
-static std::string rust_vec3(const uint64_t *v, int k) {
-    std::string s = "[";
-    for (int i = 0; i < k; i++) {
-        std::string e = std::to_string(v[i]);
-        if (e.size() < 3) e.insert(0, 3 - e.size(), ' ');
-        s += (i ? ", " : "") + e;
-    }
-    return s + "]";
-}
-
+// (the report and winterfell's message from the tops: shard_agree.hpp degrees_report / degrees_message, shared with
+// a sharded proof's merge)
 // the trace is on p's device at d_trace; arguments are checked.  B: the blowup whose plan lends its tables
 static int degrees_on_device(zk_prover *p, const fe *d_trace, size_t n, const zk_pub_inputs *pub, uint32_t B,
                              zk_degrees *out, uint8_t *quotients_out) {
@@ -2014,28 +2005,45 @@ static int degrees_on_device(zk_prover *p, const fe *d_trace, size_t n, const zk
         ZK_CHECK_HIP(hipStreamSynchronize(p->st));
     }
     collect_kernel_stats(p);  // (zk_prover_profile: a stand-alone check's kernels are counted like a proof's)
-    zk_degrees D;
-    memset(&D, 0, sizeof D);
-    D.trace_len = n;
-    D.ce_len = CE;
-    const DeclaredDegrees &decl = air_declared_degrees();
-    for (int k = 0; k < NUM_TCONS; k++) {
+    for (int k = 0; k < NUM_TCONS; k++)
         if (R.top[k] >= CE) ZK_FAIL(ZK_ERR_DEVICE, "constraint degrees: the device reported a coefficient outside the domain");
-        D.expected[k] = decl.evaluation_degree(k, n) - (n - 2);
-        D.actual[k] = R.top[k];
-        if (!((R.nonzero >> k) & 1u)) D.zero_mask |= 1u << k;
-        if (D.actual[k] != D.expected[k]) D.mismatch_mask |= 1u << k;
-        if (D.actual[k] > D.expected[k]) D.over_mask |= 1u << k;
-        D.max_actual = std::max(D.max_actual, D.actual[k]);
-    }
-    D.ce_len_needed = 1;
-    while (D.ce_len_needed < std::max<uint64_t>(D.max_actual, n + 1)) D.ce_len_needed *= 2;
+    zk_degrees D;
+    uint64_t top[NUM_TCONS];
+    for (int k = 0; k < NUM_TCONS; k++) top[k] = R.top[k];
+    degrees_report(n, top, R.nonzero, &D);
     p->deg_last = D;
     p->deg_have = true;
     *out = D;
     if (!D.mismatch_mask) return ZK_OK;
-    ZK_FAIL(ZK_ERR_DEGREES, "transition constraint degrees didn't match\nexpected: " + rust_vec3(D.expected, NUM_TCONS) +
-                                "\nactual:   " + rust_vec3(D.actual, NUM_TCONS));
+    ZK_FAIL(ZK_ERR_DEGREES, degrees_message(D));
+}
+
+// The merged report of `world` partials (merge_degrees) of a sharded degree check of a trace of n rows, stored in each
+// of the provers P (zk_prover_degrees).  ZK_OK, ZK_ERR_DEGREES with zk_degrees_device's message, or -- a rank's partial
+// carries an error -- ZK_ERR_PEER naming the lowest such rank.
+int zk::degrees_from_partials(const DegPartial *parts, int world, size_t n, zk_prover *const *P, int np,
+                              zk_degrees *out) {
+    zk_degrees D;
+    int bad = -1;
+    if (merge_degrees(parts, world, n, &D, &bad) != ZK_OK) {
+        if (parts[bad].version != ZK_AGREE_VERSION)
+            ZK_FAIL(ZK_ERR_PEER, "rank " + std::to_string(bad) + " sent a degree partial of layout version " +
+                                     std::to_string(parts[bad].version));
+        if (parts[bad].status == ZK_OK)
+            ZK_FAIL(ZK_ERR_PEER, "rank " + std::to_string(bad) + " reported a coefficient outside the domain");
+        char m[ZK_AGREE_MSG + 1];
+        memcpy(m, parts[bad].msg, ZK_AGREE_MSG);
+        m[ZK_AGREE_MSG] = 0;
+        ZK_FAIL(ZK_ERR_PEER, "rank " + std::to_string(bad) + " could not check its coefficients: " +
+                                 std::to_string(parts[bad].status) + ": " + m);
+    }
+    for (int l = 0; l < np; l++) {
+        P[l]->deg_last = D;
+        P[l]->deg_have = true;
+    }
+    if (out) *out = D;
+    if (!D.mismatch_mask) return ZK_OK;
+    ZK_FAIL(ZK_ERR_DEGREES, degrees_message(D));
 }
 
 static int degrees_columns(zk_prover *p, const uint8_t *const *columns, size_t n, const zk_pub_inputs *pub, uint32_t B,

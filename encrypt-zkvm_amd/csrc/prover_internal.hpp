@@ -511,6 +511,11 @@ int validate_window_partial(zk_prover *p, const fe *win, size_t ld, size_t n, co
                             const zk_pub_inputs *pub, int rank, ValPartial *out);
 int validation_from_partials(const ValPartial *parts, int world, size_t n, const zk_pub_inputs *pub,
                              zk_prover *const *P, int np, zk_validation *out);
+// a sharded proof's degree check (shard.hip DegreesSharded): the merged report of the ranks' partials
+int degrees_from_partials(const DegPartial *parts, int world, size_t n, zk_prover *const *P, int np, zk_degrees *out);
+// shard.hip's k_sh_pack_coset on planes of the caller's choice (diag.hip zk_diag_degrees_parts): `planes` planes of n
+// coefficients at plane_stride -> send[d][plane][k'] = c[plane][d kg + k'], kg = 2^log_kg
+void diag_pack_coset(hipStream_t st, const fe *c, size_t plane_stride, int log_n, int planes, int log_kg, fe *send);
 
 // the single-GPU prove path (prover.hip) for a sharded proof over one rank: trace = host column-major trace, or
 // NULL when it already sits in p->d_trace

@@ -1678,6 +1678,240 @@ static int validate_sharded(Ctx &X, const uint8_t *trace, const zk_pub_inputs *p
     return validation_from_partials(all.data(), X.G, n, pub, X.P.data(), nl, nullptr);
 }
 
+// validate_transition_degrees of a sharded proof (include/zkvm_gpu.h "transition constraint degrees": nothing in the
+// definitions changes), the work split by CE coset and then by coefficient range.  Every rank holds the whole trace in
+// its trace buffer (a host trace: the 28 columns copied whole, as zk_degrees_columns does), interpolates all 28 columns
+// and extends them over its own Bl = 8 / G CE cosets; it forms the 20 quotients there, inverse-transforms them per
+// coset and sends each rank its kg = n / G coefficients of every one (all-to-all "degrees_slices"); k_cross_degrees
+// then forms coefficients k1 + n k2 of the rank's k1 range and keeps each quotient's highest non-zero global index.
+// The partials travel over the control channel ("degrees_report") and every rank runs merge_degrees.  No allocation:
+// the check runs in a rank-sized prover's buffers (polys; lde and tmp of 28 Bl n each), which no stage of the proof
+// has written yet --
+//   p->polys  the 28 trace polynomials (dense interpolation of the trace buffer, scale 1/n);
+//   p->lde    first the trace LDE over the Bl local cosets (28 x Bl x n), then, once the quotients are written, the
+//             20 Bl per-coset inverse transforms (plane k Bl + j), and last, once those are packed, the receive area
+//             [source s][plane k Bl + j][kl] of 20 x 8 x kg coefficients: coset s Bl + j of quotient k;
+//   p->tmp    the four-step scratch of the front; then the 20 x Bl n quotient values with the 8 Bl n behind them first
+//             as the divisor table (3 Bl n, unless the plan's sh_divs already holds this rank's cosets) and then as the
+//             scratch of the inverse transforms (groups of 8 constraints); then the send area [destination d][plane][kl];
+//             and last, the exchange over, the 20 x 8 x kg coefficients when the caller asked for them.
+// A rank's own error goes into its partial's status and it still issues every collective, so no peer is stranded.
+struct DegreesSharded {
+    Ctx &X;
+    const uint8_t *const trace;  // the caller's host trace, or null: the trace is in every rank's trace buffer
+    const zk_pub_inputs *const pub;
+    uint8_t *const *const quotients_out;  // per local rank (null entries skipped), or null
+    const int G = X.G, Bl = X.Bl, nl = (int)X.P.size(), log_n = X.log_n;
+    const size_t n = X.n, kg = n / (size_t)G, CEl = (size_t)Bl * n, slice = (size_t)NUM_TCONS * 8 * kg;
+    std::vector<DegPartial> mine = std::vector<DegPartial>(nl), all = std::vector<DegPartial>(G);
+    std::vector<DegReport> rep = std::vector<DegReport>(nl);
+
+    bool wants(int l) const { return quotients_out && quotients_out[l]; }
+    void fail(int l, int rc) {  // (the first error of a rank is the one it reports)
+        if (mine[l].status != ZK_OK) return;
+        mine[l].status = rc;
+        snprintf(mine[l].msg, sizeof mine[l].msg, "%s", g_err.c_str());
+    }
+    // steps 1 to 3 and the packing on local rank l
+    int front(int l) {
+        zk_prover *p = X.P[l];
+        Plan *pl = X.pl[l];
+        ZK_CHECK_HIP(hipSetDevice(p->device));
+        if (trace) ZK_CHECK_HIP(hipMemcpyAsync(p->d_trace, trace, (size_t)W * n * sizeof(fe), hipMemcpyHostToDevice, p->st));
+        const int r0 = X.rank[l] * Bl;
+        const fe inv_n = h_inv(fe_make(n));
+        ntt(p->st, pl->Tn, p->d_trace, n, p->polys, n, W, true, nullptr, &inv_n, p->tmp);
+        ntt_lde(p->st, pl->Tn, pl->ct, p->polys, n, W, r0, 1, Bl, p->lde, CEl, n, p->tmp);
+        fe *quot = p->tmp, *scratch = p->tmp + NUM_TCONS * CEl, *per_coset = p->lde, *send = p->tmp;
+        // plane 0 of the divisor tables of the local cosets: they depend on n and the cosets only
+        const fe *divs = pl->sh_divs;
+        if (!divs || pl->sh_divs_r0 != r0 || pl->sh_divs_cos != Bl) {
+            const fe g = h_root_of_unity(log_n);
+            const Fe8 zall = ce_inv_zn(log_n);
+            Fe8 zloc{};
+            for (int j = 0; j < Bl; j++) zloc.v[j] = zall.v[r0 + j];
+            divisor_tables(p->st, pl->Tn, pl->xr_ce + r0, ilog2(Bl), log_n, h_pow(g, n - 1), h_pow(g, n - 2), zloc, scratch);
+            divs = scratch;
+        }
+        const EvalMap em{Bl, r0, 1, 0, Bl};
+        ZK_CHECK_HIP(transition_quotients(p->st, p->lde, log_n, em, pl->periodic, divs, fe_make(pub->delta),
+                                          (int)pub->lwe_size, quot));
+        for (int k0 = 0; k0 < NUM_TCONS; k0 += 8) {
+            const int cnt = std::min(8, NUM_TCONS - k0);
+            ntt(p->st, pl->Tn, quot + k0 * CEl, n, per_coset + k0 * CEl, n, Bl * cnt, true, nullptr, nullptr, scratch);
+        }
+        const int planes = NUM_TCONS * Bl;
+        hipLaunchKernelGGL(k_sh_pack_coset, dim3(cdiv((size_t)planes * n, 256)), dim3(256), 0, p->st,
+                           (const fe *)per_coset, n, log_n, planes, ilog2(kg), send);
+        ZK_CHECK_HIP(hipGetLastError());
+        return ZK_OK;
+    }
+    // steps 5 and 6's first half on local rank l: the fused kernel over the received slices, the report read back
+    int scan_launch(int l) {
+        zk_prover *p = X.P[l];
+        Plan *pl = X.pl[l];
+        ZK_CHECK_HIP(hipSetDevice(p->device));
+        DegCrossMap m;
+        m.c = p->lde;
+        for (int r = 0; r < 8; r++) m.off[r] = ((size_t)(r / Bl) * NUM_TCONS * Bl + (size_t)(r % Bl)) * kg;
+        m.cstride = (size_t)Bl * kg;
+        m.k0 = (size_t)X.rank[l] * kg;
+        m.kcount = kg;
+        m.log_n = log_n;
+        m.first = 0;
+        m.count = NUM_TCONS;
+        m.coeffs = wants(l) ? p->tmp : nullptr;
+        ZK_CHECK_HIP(hipMemsetAsync(p->deg_rep, 0, sizeof(DegReport), p->st));
+        cross_degrees(p->st, m, pl->Tce, pl->inv3, h_inv(fe_make(8 * n)), h_inv(h_root_of_unity(3)),
+                      h_inv(h_pow(fe_make(3), n)), p->deg_rep);
+        ZK_CHECK_HIP(hipGetLastError());
+        ZK_TRY(d2h_small(p, &rep[l], p->deg_rep, sizeof(DegReport)));
+        if (wants(l))
+            ZK_CHECK_HIP(hipMemcpyAsync(quotients_out[l], p->tmp, slice * sizeof(fe), hipMemcpyDeviceToHost, p->st));
+        return ZK_OK;
+    }
+    int scan_read(int l) {
+        zk_prover *p = X.P[l];
+        ZK_CHECK_HIP(hipSetDevice(p->device));
+        ZK_TRY(d2h_flush(p));  // (a stream sync: the caller's trace and quotients_out are free again)
+        collect_kernel_stats(p);
+        mine[l].nonzero = rep[l].nonzero;
+        for (int k = 0; k < NUM_TCONS; k++) mine[l].top[k] = rep[l].top[k];
+        return ZK_OK;
+    }
+    // in the measurement mode a collective's copies run on local rank 0's stream, which the ranks do not share yet
+    // (prove_sharded_entry swaps the streams after the checks): the ranks' streams are drained around it instead
+    void drain() {
+        for (zk_prover *p : X.P) {
+            (void)hipSetDevice(p->device);
+            (void)hipStreamSynchronize(p->st);
+        }
+    }
+    int run(zk_degrees *out) {
+        std::vector<std::unique_ptr<IoScope>> io_scopes;
+        for (int l = 0; l < nl; l++) {
+            ZK_CHECK_HIP(hipSetDevice(X.P[l]->device));
+            io_scopes.push_back(std::make_unique<IoScope>(X.P[l]));
+            memset(&mine[l], 0, sizeof mine[l]);
+            mine[l].version = ZK_AGREE_VERSION;
+            mine[l].rank = (uint32_t)X.rank[l];
+            mine[l].first = (uint64_t)X.rank[l] * kg;
+            mine[l].count = kg;
+        }
+        Bufs b(X);
+        for (int l = 0; l < nl; l++) {
+            const int rc = front(l);
+            if (rc != ZK_OK) fail(l, rc);
+            b.set(l, X.P[l]->tmp, X.P[l]->lde);
+        }
+        if (X.comm->measure) drain();
+        const int xrc = xchg(X, "degrees_slices", A2A, b, (size_t)NUM_TCONS * Bl * kg * sizeof(fe));
+        if (X.comm->measure) drain();
+        if (xrc != ZK_OK) {  // (a transport error: the peers meet it too)
+            drain();
+            return xrc;
+        }
+        for (int l = 0; l < nl; l++) {
+            const int rc = mine[l].status == ZK_OK ? scan_launch(l) : ZK_OK;
+            if (rc != ZK_OK) fail(l, rc);
+        }
+        for (int l = 0; l < nl; l++) {
+            const int rc = scan_read(l);
+            if (rc != ZK_OK) fail(l, rc);
+        }
+        drain();  // on every way: the caller's trace and quotients_out are free again, the buffers the proof's again
+        ZK_TRY(control_exchange(X.comm, X.P[0], "degrees_report", mine.data(), all.data(), sizeof(DegPartial)));
+        for (int r = 0; r < G; r++)
+            if (all[r].status != ZK_OK && rank_is_local(X.comm, r)) {  // this rank's own error, as it met it
+                char m[ZK_AGREE_MSG + 1];
+                memcpy(m, all[r].msg, ZK_AGREE_MSG);
+                m[ZK_AGREE_MSG] = 0;
+                ZK_FAIL(all[r].status, std::string(m));
+            } else if (all[r].status != ZK_OK) {
+                break;  // (degrees_from_partials names the lowest such rank)
+            }
+        return degrees_from_partials(all.data(), G, n, X.P.data(), nl, out);
+    }
+};
+static int degrees_sharded(Ctx &X, const uint8_t *trace, const zk_pub_inputs *pub, zk_degrees *out,
+                           uint8_t *const *quotients_out) {
+    DegreesSharded D{X, trace, pub, quotients_out};
+    return D.run(out);
+}
+
+// The front of every sharded entry point (world > 1): this rank's own checks into a status -- a rank that returned
+// here would strand the peers whose arguments passed in their first collective -- then the control exchange, from which
+// every rank learns the same outcome.  opt: the proof's options, or null for the stand-alone degree check (the record's
+// options are all zero, and the context is checked under the smallest options a sharded proof accepts: n / world >= 8
+// and n >= 16 world).  On a non-OK outcome nothing else has run.
+static int agree_first(Ctx &X, Agreed *out, zk_comm *comm, zk_prover **provers, int nlocal, const uint8_t *trace, size_t n,
+                       const zk_options *opt, bool proof, const zk_pub_inputs *pub, const FixedCols *fixed) {
+    const int G = comm->world;
+    int status = ZK_OK;
+    zk_options shortest;
+    memset(&shortest, 0, sizeof shortest);
+    shortest.num_queries = 1, shortest.blowup = 8, shortest.field_extension = 1, shortest.fri_folding = 2;
+    if ((proof && !opt) || !pub) {
+        g_err = "null argument";
+        status = ZK_ERR_INVALID_ARG;
+    } else if (fixed && trace) {
+        g_err = "preprocessed columns go with a device trace";
+        status = ZK_ERR_INVALID_ARG;
+    } else {
+        status = shard_context(X, comm, provers, nlocal, n, proof ? opt : &shortest, pub);
+    }
+    const std::string status_msg = status != ZK_OK ? g_err : std::string();
+    std::vector<AgreeRecord> mine(nlocal), all(G);
+    for (int l = 0; l < nlocal; l++) {
+        AgreeRecord &r = mine[l];
+        memset(&r, 0, sizeof r);
+        r.version = ZK_AGREE_VERSION;
+        r.world = (uint32_t)G;
+        r.rank = (uint32_t)shard_rank_of(comm, l);
+        r.status = status;
+        snprintf(r.msg, sizeof r.msg, "%s", status_msg.c_str());
+        r.n = n;
+        if (proof && opt) {
+            const uint32_t o[6] = {opt->num_queries,     opt->blowup,      opt->grinding,
+                                   opt->field_extension, opt->fri_folding, opt->fri_rem_max_deg};
+            memcpy(r.opt, o, sizeof o);
+        }
+        if (pub) b3::hash_bytes(reinterpret_cast<const uint8_t *>(pub), sizeof *pub, r.pub_hash);
+        r.source = fixed ? ZK_SRC_FIXED : trace ? ZK_SRC_HOST : ZK_SRC_DEVICE;
+        r.split_rep = comm->split_rep;
+        r.measure = comm->measure ? 1u : 0u;
+        r.validate = provers[l]->validate ? 1u : 0u;
+        r.validate_degrees = provers[l]->validate_degrees ? 1u : 0u;
+        if (status != ZK_OK) continue;
+        const Plan *pl = X.pl[l];
+        r.detect = (sparse_on() && pl->lagr && pl->lagr_lde ? 1u : 0u) | (clock_on() ? 2u : 0u);
+        if (trace && proof) {
+            const HintSet h = local_hints(provers[l], pl, n, G, pub);
+            r.hint_fresh = h.fresh, r.hint_S = h.S, r.hint_clk = h.clk, r.hint_N8 = h.N8, r.hint_N32 = h.N32;
+        }
+    }
+    zk_prover *const p0 = provers[0];
+    stage_begin(p0);  // the record of this call's exchanges starts with the control exchange
+    comm->last = zk_agreement{};
+    comm->have_last = false;
+    ZK_TRY(control_exchange(comm, p0, "control", mine.data(), all.data(), sizeof(AgreeRecord)));
+    const Agreed A = agree(all.data(), G);
+    {
+        const uint64_t calls = comm->last.control_calls, bytes = comm->last.control_bytes;
+        comm->last = A.a;
+        comm->last.control_calls = calls;
+        comm->last.control_bytes = bytes;
+        comm->have_last = true;
+    }
+    *out = A;
+    if (A.a.code != ZK_OK) {
+        p0->stage_done = true;  // (zk_prover_exchange_stats: the control exchange is all that ran)
+        if (A.a.code == ZK_ERR_PEER && rank_is_local(comm, A.a.rank_a)) ZK_FAIL(status, status_msg);
+        ZK_FAIL(A.a.code, A.msg);
+    }
+    return ZK_OK;
+}
+
 int zk::prove_sharded_entry(zk_comm *comm, zk_prover **provers, int nlocal, const uint8_t *trace, size_t n,
                             const zk_options *opt, const zk_pub_inputs *pub, uint8_t *proof_out, size_t *proof_len,
                             zk_record *rec, const FixedCols *fixed) {
@@ -1697,66 +1931,9 @@ int zk::prove_sharded_entry(zk_comm *comm, zk_prover **provers, int nlocal, cons
         return fixed ? prove_fixed(X.P[0], n, opt, pub, fixed, proof_out, proof_len)
                      : prove_single(X.P[0], trace, n, opt, pub, proof_out, proof_len, rec);
     }
-    // This rank's own checks, into a status: a rank that returned here would strand the peers whose arguments passed
-    // in their first collective.  Every rank goes on to the control exchange and learns the same outcome from it.
-    const int G = comm->world;
-    int status = ZK_OK;
-    if (!opt || !pub) {
-        g_err = "null argument";
-        status = ZK_ERR_INVALID_ARG;
-    } else if (fixed && trace) {
-        g_err = "preprocessed columns go with a device trace";
-        status = ZK_ERR_INVALID_ARG;
-    } else {
-        status = shard_context(X, comm, provers, nlocal, n, opt, pub);
-    }
-    const std::string status_msg = status != ZK_OK ? g_err : std::string();
-    std::vector<AgreeRecord> mine(nlocal), all(G);
-    for (int l = 0; l < nlocal; l++) {
-        AgreeRecord &r = mine[l];
-        memset(&r, 0, sizeof r);
-        r.version = ZK_AGREE_VERSION;
-        r.world = (uint32_t)G;
-        r.rank = (uint32_t)shard_rank_of(comm, l);
-        r.status = status;
-        snprintf(r.msg, sizeof r.msg, "%s", status_msg.c_str());
-        r.n = n;
-        if (opt) {
-            const uint32_t o[6] = {opt->num_queries,     opt->blowup,      opt->grinding,
-                                   opt->field_extension, opt->fri_folding, opt->fri_rem_max_deg};
-            memcpy(r.opt, o, sizeof o);
-        }
-        if (pub) b3::hash_bytes(reinterpret_cast<const uint8_t *>(pub), sizeof *pub, r.pub_hash);
-        r.source = fixed ? ZK_SRC_FIXED : trace ? ZK_SRC_HOST : ZK_SRC_DEVICE;
-        r.split_rep = comm->split_rep;
-        r.measure = comm->measure ? 1u : 0u;
-        r.validate = provers[l]->validate ? 1u : 0u;
-        if (status != ZK_OK) continue;
-        const Plan *pl = X.pl[l];
-        r.detect = (sparse_on() && pl->lagr && pl->lagr_lde ? 1u : 0u) | (clock_on() ? 2u : 0u);
-        if (trace) {
-            const HintSet h = local_hints(provers[l], pl, n, G, pub);
-            r.hint_fresh = h.fresh, r.hint_S = h.S, r.hint_clk = h.clk, r.hint_N8 = h.N8, r.hint_N32 = h.N32;
-        }
-    }
+    Agreed A;
+    ZK_TRY(agree_first(X, &A, comm, provers, nlocal, trace, n, opt, true, pub, fixed));
     zk_prover *const p0 = provers[0];
-    stage_begin(p0);  // the record of this call's exchanges starts with the control exchange
-    comm->last = zk_agreement{};
-    comm->have_last = false;
-    ZK_TRY(control_exchange(comm, p0, "control", mine.data(), all.data(), sizeof(AgreeRecord)));
-    const Agreed A = agree(all.data(), G);
-    {
-        const uint64_t calls = comm->last.control_calls, bytes = comm->last.control_bytes;
-        comm->last = A.a;
-        comm->last.control_calls = calls;
-        comm->last.control_bytes = bytes;
-        comm->have_last = true;
-    }
-    if (A.a.code != ZK_OK) {
-        p0->stage_done = true;  // (zk_prover_exchange_stats: the control exchange is all that ran)
-        if (A.a.code == ZK_ERR_PEER && rank_is_local(comm, A.a.rank_a)) ZK_FAIL(status, status_msg);
-        ZK_FAIL(A.a.code, A.msg);
-    }
     X.detect = A.a.detect != 0;
     X.clock = A.a.clock != 0;
     X.hints = A.hints;
@@ -1773,6 +1950,20 @@ int zk::prove_sharded_entry(zk_comm *comm, zk_prover **provers, int nlocal, cons
             rc = ZK_ERR_INVALID_ARG;
         } else {
             rc = validate_sharded(X, trace, pub);
+        }
+        if (rc != ZK_OK) {
+            *proof_len = 0;
+            p0->stage_done = true;
+            return rc;
+        }
+    }
+    if (A.a.validate_degrees) {  // the order of a debug build: Trace::validate, then the evaluator's degree check
+        int rc = ZK_OK;
+        if (fixed) {
+            g_err = "the sharded degree check needs every trace column in HBM, not the preprocessed ones";
+            rc = ZK_ERR_INVALID_ARG;
+        } else {
+            rc = degrees_sharded(X, trace, pub, nullptr, nullptr);
         }
         if (rc != ZK_OK) {
             *proof_len = 0;
@@ -1820,9 +2011,50 @@ int zk::prove_sharded_entry(zk_comm *comm, zk_prover **provers, int nlocal, cons
     forget_hints(X);
     for (zk_prover *p : X.P) p->hint_redos++;
     {  // the redone proof's record starts over, the control exchanges kept at its head
-        const std::vector<zk_prover::XchgRec> ctl(p0->xchg.begin(), p0->xchg.begin() + (long)comm->last.control_calls);
+        // (host-timed records only: a degree check's "degrees_slices" sits among them, and its events start over too)
+        std::vector<zk_prover::XchgRec> ctl;
+        for (const auto &r : p0->xchg)
+            if (r.host_ms >= 0.f && ctl.size() < comm->last.control_calls) ctl.push_back(r);
         stage_begin(p0);
         p0->xchg = ctl;
     }
     return prove_sharded(X, trace, opt, pub, proof_out, proof_len, rec);
+}
+
+int zk_degrees_sharded(zk_comm *comm, zk_prover **provers, int nlocal, const uint8_t *trace, size_t n,
+                       const zk_pub_inputs *pub, zk_degrees *out, uint8_t *const *quotients_out) {
+    if (!comm || !provers || nlocal <= 0) ZK_FAIL(ZK_ERR_INVALID_ARG, "null argument");
+    if (comm->loopback() ? nlocal != comm->world : nlocal != 1)
+        ZK_FAIL(ZK_ERR_INVALID_ARG,
+                "a loopback communicator needs one prover per rank, an RCCL or host-exchange one exactly one");
+    for (int l = 0; l < nlocal; l++)
+        if (!provers[l]) ZK_FAIL(ZK_ERR_INVALID_ARG, "null prover");
+    if (comm->world == 1) {  // one rank: the single-GPU check (its quotients_out is the one slice, k1 = 0 .. n - 1)
+        zk_degrees d;
+        uint8_t *q = quotients_out ? quotients_out[0] : nullptr;
+        if (!trace) {
+            void *dt = nullptr;
+            ZK_TRY(zk_prover_trace_buffer(provers[0], &dt));
+            const int rc = zk_degrees_device(provers[0], dt, n, pub, &d, q);
+            if (out && (rc == ZK_OK || rc == ZK_ERR_DEGREES)) *out = d;
+            return rc;
+        }
+        const uint8_t *cols[W];
+        for (int c = 0; c < W; c++) cols[c] = trace + (size_t)c * n * sizeof(fe);
+        const int rc = zk_degrees_columns(provers[0], cols, n, pub, &d, q);
+        if (out && (rc == ZK_OK || rc == ZK_ERR_DEGREES)) *out = d;
+        return rc;
+    }
+    Ctx X;
+    Agreed A;
+    ZK_TRY(agree_first(X, &A, comm, provers, nlocal, trace, n, nullptr, false, pub, nullptr));
+    const int rc = degrees_sharded(X, trace, pub, out, quotients_out);
+    provers[0]->stage_done = true;
+    return rc;
+}
+
+// (diag.hip zk_diag_degrees_parts: the production pack kernel on planes of the caller's choice)
+void zk::diag_pack_coset(hipStream_t st, const fe *c, size_t plane_stride, int log_n, int planes, int log_kg, fe *send) {
+    hipLaunchKernelGGL(k_sh_pack_coset, dim3(cdiv((size_t)planes << log_n, 256)), dim3(256), 0, st, c, plane_stride, log_n,
+                       planes, log_kg, send);
 }

@@ -13,6 +13,7 @@
 #include <string>
 
 #include "../../include/zkvm_gpu.h"
+#include "air_shape.hpp"
 
 namespace zk {
 
@@ -21,7 +22,8 @@ constexpr int ZK_AGREE_MSG = 120;
 
 // One rank's record, 256 bytes, little-endian, in this (layout) order.  Must match on every rank: world, n, every
 // member of zk_options, the BLAKE3 of zk_pub_inputs, the trace source, and the communicator's two settings (both
-// change the number of collectives).  Decided from all records: detect, clock, the hint set, validate.
+// change the number of collectives).  Decided from all records: detect, clock, the hint set, validate,
+// validate_degrees (the first 4 of the once 16 reserved bytes: a record of an older build reads as "off").
 enum { ZK_SRC_HOST = 0, ZK_SRC_DEVICE = 1, ZK_SRC_FIXED = 2 };
 struct AgreeRecord {
     uint32_t version, world, rank;
@@ -37,7 +39,8 @@ struct AgreeRecord {
     // the hint set this rank would use for a host trace (shard.hip classify_host), all zero when not fresh
     uint32_t hint_fresh, hint_S, hint_clk, hint_N8, hint_N32;
     char msg[ZK_AGREE_MSG];  // the first bytes of the status' message, NUL-padded
-    uint8_t reserved[16];
+    uint32_t validate_degrees;  // zk_prover_set_validate_degrees of this rank's prover(s)
+    uint8_t reserved[12];
 };
 static_assert(sizeof(AgreeRecord) == 256, "the control record is a fixed 256-byte layout");
 
@@ -76,7 +79,8 @@ inline int first_other(int world, Same same) {
 // The rule.  1: a record of another layout version is refused.  2: a rank with a non-OK status -- the lowest is named,
 // code ZK_ERR_PEER (that rank itself returns its own code and text: shard.hip).  3: a must-match field differs -- the
 // first in layout order is named with the two lowest ranks that hold different values, code ZK_ERR_INVALID_ARG.
-// 4: the decisions: detect and clock = AND, validate = OR, hints = rank 0's set if every rank's set is equal.
+// 4: the decisions: detect and clock = AND, validate and validate_degrees = OR, hints = rank 0's set if every rank's
+// set is equal.
 inline Agreed agree(const AgreeRecord *R, int world) {
     using namespace agree_detail;
     Agreed A;
@@ -136,18 +140,20 @@ inline Agreed agree(const AgreeRecord *R, int world) {
         return disagree("comm.trace_split", o, std::to_string(R[0].split_rep), std::to_string(R[o].split_rep)), A;
     if ((o = first_other(world, [&](int r) { return R[r].measure == R[0].measure; })) >= 0)
         return disagree("comm.measure", o, u(R[0].measure), u(R[o].measure)), A;
-    uint32_t det = 3u, val = 0;
+    uint32_t det = 3u, val = 0, vdeg = 0;
     bool same = true;
     const HintSet h0{R[0].hint_fresh, R[0].hint_S, R[0].hint_clk, R[0].hint_N8, R[0].hint_N32};
     for (int r = 0; r < world; r++) {
         det &= R[r].detect;
         val |= R[r].validate;
+        vdeg |= R[r].validate_degrees;
         same = same && HintSet{R[r].hint_fresh, R[r].hint_S, R[r].hint_clk, R[r].hint_N8, R[r].hint_N32} == h0;
     }
     a.code = ZK_OK;
     a.detect = (int32_t)(det & 1u);
     a.clock = (int32_t)((det >> 1) & 1u);
     a.validate = val ? 1 : 0;
+    a.validate_degrees = vdeg ? 1 : 0;
     a.hints_equal = same ? 1 : 0;
     a.hints = same && h0.fresh ? 1 : 0;
     if (a.hints) A.hints = h0;
@@ -221,6 +227,79 @@ inline int merge_validation(const ValPartial *P, int world, zk_validation *V, in
             if ((P[r].amask >> k) & 1u) memcpy(V->a_found[k], P[r].a_found[k], 16);
     }
     V->a_failed = (uint32_t)__builtin_popcount(V->a_mask);
+    return ZK_OK;
+}
+
+// ---------------------------------------------------------------- sharded degree check: one rank's coefficient range
+// Rank g of G receives, of every quotient Q_k, the 8 per-coset coefficient slices k1 in [g n / G, (g + 1) n / G) and
+// forms the coefficients k1 + n k2, k2 < 8, from them (kernels.hip k_cross_degrees).  One rank's partial report, 312
+// bytes, little-endian: top[k] is the highest GLOBAL index k1 + n k2 it found non-zero in Q_k (0 if none: bit k of
+// nonzero tells the two apart, as DegReport does).
+struct DegPartial {
+    uint32_t version, rank;
+    int32_t status;    // ZK_OK, or the code of an error on this rank, its text in msg
+    uint32_t nonzero;  // bit k: Q_k has a non-zero coefficient in this rank's range
+    uint64_t first, count;  // the k1 range
+    uint64_t top[20];
+    char msg[ZK_AGREE_MSG];
+};
+static_assert(sizeof(DegPartial) == 312, "the degree partial is a fixed layout");
+
+// Rust's {:>3?} of a Vec<usize>: every element right-aligned in 3 columns
+inline std::string rust_vec3(const uint64_t *v, int k) {
+    std::string s = "[";
+    for (int i = 0; i < k; i++) {
+        std::string e = std::to_string(v[i]);
+        if (e.size() < 3) e.insert(0, 3 - e.size(), ' ');
+        s += (i ? ", " : "") + e;
+    }
+    return s + "]";
+}
+// The report of a degree check from the 20 tops and the non-zero bits (zk_degrees_device on one GPU, merge_degrees
+// over the ranks): expected from the AIR's declared degrees, the masks, max_actual and ce_len_needed.
+inline void degrees_report(size_t n, const uint64_t *top, uint32_t nonzero, zk_degrees *D) {
+    memset(D, 0, sizeof *D);
+    D->trace_len = n;
+    D->ce_len = 8 * (uint64_t)n;
+    const DeclaredDegrees &decl = air_declared_degrees();
+    for (int k = 0; k < 20; k++) {
+        D->expected[k] = decl.evaluation_degree(k, n) - (n - 2);
+        D->actual[k] = top[k];
+        if (!((nonzero >> k) & 1u)) D->zero_mask |= 1u << k;
+        if (D->actual[k] != D->expected[k]) D->mismatch_mask |= 1u << k;
+        if (D->actual[k] > D->expected[k]) D->over_mask |= 1u << k;
+        D->max_actual = std::max(D->max_actual, D->actual[k]);
+    }
+    D->ce_len_needed = 1;
+    while (D->ce_len_needed < std::max<uint64_t>(D->max_actual, n + 1)) D->ce_len_needed *= 2;
+}
+// winterfell's three-line message of a mismatch
+inline std::string degrees_message(const zk_degrees &D) {
+    return "transition constraint degrees didn't match\nexpected: " + rust_vec3(D.expected, 20) +
+           "\nactual:   " + rust_vec3(D.actual, 20);
+}
+
+// The merge: top = the maximum over the ranks of the global index (a rank with a lower k1 range wins with a higher
+// block k2), nonzero = OR; the rest of the report as degrees_report fills it.  ZK_OK, or ZK_ERR_PEER with the lowest
+// rank whose partial carries an error, another layout version or a coefficient outside the domain in *bad.
+inline int merge_degrees(const DegPartial *P, int world, size_t n, zk_degrees *D, int *bad) {
+    *bad = -1;
+    for (int r = 0; r < world; r++) {
+        bool ok = P[r].status == ZK_OK && P[r].version == ZK_AGREE_VERSION;
+        for (int k = 0; ok && k < 20; k++) ok = P[r].top[k] < 8 * (uint64_t)n;
+        if (!ok) {
+            *bad = r;
+            return ZK_ERR_PEER;
+        }
+    }
+    uint64_t top[20] = {};
+    uint32_t nonzero = 0;
+    for (int r = 0; r < world; r++) {
+        nonzero |= P[r].nonzero & 0xfffffu;
+        for (int k = 0; k < 20; k++)
+            if ((P[r].nonzero >> k) & 1u) top[k] = std::max(top[k], P[r].top[k]);
+    }
+    degrees_report(n, top, nonzero, D);
     return ZK_OK;
 }
 

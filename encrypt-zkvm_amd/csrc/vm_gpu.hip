@@ -602,9 +602,11 @@ int zk_vm_prove_sharded(zk_comm *comm, zk_prover **provers, int nlocal, zk_progr
     const int G = comm->world;
     // ZK_VM_PREPROCESS=0: every column from the device trace, as zk_vm_prove
     // zk_prover_set_validate on a local prover: Trace::validate needs every column of the written trace in HBM, so the
-    // call takes the all-columns path, as zk_vm_prove (the trace source is one of the fields the ranks must agree on)
+    // call takes the all-columns path, as zk_vm_prove (the trace source is one of the fields the ranks must agree on);
+    // zk_prover_set_validate_degrees likewise: the sharded degree check interpolates all 28 written columns
     bool validates = false;
-    for (int l = 0; l < nlocal; l++) validates = validates || (G > 1 && provers[l]->validate);
+    for (int l = 0; l < nlocal; l++)
+        validates = validates || (G > 1 && (provers[l]->validate || provers[l]->validate_degrees));
     const bool pre = env_switch("ZK_VM_PREPROCESS") && opt->blowup == 8 && (G == 1 || G == 2 || G == 4 || G == 8) &&
                      !validates;
     std::vector<FixedCols> fx(pre ? nlocal : 0);

@@ -421,6 +421,22 @@ void boundary_range_end(hipStream_t st, int log_n, fe c, fe *scratch, size_t k0,
 // and write column k2 < ncols of the segmented composition polynomial, for the k1 range of the CrossMap.
 void comp_cross_mapped(hipStream_t st, const CrossMap &m, const NttTables &T8n, const PowTable &inv3, fe scale,
                        fe w8inv, fe inv3n, int ncols, fe *polys, unsigned *nonzero_flag);
+// The cross-coset step of a batch of `count` (<= 20) polynomials over the coefficient range k0 .. k0 + kcount, fused
+// with the degree scan (a sharded degree check: shard.hip DegreesSharded).  Inputs: c_r[k0 + kl] of polynomial k at
+// c[off[r] + k cstride + kl].  rep (zeroed in-stream): top[first + k] takes the highest GLOBAL index k1 + n k2 whose
+// coefficient is non-zero, bit first + k of nonzero that there is one.  coeffs = null: no coefficient is written (nor
+// scaled: the scale is non-zero).  Else coefficient k1 + n k2 of polynomial k goes to coeffs[((first + k) 8 + k2)
+// kcount + kl], bit-identical to comp_cross_mapped's.  max_blocks: the grid's x extent (0: the default), past which
+// a block strides.
+struct DegCrossMap {
+    const fe *c;
+    size_t off[8], cstride;
+    size_t k0, kcount;
+    int log_n, first, count;
+    fe *coeffs;
+};
+void cross_degrees(hipStream_t st, const DegCrossMap &m, const NttTables &T8n, const PowTable &inv3, fe scale, fe w8inv,
+                   fe inv3n, DegReport *rep, unsigned max_blocks = 0);
 
 // ---------------------------------------------------------------- OOD / DEEP / FRI
 // Written once over the challenge field (chal.hpp): KX = 1 the base field, KX = 2 FieldExtension::Quadratic.  A

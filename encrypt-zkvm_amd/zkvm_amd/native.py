@@ -46,6 +46,7 @@ EXPORTED = (
     "zk_lde_new_columns", "zk_eval_constraints_ext", "zk_commit_composition_ext",
     "zk_lde_read_rows", "zk_comp_read_rows",
     "zk_comm_agreement",
+    "zk_degrees_sharded",
 )
 
 
@@ -114,16 +115,17 @@ class Agreement(C.Structure):
         ("detect", C.c_int32), ("clock", C.c_int32), ("hints", C.c_int32), ("hints_equal", C.c_int32),
         ("validate", C.c_int32), ("world", C.c_uint32), ("_pad", C.c_uint32),
         ("control_calls", C.c_uint64), ("control_bytes", C.c_uint64), ("field", C.c_char * 32),
+        ("validate_degrees", C.c_int32), ("_pad2", C.c_int32),
     ]
 
     def to_dict(self) -> dict:
-        d = {f: getattr(self, f) for f, _ in self._fields_ if f != "_pad"}
+        d = {f: getattr(self, f) for f, _ in self._fields_ if not f.startswith("_pad")}
         d["field"] = self.field.decode()
         return d
 
 
-# The control record and the validation partial of csrc/shard_agree.hpp (AgreeRecord: 256 bytes, ValPartial: 1160), for
-# the test entry points bound in zkvm_amd/shard_diag.py
+# The control record and the partial reports of csrc/shard_agree.hpp (AgreeRecord: 256 bytes, ValPartial: 1160,
+# DegPartial: 312), for the test entry points bound in zkvm_amd/shard_diag.py
 AGREE_VERSION, AGREE_MSG = 1, 120
 SRC_HOST, SRC_DEVICE, SRC_FIXED = 0, 1, 2
 ASSERT_ROW0, ASSERT_LAST = 0x155557, 0x2AAAA8
@@ -137,7 +139,7 @@ class AgreeRecord(C.Structure):
         ("detect", C.c_uint32),
         ("hint_fresh", C.c_uint32), ("hint_S", C.c_uint32), ("hint_clk", C.c_uint32), ("hint_N8", C.c_uint32),
         ("hint_N32", C.c_uint32),
-        ("msg", C.c_char * AGREE_MSG), ("reserved", C.c_uint8 * 16),
+        ("msg", C.c_char * AGREE_MSG), ("validate_degrees", C.c_uint32), ("reserved", C.c_uint8 * 12),
     ]
 
 
@@ -151,7 +153,17 @@ class ValPartial(C.Structure):
     ]
 
 
-assert C.sizeof(AgreeRecord) == 256 and C.sizeof(ValPartial) == 1160
+class DegPartial(C.Structure):
+    """One rank's partial report of a sharded degree check: top[k] is the highest GLOBAL coefficient index k1 + n k2 of
+    Q_k that is non-zero in the rank's k1 range [first, first + count), bit k of nonzero that there is one."""
+    _fields_ = [
+        ("version", C.c_uint32), ("rank", C.c_uint32), ("status", C.c_int32), ("nonzero", C.c_uint32),
+        ("first", C.c_uint64), ("count", C.c_uint64), ("top", C.c_uint64 * 20),
+        ("msg", C.c_char * AGREE_MSG),
+    ]
+
+
+assert C.sizeof(AgreeRecord) == 256 and C.sizeof(ValPartial) == 1160 and C.sizeof(DegPartial) == 312
 
 
 class Degrees(C.Structure):
@@ -348,6 +360,10 @@ def lib():
         L.zk_prover_shard_schedule.argtypes = [vp, C.c_char_p, sz, C.POINTER(sz)]
         L.zk_prove_sharded.argtypes = [vp, C.POINTER(vp), i32, vp, sz, C.POINTER(Options), C.POINTER(PubInputs), vp,
                                        C.POINTER(sz), C.POINTER(Record)]
+        if hasattr(L, "zk_degrees_sharded"):  # (an A/B library of an earlier commit, ZKVM_GPU_LIB, has none)
+            # (comm, provers[nlocal], nlocal, trace, n, pub, out, quotients_out[nlocal])
+            L.zk_degrees_sharded.argtypes = [vp, C.POINTER(vp), i32, vp, sz, C.POINTER(PubInputs), C.POINTER(Degrees),
+                                             C.POINTER(vp)]
         L.zk_vm_trace.argtypes = [C.c_char_p, vp, sz, vp, sz, u32, u32, vp, vp, sz, C.POINTER(sz), vp, vp]
         L.zk_vm_last_error.restype = C.c_char_p
         L.zk_program_compile.argtypes = [C.c_char_p, C.POINTER(vp), vp, C.POINTER(sz)]

@@ -134,6 +134,49 @@ class ShardedProver:
         check(lib().zk_prover_validation(self.provers[local], C.byref(v)), "zk_prover_validation")
         return v.to_dict()
 
+    # ---- validate_transition_degrees split over the ranks (zk_degrees_sharded)
+    def set_validate_degrees(self, on: bool):
+        """zk_prover_set_validate_degrees on every local rank's prover: the sharded proof checks the transition
+        constraint degrees first (after the trace validation, if that is on too), split over the ranks, when any rank
+        of the proof has the switch on."""
+        for p in self.provers:
+            check(lib().zk_prover_set_validate_degrees(p, 1 if on else 0), "zk_prover_set_validate_degrees")
+
+    def degrees(self, local: int = 0) -> dict:
+        """zk_prover_degrees of a local rank's prover: the merged report of the last sharded degree check."""
+        d = native.Degrees()
+        check(lib().zk_prover_degrees(self.provers[local], C.byref(d)), "zk_prover_degrees")
+        return d.to_dict()
+
+    def _degrees(self, trace_ptr, n: int, pub, quotients: bool):
+        """(rc, report[, slices]) for ZK_OK and ZK_ERR_DEGREES; anything else raises.  slices: per local rank the
+        20 x 8 x kg coefficients it formed, [k][k2][kl] = coefficient rank kg + kl + n k2 of Q_k, as nested lists."""
+        from .prover import bytes_elems
+        d = native.Degrees()
+        nl, kg = len(self.provers), n // self.world if n >= self.world else 0
+        arr = (C.c_void_p * nl)(*[p.value for p in self.provers])
+        bufs = [np.zeros((20 * 8 * kg, 2), dtype=np.uint64) for _ in range(nl)] if quotients else []
+        qs = (C.c_void_p * nl)(*[b.ctypes.data for b in bufs]) if quotients else None
+        rc = lib().zk_degrees_sharded(self.comm, arr, nl, trace_ptr, n, C.byref(pub), C.byref(d), qs)
+        if rc not in (native.ZK_OK, native.ZK_ERR_DEGREES):
+            check(rc, "zk_degrees_sharded")
+        if not quotients:
+            return rc, d.to_dict()
+        out = []
+        for b in bufs:
+            flat = bytes_elems(b.tobytes())
+            out.append([[flat[(k * 8 + k2) * kg:(k * 8 + k2 + 1) * kg] for k2 in range(8)] for k in range(20)])
+        return rc, d.to_dict(), out
+
+    def degrees_host(self, trace: np.ndarray, pub, quotients: bool = False):
+        """zk_degrees_sharded on a (28, n, 2) uint64 host trace: every rank copies it whole (a debugging aid)."""
+        trace = np.ascontiguousarray(trace, dtype=np.uint64)
+        return self._degrees(trace.ctypes.data, trace.shape[1], pub, quotients)
+
+    def degrees_device(self, n: int, pub, quotients: bool = False):
+        """zk_degrees_sharded on the trace already in every local prover's trace buffer (upload_trace)."""
+        return self._degrees(None, n, pub, quotients)
+
     def stage_times(self) -> dict:
         names = (C.c_char_p * 32)()
         ms = (C.c_float * 32)()

@@ -276,8 +276,10 @@ int zk_degrees_columns(zk_prover *p, const uint8_t *const *columns, size_t n, co
  * prove, after Trace::validate when zk_prover_set_validate is on as well (the order of a debug build: Prover::prove
  * validates the trace, then the evaluator checks the degrees).  A mismatch returns ZK_ERR_DEGREES with *proof_len = 0:
  * no proof is written and no column hint or snapshot is touched.  A pass goes on to the same proof bytes.  Default 0:
- * nothing changes, and zk_prover_set_validate keeps its meaning.  The sharded entry points (zk_prove_sharded,
- * zk_vm_prove_sharded) ignore THIS setting: they validate the trace (zk_prover_set_validate), never the degrees. */
+ * nothing changes, and zk_prover_set_validate keeps its meaning.  The setting applies to rank-sized provers
+ * (zk_prover_create_shard) too: zk_prove_sharded and zk_vm_prove_sharded check the degrees first, split over the ranks
+ * by CE coset and then by coefficient range (zk_degrees_sharded below), when ANY rank's prover has it on, after the
+ * sharded trace validation when that is on as well. */
 int zk_prover_set_validate_degrees(zk_prover *p, int on);
 /* The report of the last degree check that ran on p (by either call above or by a proof with the switch on);
  * ZK_ERR_INVALID_ARG if none has run. */
@@ -440,7 +442,21 @@ int zk_prove_sharded(zk_comm *comm, zk_prover **provers, int nlocal, const uint8
  * device trace, for a host trace from an upload of only its rows -- the partial reports are all-gathered over the
  * control channel and merged, every local prover stores the merged report, read with zk_prover_validation, and a failing
  * trace returns ZK_ERR_TRACE on every rank with *proof_len = 0 and zk_validate_device's message, before any data
- * collective.  zk_prover_exchange_stats lists the control exchanges as "control" and "validate_report". */
+ * collective.  zk_prover_exchange_stats lists the control exchanges as "control" and "validate_report".
+ * Sharded degree check (any rank's zk_prover_set_validate_degrees; after the validation, before the proof's own data
+ * collectives): "transition constraint degrees" above, unchanged, with the work split twice.  Every rank interpolates
+ * the whole trace (a host trace: all 28 columns copied whole into every rank's trace buffer, a debugging aid) and
+ * extends it over its own 8 / world CE cosets only; it forms the 20 quotients there, inverse-transforms them per
+ * coset and sends each rank its n / world coefficients of every coset (one all-to-all, "degrees_slices": 20 x 8 x
+ * n / world elements received per rank); a rank then forms coefficients k1 + n k2, k2 < 8, of its k1 range with the
+ * composition's cross-coset step and keeps only each quotient's highest non-zero index.  The partial reports travel
+ * over the control channel ("degrees_report"), every rank merges them (maximum of the tops, OR of the non-zero bits)
+ * and every local prover stores the merged report (zk_prover_degrees).  A mismatch returns ZK_ERR_DEGREES on every
+ * rank with *proof_len = 0 and zk_degrees_device's message; no hint state moves.  It runs in a rank-sized prover's own
+ * buffers (trace LDE and NTT scratch of 28 x 8 / world x n each) and allocates nothing per call.  Cost: about a
+ * single-GPU check's front (the dense interpolation, repeated on every rank) plus 1 / world of the rest; loopback on
+ * one GPU at 2^20: 21 / 22 / 27 ms at world 2 / 4 / 8 against 15 ms single-GPU (profiles/shard_degrees_time.txt).  The
+ * preprocessed trace source of zk_vm_prove_sharded is taken only when no local prover has either switch on. */
 typedef struct {
     int32_t code;           /* ZK_OK; ZK_ERR_PEER (case 1); ZK_ERR_INVALID_ARG (case 2); the same on every rank */
     int32_t rank_a, rank_b; /* case 1: the rank that refused, -1; case 2: the two ranks named; else -1, -1 */
@@ -451,11 +467,21 @@ typedef struct {
     uint32_t world, _pad;
     uint64_t control_calls, control_bytes; /* control exchanges of the call, and the bytes each rank received in them */
     char field[32];         /* case 2: the field named; case 1: "status" */
+    int32_t validate_degrees, _pad2; /* case 3: the transition constraint degrees are checked first */
 } zk_agreement;
 /* The outcome of the last sharded call on this communicator (ZK_ERR_INVALID_ARG if none has exchanged records). */
 int zk_comm_agreement(const zk_comm *comm, zk_agreement *out);
+/* The sharded degree check on its own: the control exchange of a proof first (refusals and disagreements as there;
+ * the record's options are all zero), then the check described above.  `trace`: the flat column-major host trace of
+ * zk_prove_sharded, or NULL: the trace is already in every prover's trace buffer.  ZK_OK or ZK_ERR_DEGREES, the same
+ * report (`out`, optional) and message on every rank.  quotients_out (optional): nlocal pointers, a NULL entry skips
+ * that rank; local rank l receives its slice of the coefficients, 20 x 8 x kg elements of 16 bytes with kg = n / world:
+ * element [k][k2][kl] is coefficient k1 + n k2 of Q_k, k1 = rank kg + kl.  Lengths as a sharded proof's cross step:
+ * n / world >= 8 and n >= 16 world.  world == 1 forwards to zk_degrees_columns / zk_degrees_device. */
+int zk_degrees_sharded(zk_comm *comm, zk_prover **provers, int nlocal, const uint8_t *trace, size_t n,
+                       const zk_pub_inputs *pub, zk_degrees *out, uint8_t *const *quotients_out);
 /* The collectives of the last sharded proof on this (local rank 0) prover, aggregated by name (control,
- * validate_report, trace_coeffs,
+ * validate_report, degrees_slices, degrees_report, trace_coeffs,
  * trace_digests, trace_roots, comp_slices, comp_columns, degree_flags, comp_digests, comp_roots, ood_parts,
  * deep_totals, deep_slices, fri0_digests, fri0_roots, fri_layer1, openings): ms between HIP events recorded on the
  * stream the collective runs on around each call (waiting for slower ranks included), bytes this rank received from
