@@ -19,6 +19,8 @@ ZK_ERR_BUFFER_TOO_SMALL = -2
 ZK_ERR_DEVICE = -3
 ZK_ERR_OUT_OF_MEMORY = -4
 ZK_ERR_PEER = -5
+ZK_ERR_PENDING = -6
+ZK_ERR_CANCELLED = -7
 ZK_ERR_PROGRAM = -10
 ZK_ERR_STACK = -11
 ZK_ERR_CHIPLETS = -12
@@ -47,6 +49,10 @@ EXPORTED = (
     "zk_lde_read_rows", "zk_comp_read_rows",
     "zk_comm_agreement",
     "zk_degrees_sharded",
+    "zk_queue_create", "zk_queue_destroy", "zk_queue_set_validate", "zk_queue_set_validate_degrees", "zk_queue_pause",
+    "zk_queue_resume", "zk_queue_submit_columns", "zk_queue_submit_device", "zk_queue_submit_vm", "zk_queue_wait",
+    "zk_queue_poll", "zk_queue_wait_any", "zk_queue_cancel", "zk_queue_job_validation", "zk_queue_job_degrees",
+    "zk_queue_stats",
 )
 
 
@@ -75,6 +81,19 @@ class ProofInfo(C.Structure):
     """zk_proof_info (include/zkvm_gpu.h): what the last proof on a prover did."""
     _fields_ = [("schedule", C.c_int32), ("hint_redos", C.c_uint32), ("hint_sets", C.c_uint32),
                 ("hinted_sparse", C.c_uint32), ("derived", C.c_uint32), ("fixed_sets", C.c_uint32)]
+
+
+class JobResult(C.Structure):
+    """zk_job_result (include/zkvm_gpu.h): what a proof queue delivers for one job."""
+    _fields_ = [("status", C.c_int32), ("prover", C.c_int32), ("proof_len", C.c_uint64),
+                ("queued_ms", C.c_float), ("run_ms", C.c_float), ("running_at_start", C.c_uint32), ("_pad", C.c_uint32),
+                ("info", ProofInfo), ("message", C.c_char * 512)]
+
+    def to_dict(self) -> dict:
+        d = {f: getattr(self, f) for f in ("status", "prover", "proof_len", "queued_ms", "run_ms", "running_at_start")}
+        d["info"] = {f: getattr(self.info, f) for f, _ in ProofInfo._fields_}
+        d["message"] = self.message.decode(errors="replace")
+        return d
 
 
 class Validation(C.Structure):
@@ -430,6 +449,32 @@ def lib():
             # (device, leaves, nl, l3_min_log, pf_blocks, block_p, nodes_out, guard_out[2 * 4096], leaves_out, positions,
             #  k, proof_out, proof_len)
             L.zk_diag_merkle.argtypes = [i32, vp, sz, i32, u32, u32, vp, vp, vp, vp, sz, vp, C.POINTER(sz)]
+        if hasattr(L, "zk_queue_create"):  # (an A/B library of an earlier commit, ZKVM_GPU_LIB, has no proof queue)
+            u64 = C.c_uint64
+            L.zk_queue_create.argtypes = [i32, sz, u32, i32, C.POINTER(vp)]
+            L.zk_queue_destroy.argtypes = [vp]
+            L.zk_queue_destroy.restype = None
+            L.zk_queue_set_validate.argtypes = [vp, i32]
+            L.zk_queue_set_validate_degrees.argtypes = [vp, i32]
+            L.zk_queue_pause.argtypes = [vp]
+            L.zk_queue_resume.argtypes = [vp]
+            # (q, columns[28] / d_trace, n, opt, pub, proof_out, proof_cap, job)
+            L.zk_queue_submit_columns.argtypes = [vp, C.POINTER(vp), sz, C.POINTER(Options), C.POINTER(PubInputs), vp, sz,
+                                                  C.POINTER(u64)]
+            L.zk_queue_submit_device.argtypes = [vp, vp, sz, C.POINTER(Options), C.POINTER(PubInputs), vp, sz,
+                                                 C.POINTER(u64)]
+            # (q, prog, public, num_public, secret, num_secret, lwe_size, delta, last_row, opt, proof_out, proof_cap,
+            #  outputs, program_hash, job)
+            L.zk_queue_submit_vm.argtypes = [vp, vp, vp, sz, vp, sz, u32, u32, vp, C.POINTER(Options), vp, sz, vp, vp,
+                                             C.POINTER(u64)]
+            L.zk_queue_wait.argtypes = [vp, u64, C.POINTER(JobResult)]
+            L.zk_queue_poll.argtypes = [vp, u64, C.POINTER(JobResult)]
+            L.zk_queue_wait_any.argtypes = [vp, C.POINTER(u64), C.POINTER(JobResult)]
+            L.zk_queue_cancel.argtypes = [vp, u64]
+            L.zk_queue_job_validation.argtypes = [vp, u64, C.POINTER(Validation)]
+            L.zk_queue_job_degrees.argtypes = [vp, u64, C.POINTER(Degrees)]
+            L.zk_queue_stats.argtypes = [vp, C.POINTER(u64), C.POINTER(u64), C.POINTER(u32), C.POINTER(u32),
+                                         C.POINTER(u32)]
         _lib = L
     return _lib
 

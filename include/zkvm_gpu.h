@@ -33,6 +33,8 @@ extern "C" {
 #define ZK_ERR_DEVICE -3
 #define ZK_ERR_OUT_OF_MEMORY -4
 #define ZK_ERR_PEER -5      /* sharded proof: another rank refused it (that rank and its reason in the message) */
+#define ZK_ERR_PENDING -6   /* zk_queue_poll: the job has not finished */
+#define ZK_ERR_CANCELLED -7 /* proof queue: the job was cancelled before it started */
 #define ZK_ERR_PROGRAM -10  /* ProgramError (vm/src/program/errors.rs) */
 #define ZK_ERR_STACK -11    /* StackError (vm/src/processor/errors.rs:4-42) */
 #define ZK_ERR_CHIPLETS -12 /* ChipletsError (vm/src/processor/errors.rs:44-71) */
@@ -620,6 +622,88 @@ int zk_vm_prove_sharded(zk_comm *comm, zk_prover **provers, int nlocal, zk_progr
                         size_t num_public, const uint8_t *secret, size_t num_secret, uint32_t lwe_size, uint32_t delta,
                         const uint8_t *last_row, const zk_options *opt, uint8_t *proof_out, size_t *proof_len,
                         uint8_t *outputs, uint8_t *program_hash);
+
+/* ---- proof queue: one host thread keeps several proofs in flight (no reference counterpart: vm::prove,
+ * vm/src/lib.rs:13-29, is one thread that proves one program and then takes the next) ----
+ * Every zk_prove* / zk_vm_prove call blocks its caller, and a device gives its best throughput with three provers at
+ * work.  A zk_queue owns `provers` (1 .. 8; 3 is the recommendation: P + 1 = 4 streams fit
+ * HIP's default hardware queues) full provers of one device, taken with zk_prover_acquire and handed back with
+ * zk_prover_release at destroy, and one worker thread bound to each for the queue's lifetime (which keeps the worker's
+ * thread-local tables warm).  A job is one blocking call -- zk_prove_columns, zk_prove_device or zk_vm_prove -- run by a
+ * worker on its prover: the same code path, the same proof bytes.  (The section stands at the end of the header, not
+ * after the prover pool, because zk_job_result holds a zk_proof_info and zk_queue_submit_vm takes a zk_program.)
+ * Jobs and provers.  Jobs start in submission order.  Among the idle provers a job takes the one whose last job had
+ * the same (trace length, program hash) -- column hints and fixed-column snapshots are kept per prover and per such
+ * key -- else the idle prover used least recently.  Queued jobs and idle provers are matched in one step, so resuming
+ * a paused queue that holds k <= P jobs marks k jobs running before any of them completes.
+ * Copied at submit: the 28 column pointers, *opt, *pub, the public and secret inputs and last_row.  What must stay
+ * valid until the job is done: the column data, d_trace, the program handle and the output buffers (proof_out, outputs,
+ * program_hash); after that the trace is not read, as with zk_prove.
+ * Argument checks.  Submit runs the blocking call's argument checks against the queue's sizes (null pointers, and for
+ * column and device jobs the trace length, options and lwe_size checks of zk_prove) and returns their code with their
+ * zk_last_error() text at once; no job is created.  zk_vm_prove's remaining checks are part of the VM run (the
+ * program's length against the prover, the input counts), so for a VM job only the null pointers are checked at submit.
+ * Everything that can only fail later arrives in the job's status and message: ZK_ERR_BUFFER_TOO_SMALL (proof_len then
+ * holds the needed size), ZK_ERR_TRACE, ZK_ERR_DEGREES, ZK_ERR_DEGREE, the VM's errors, device errors.
+ * Delivery.  zk_queue_wait and zk_queue_wait_any return ZK_OK once they have delivered a result, whatever the job's
+ * status, and set the caller's zk_last_error() to the job's message.  Each job is delivered exactly once; after that
+ * its id is unknown (ZK_ERR_INVALID_ARG); ids are never reused.  zk_queue_wait_any delivers jobs in the order they
+ * finished and returns ZK_ERR_INVALID_ARG when nothing is pending or undelivered.  zk_queue_poll is zk_queue_wait that
+ * returns ZK_ERR_PENDING instead of blocking.  The wait calls block on a condition variable; only the workers spin on
+ * the device.  zk_queue_cancel succeeds only on a job that has not started: it is then delivered with status
+ * ZK_ERR_CANCELLED, prover -1 and its buffers untouched; a running, finished or delivered job gives
+ * ZK_ERR_INVALID_ARG.  zk_queue_destroy cancels the queued jobs (their buffers stay untouched), waits for the running
+ * ones and drops every undelivered result.  All calls are thread-safe; destroy must be the last one.
+ * The provers of a queue come from and return to the process-wide pool: blocking calls on other provers, and other
+ * queues, keep working beside it.  A job is a proof like any other for the AUTO upload schedule, so a job that starts
+ * on an idle device takes the latency schedule.  One device per queue: a queue does not span devices, and sharded
+ * proofs (zk_prove_sharded) are not queue jobs. */
+typedef struct zk_queue zk_queue;
+typedef struct {
+    int32_t status;            /* what the blocking call would have returned; ZK_ERR_CANCELLED */
+    int32_t prover;            /* index 0 .. P-1 of the prover that ran it, -1 if none */
+    uint64_t proof_len;        /* bytes written; the needed size with ZK_ERR_BUFFER_TOO_SMALL */
+    float queued_ms, run_ms;   /* host wall time waiting for a prover / inside the call */
+    uint32_t running_at_start; /* jobs already running when this one started */
+    uint32_t _pad;
+    zk_proof_info info;        /* zk_prover_proof_info right after the call */
+    char message[512];         /* zk_last_error() of the worker thread after a failed call, truncated; else empty */
+} zk_job_result;
+
+int zk_queue_create(int device, size_t max_trace_len, uint32_t max_blowup, int provers, zk_queue **out);
+void zk_queue_destroy(zk_queue *q);
+/* zk_prover_set_validate / zk_prover_set_validate_degrees on every prover of the queue; refused (ZK_ERR_INVALID_ARG)
+ * while a job is queued or running. */
+int zk_queue_set_validate(zk_queue *q, int on);
+int zk_queue_set_validate_degrees(zk_queue *q, int on);
+/* pause: no job starts, running jobs finish; submit, cancel and the wait calls keep working.  resume: see above. */
+int zk_queue_pause(zk_queue *q);
+int zk_queue_resume(zk_queue *q);
+/* proof_cap: the capacity of proof_out (the blocking calls' *proof_len on entry); *job: the job's id. */
+int zk_queue_submit_columns(zk_queue *q, const uint8_t *const *columns, size_t n, const zk_options *opt,
+                            const zk_pub_inputs *pub, uint8_t *proof_out, size_t proof_cap, uint64_t *job);
+/* d_trace: a trace in the queue's device's HBM (any prover's zk_prover_trace_buffer, or the caller's own allocation) */
+int zk_queue_submit_device(zk_queue *q, const void *d_trace, size_t n, const zk_options *opt,
+                           const zk_pub_inputs *pub, uint8_t *proof_out, size_t proof_cap, uint64_t *job);
+/* zk_vm_prove; last_row may be NULL (drawn by the library), outputs and program_hash are optional */
+int zk_queue_submit_vm(zk_queue *q, zk_program *prog, const uint8_t *public_in, size_t num_public,
+                       const uint8_t *secret, size_t num_secret, uint32_t lwe_size, uint32_t delta,
+                       const uint8_t *last_row, const zk_options *opt, uint8_t *proof_out, size_t proof_cap,
+                       uint8_t *outputs, uint8_t *program_hash, uint64_t *job);
+int zk_queue_wait(zk_queue *q, uint64_t job, zk_job_result *res);
+int zk_queue_poll(zk_queue *q, uint64_t job, zk_job_result *res);
+int zk_queue_wait_any(zk_queue *q, uint64_t *job, zk_job_result *res);
+int zk_queue_cancel(zk_queue *q, uint64_t job);
+/* The validation / degree report of a job that has not been delivered yet (zk_prover_validation / zk_prover_degrees
+ * right after its call, kept with the job).  Both block until the job has finished, as zk_queue_wait does, and deliver
+ * nothing: the job is still there for a wait call.  ZK_ERR_INVALID_ARG for an unknown (or delivered) id and for a job
+ * during which that check did not run (the switch was off, the job was cancelled). */
+int zk_queue_job_validation(zk_queue *q, uint64_t job, zk_validation *out);
+int zk_queue_job_degrees(zk_queue *q, uint64_t job, zk_degrees *out);
+/* submitted: jobs accepted; completed: jobs a prover has finished (cancelled jobs are in neither `completed` nor
+ * `queued`); queued / running: now; peak_running: the most jobs running at once so far.  Any pointer may be NULL. */
+int zk_queue_stats(const zk_queue *q, uint64_t *submitted, uint64_t *completed, uint32_t *queued, uint32_t *running,
+                   uint32_t *peak_running);
 
 #ifdef __cplusplus
 }
